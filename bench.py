@@ -1,6 +1,16 @@
 """Benchmark: env-steps/sec of the vectorised rollout hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--horizon 200]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the
+workload, brings the GPU to its sustained clock (--prewarm-s), runs the W warmup
+steps, times the K steps, writes the last timed step's outputs (--dump-outputs;
+the prewarm then runs on a throwaway twin of the workload, so that the files are
+the same on every run) and prints one JSON line.  Everything else
+the benchmark measures (the phase breakdown, MFMA utilisation, training
+statistics, device memory, the k_step roofline and the CPU baseline below) is
+behind --full.
 
 One bench "step" = one training iteration of the hot path over one batch
 (BASELINE configs[1]: config_easy curriculum, dense reward, 4096 envs per
@@ -23,7 +33,7 @@ the advantage moments and one flat f32 gradient buffer per iteration; the
 timing uses a barrier + max-over-ranks.  value = all ranks' env steps / max
 time (weak scaling).
 
-Also measured in-process (HIP events on the launch stream):
+With --full, also measured in-process (HIP events on the launch stream):
   * roofline: the standalone step kernel (dxrl_env_step, k_step) at a large N
     (default 2^22 envs, traffic >> the 256 MB Infinity Cache) -- the
     "%HBM roofline step kernel" half of the BASELINE metric;
@@ -55,7 +65,7 @@ import dexterous_rl_manipulation_amd  # noqa: E402,F401  (the package alias)
 from dexterous_rl_manipulation_amd.workloads import WORKLOADS, build_pg_workload  # noqa: E402
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
@@ -73,6 +83,16 @@ def parse():
     p.add_argument("--minibatches", type=int, default=1, help="PPO minibatches per epoch")
     p.add_argument("--learner", choices=["pg", "simple"], default="pg",
                    help="pg: MLP actor-critic policy-gradient iteration (default); simple: SimpleLearner rollout")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (the trainer's updated "
+                        "parameters and its rollout / advantage tapes; for --learner simple the learner and env "
+                        "state) as DIR/<name>.npy in float32 / float64.  An array above 4 MiB is written as a "
+                        "fixed seeded sample of its rows (at most 64 MB in all).  The same arguments give the "
+                        "same inputs, and so the same files, on every run")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and report everything beside the headline figure: the per-phase breakdown, "
+                        "MFMA utilisation, training statistics, device memory, the k_step roofline and the CPU "
+                        "baseline (the last two can be switched off with --no-roofline / --no-cpu-baseline)")
     p.add_argument("--roofline-envs", type=int, default=1 << 22)
     p.add_argument("--roofline-launches", type=int, default=30)
     p.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -101,7 +121,8 @@ def parse():
                         "runs) or gloo (host-staged exchanges; ranks may share a GPU, rank r on GPU r mod the "
                         "visible count -- exercises the multi-rank harness on a one-GPU box, not a scaling "
                         "measurement)")
-    a = p.parse_args()
+    a = p.parse_args(argv)
+    a.argv = list(sys.argv[1:] if argv is None else argv)
     w = WORKLOADS[a.config]
     a.envs = a.envs or w["envs"]
     a.curriculum = a.curriculum or w["curriculum"]
@@ -125,7 +146,7 @@ def launch_ranks(args) -> int:
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-           "--master-addr=127.0.0.1", f"--master-port={port}", os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-addr=127.0.0.1", f"--master-port={port}", os.path.abspath(__file__)] + args.argv
     return subprocess.call(cmd, env=env)
 
 
@@ -188,6 +209,51 @@ BWD_BOTH = FWD_BOTH + 2 * (256 * 256 + 256 * 15) + 2 * (256 * 256 + 256)  # weig
 PEAK_BF16_TFS = 2500.0  # dense bf16 MFMA peak (MI355X_MICROARCH.md)
 
 
+DUMP_ARRAY_BYTES = 4 << 20  # per --dump-outputs file; a run writes fewer than 16 of them (64 MB in all)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_rows(rows, row_bytes, cap=DUMP_ARRAY_BYTES):
+    """The rows of an output that --dump-outputs writes: None (all of them) while the array fits
+    `cap` bytes, otherwise a fixed, sorted sample.  It depends on the shape alone, so every run
+    and every build of the project writes the same rows."""
+    keep = max(1, cap // row_bytes)
+    if rows <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, keep, replace=False))
+
+
+def host_output(t):
+    """A device tensor as the float32 / float64 host array --dump-outputs writes (the rows are
+    picked on the device, so a large tape is not copied whole)."""
+    t = t.detach()
+    if t.dim() == 0:
+        t = t.reshape(1)
+    dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+    row_bytes = (t[0].numel() if t.dim() > 1 else 1) * (8 if dt == torch.float64 else 4)
+    idx = dump_rows(t.shape[0], row_bytes)
+    if idx is not None:
+        t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+    return t.to(dt).cpu().numpy()
+
+
+def write_outputs(path, outputs, rank):
+    """DIR/<name>.npy per output (rank r > 0 of a multi-rank run: DIR/<name>.rank<r>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    assert sum(a.nbytes for a in outputs.values()) <= 64_000_000
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
+def pg_outputs(tr):
+    """What a caller of PGTrainer.iteration() holds afterwards: the updated parameters, the
+    rollout tape (observations incl. the bootstrap row, actions, log-probabilities, rewards,
+    dones), the critic's values and the advantages / returns the update was computed from."""
+    return {k: host_output(v) for k, v in (
+        ("params", tr.params), ("obs", tr.obs_rm), ("act", tr.act), ("logp", tr.logp), ("rew", tr.rew),
+        ("done", tr.done), ("values", tr.V[0]), ("adv", tr.adv), ("ret", tr.ret))}
+
+
 def pg_bench(args, world, rank, dev):
     """One bench step = one PGTrainer.iteration(): rollout (T env steps of every env, actor
     MLP fused) + critic forward + GAE + adv-norm + actor forward + heads + backward +
@@ -203,29 +269,37 @@ def pg_bench(args, world, rank, dev):
         kw["reserve_cus"] = args.reserve_cus
     if args.recompute_h2:
         kw["reuse_h2"] = False
-    env, tr = build_pg_workload(args.config, dev, rank=rank, world=world, process_group=pg, envs=args.envs,
-                                horizon=args.horizon, curriculum=args.curriculum, epochs=args.epochs,
-                                minibatches=args.minibatches, **kw)
+    def workload():
+        return build_pg_workload(args.config, dev, rank=rank, world=world, process_group=pg, envs=args.envs,
+                                 horizon=args.horizon, curriculum=args.curriculum, epochs=args.epochs,
+                                 minibatches=args.minibatches, **kw)
+
+    env, tr = workload()
     sc = tr.scheduler
     if args.sched_restart and sc is None:
         raise SystemExit("--sched-restart needs a workload with a curriculum scheduler (--config default)")
 
-    def one_iteration():
+    def one_iteration(env=env, tr=tr):
         if args.sched_restart:  # a fresh scheduler: level 0, empty window, the initial config on the device
-            sc.reset()
-            env.set_curriculum_async(sc.get_current_config())
+            tr.scheduler.reset()
+            env.set_curriculum_async(tr.scheduler.get_current_config())
         tr.iteration()
 
     # bring the GPU to its sustained clock first (not part of the W warmup steps or the timed K):
     # blocks of 8 iterations until the slowest rank has run for prewarm_s (every rank runs the
-    # same number of iterations, so their collectives pair up)
+    # same number of iterations, so their collectives pair up).  That count depends on the clock,
+    # so with --dump-outputs they run on a throwaway twin of the workload (same seeds, shapes and
+    # kernels): the state the W + K iterations start from, and with it the files written, is then
+    # the same on every run.
+    twin = workload() if args.dump_outputs and args.prewarm_s > 0 else (env, tr)
     prewarm_iters, tp, prewarm_s = 0, time.perf_counter(), 0.0
     while prewarm_s < args.prewarm_s:
         for _ in range(8):
-            one_iteration()
+            one_iteration(*twin)
         torch.cuda.synchronize(dev)
         prewarm_iters += 8
         prewarm_s = max_over_ranks(time.perf_counter() - tp, world, dev)
+    del twin
     for _ in range(args.warmup):
         one_iteration()
     torch.cuda.synchronize(dev)
@@ -245,6 +319,9 @@ def pg_bench(args, world, rank, dev):
     barrier(world)
     wall = time.perf_counter() - t0
     wall = max_over_ranks(wall, world, dev)
+    outputs = pg_outputs(tr) if args.dump_outputs else None  # before --full runs anything more
+    if not args.full:
+        return wall, outputs, {}
     # phase breakdown (one extra iteration, outside the timed region)
     stream = torch.cuda.current_stream(dev)
     names = tr.phases()
@@ -279,7 +356,7 @@ def pg_bench(args, world, rank, dev):
         stats["success_rule"] = tr.cfg.success_rule
     stats["prewarm"] = {"s": round(prewarm_s, 3), "iterations": prewarm_iters}
     stats.update({k: round(v, 5) for k, v in tr.loss_stats().items()})
-    return wall, phases, mfma, stats
+    return wall, outputs, {"phases_ms": phases, "mfma": mfma, "train_stats": stats}
 
 
 def rollout_bench(args, world, rank, dev):
@@ -308,10 +385,17 @@ def rollout_bench(args, world, rank, dev):
     wall = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps
     wall = max_over_ranks(wall, world, dev)
+    # what the fused rollout leaves its caller: the learner's and the envs' state
+    outputs = {k: host_output(v) for k, v in (
+        ("mean_action", learner.mean_action), ("best_reward", learner.best_reward),
+        ("episode_return", learner.episode_return), ("joint_positions", env.joint_positions),
+        ("object_position", env.object_position))} if args.dump_outputs else None
+    if not args.full:
+        return wall, outputs, {}
     # bookkeeping check outside the timed region
     rec = ro.run(args.horizon)
     assert rec.dropped == 0 and len(rec) > 0
-    return wall, kernel_ms
+    return wall, outputs, {"rollout_kernel_ms": round(kernel_ms, 4)}
 
 
 def step_kernel_time(n, launches, dev, seed=5):
@@ -446,20 +530,19 @@ def cpu_baseline(args):
                       f"core (tools/cpu_ratio.py, DESIGN.md §6)"}
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
     cpu = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)  # before the GPU is touched (spawned workers)
     world, rank, local = dist_setup(args)
     dev = torch.device("cuda", local if world > 1 else 0)
     backend = args.backend if world > 1 or args.dist else None
     total_steps = args.envs * world * args.horizon * args.steps
-    extra = {}
     if args.learner == "pg":
-        wall, phases, mfma, stats = pg_bench(args, world, rank, dev)
+        wall, outputs, extra = pg_bench(args, world, rank, dev)
         upd = ("1 epoch x 1 minibatch: ratio == 1, an A2C-style step" if args.epochs * args.minibatches == 1
                else f"{args.epochs} epochs x {args.minibatches} minibatches, one Adam step each (PPO extension: "
                     f"time-contiguous minibatch slices, order shuffled per epoch; the reference has no PPO, "
@@ -475,14 +558,12 @@ def main():
         coll = "RCCL" if backend == "nccl" else "gloo (host-staged)"
         par = (f"dp{world} (env shards; {coll} all-gather of the f64 advantage moments, all-reduce of the f32 "
                f"grads)" if backend else "dp1")
-        extra = {"phases_ms": phases, "mfma": mfma, "train_stats": stats}
     else:
-        wall, kernel_ms = rollout_bench(args, world, rank, dev)
+        wall, outputs, extra = rollout_bench(args, world, rank, dev)
         workload = (f"config_{args.curriculum}.json fused rollout: run_episode x SimpleLearner, dense reward, "
                     f"{args.horizon} env steps per bench step")
         dtype = "f32+f64"
         par = f"env-shard replicas x{world} (no collective)"
-        extra = {"rollout_kernel_ms": round(kernel_ms, 4)}
     value = total_steps / wall
     out = {
         "metric": "env-steps/sec @4096 envs/GPU, 1/2/4/8 MI355X; %HBM roofline step kernel",
@@ -501,11 +582,14 @@ def main():
                    "reuse_h2": not args.recompute_h2},
     }
     out.update(extra)
-    # peak torch-allocated device memory of the bench itself (trainer buffers, tapes), read
-    # before the roofline probe allocates its own
-    out["device_memory_gb"] = {"max_allocated": round(torch.cuda.max_memory_allocated(dev) / 1e9, 3),
-                               "max_reserved": round(torch.cuda.max_memory_reserved(dev) / 1e9, 3)}
-    if rank == 0 and not args.no_roofline:
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs, rank)
+    if args.full:
+        # peak torch-allocated device memory of the bench itself (trainer buffers, tapes; with
+        # --dump-outputs also the prewarm twin's), read before the roofline probe allocates its own
+        out["device_memory_gb"] = {"max_allocated": round(torch.cuda.max_memory_allocated(dev) / 1e9, 3),
+                                   "max_reserved": round(torch.cuda.max_memory_reserved(dev) / 1e9, 3)}
+    if args.full and rank == 0 and not args.no_roofline:
         out["roofline"] = step_kernel_roofline(args, dev)
         out["step_kernel_at_bench_envs"] = step_kernel_small(args.envs, dev)
     if rank == 0 and cpu is not None:

@@ -23,7 +23,7 @@ def test_bench_two_ranks_over_gloo(config):
     envs, horizon, steps = 1024, 64, 3
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--config", config,
            "--envs", str(envs), "--horizon", str(horizon), "--steps", str(steps), "--warmup", "1",
-           "--prewarm-s", "0.2", "--no-roofline", "--no-cpu-baseline"]
+           "--prewarm-s", "0.2", "--full", "--no-roofline", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -19,7 +19,7 @@ done
 for r in 1 2; do
   for v in bmold bmnew; do
     for c in easy variable_noise; do
-      DXRL_LIB=ab/lib$v.so timeout -k 10 120 python bench.py --config $c --no-cpu-baseline --no-roofline --steps 30 --warmup 3 > $O/b.log 2>&1 || exit 1
+      DXRL_LIB=ab/lib$v.so timeout -k 10 120 python bench.py --config $c --full --no-cpu-baseline --no-roofline --steps 30 --warmup 3 > $O/b.log 2>&1 || exit 1
       python3 -c "
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -16,7 +16,7 @@ for r in 1 2 3; do
 done
 for r in 1 2; do
   for v in base obsp4; do
-    DXRL_LIB=ab/lib$v.so timeout -k 10 120 python bench.py --config easy --no-cpu-baseline --no-roofline --steps 30 --warmup 3 > $O/b.log 2>&1 || exit 1
+    DXRL_LIB=ab/lib$v.so timeout -k 10 120 python bench.py --config easy --full --no-cpu-baseline --no-roofline --steps 30 --warmup 3 > $O/b.log 2>&1 || exit 1
     python3 -c "
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

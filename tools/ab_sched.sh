@@ -14,7 +14,7 @@ done
 for r in 1 2 3; do
   for v in $V; do
     DXRL_LIB=ab/lib$v.so CUR=easy timeout -k 10 120 python tools/rollout_time.py 2>&1 | grep -v amdgpu | sed "s/^/$v /" || exit 1
-    DXRL_LIB=ab/lib$v.so timeout -k 10 120 python bench.py --config easy --no-cpu-baseline --no-roofline --steps 30 --warmup 3 > $O/b.log 2>&1 || exit 1
+    DXRL_LIB=ab/lib$v.so timeout -k 10 120 python bench.py --config easy --full --no-cpu-baseline --no-roofline --steps 30 --warmup 3 > $O/b.log 2>&1 || exit 1
     python3 -c "
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
@@ -22,7 +22,7 @@ print(sys.argv[2], 'C2', round(d['value']/1e6,1), 'M', d['ms_per_step'], 'ms', d
   done
 done
 for v in $V; do
-  DXRL_LIB=ab/lib$v.so timeout -k 10 150 python bench.py --config easy --no-cpu-baseline --no-roofline --steps 15 --warmup 3 --epochs 4 --minibatches 4 > $O/b.log 2>&1 || exit 1
+  DXRL_LIB=ab/lib$v.so timeout -k 10 150 python bench.py --config easy --full --no-cpu-baseline --no-roofline --steps 15 --warmup 3 --epochs 4 --minibatches 4 > $O/b.log 2>&1 || exit 1
   python3 -c "
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

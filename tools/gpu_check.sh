@@ -22,10 +22,10 @@ for s in $STEPS; do
   case $s in
     pytest) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     configs) for c in default hard_heldout variable_noise; do
-               run bench_$c 300 python bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline --no-roofline
+               run bench_$c 300 python bench.py --config $c --steps 10 --warmup 2 --full --no-cpu-baseline --no-roofline
              done ;;
-    prof) run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline ;;
+    prof) run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline ;;
   esac
 done

@@ -38,29 +38,29 @@ if [ -z "${SKIP_PMC:-}" ]; then
 fi
 CFGS=${CFGS-easy default hard_heldout variable_noise}  # CFGS="" skips the per-config lines
 for c in $CFGS; do
-  if [ "$c" = easy ]; then step bench_$c 300 python bench.py; else
-    step bench_$c 200 python bench.py --config $c --no-cpu-baseline --no-roofline; fi
+  if [ "$c" = easy ]; then step bench_$c 300 python bench.py --full; else
+    step bench_$c 200 python bench.py --config $c --full --no-cpu-baseline --no-roofline; fi
   grep '^{' $O/bench_$c.log > $O/bench_$c.json
   step prof_$c 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$c -o run -- \
-    python3 bench.py --config $c --no-cpu-baseline $( [ "$c" = easy ] || echo --no-roofline )
+    python3 bench.py --config $c --full --no-cpu-baseline $( [ "$c" = easy ] || echo --no-roofline )
   grep '^{' $O/prof_$c.log > $O/prof_$c.json
 done
 # the extra lines: real PPO (4 epochs x 4 minibatches), C3 with progressions in every timed
 # iteration, C3 under the reference's training-loop success rule, the RCCL path at world 1
 if [ -z "${SKIP_EXTRA:-}" ]; then
-  step bench_easy_ppo4x4 200 python bench.py --epochs 4 --minibatches 4 --steps 10 --warmup 2 --no-cpu-baseline --no-roofline
+  step bench_easy_ppo4x4 200 python bench.py --epochs 4 --minibatches 4 --steps 10 --warmup 2 --full --no-cpu-baseline --no-roofline
   grep '^{' $O/bench_easy_ppo4x4.log > $O/bench_easy_ppo4x4.json
   step prof_easy_ppo4x4 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_easy_ppo4x4 -o run -- \
-    python3 bench.py --epochs 4 --minibatches 4 --steps 10 --warmup 2 --no-cpu-baseline --no-roofline
+    python3 bench.py --epochs 4 --minibatches 4 --steps 10 --warmup 2 --full --no-cpu-baseline --no-roofline
   grep '^{' $O/prof_easy_ppo4x4.log > $O/prof_easy_ppo4x4.json
   # the cold-start C2 line: no clock prewarm before the warmup iterations
-  step bench_easy_cold 200 python bench.py --prewarm-s 0 --no-cpu-baseline --no-roofline
+  step bench_easy_cold 200 python bench.py --prewarm-s 0 --full --no-cpu-baseline --no-roofline
   grep '^{' $O/bench_easy_cold.log > $O/bench_easy_cold.json
-  step bench_default_restart 200 python bench.py --config default --sched-restart --no-cpu-baseline --no-roofline
+  step bench_default_restart 200 python bench.py --config default --sched-restart --full --no-cpu-baseline --no-roofline
   grep '^{' $O/bench_default_restart.log > $O/bench_default_restart.json
-  step bench_default_training 200 python bench.py --config default --success-rule training --no-cpu-baseline --no-roofline
+  step bench_default_training 200 python bench.py --config default --success-rule training --full --no-cpu-baseline --no-roofline
   grep '^{' $O/bench_default_training.log > $O/bench_default_training.json
-  step bench_easy_dist 200 python bench.py --dist --no-cpu-baseline --no-roofline
+  step bench_easy_dist 200 python bench.py --dist --full --no-cpu-baseline --no-roofline
   grep '^{' $O/bench_easy_dist.log > $O/bench_easy_dist.json
   step eval_bench 200 python tools/eval_bench.py
   grep '^{' $O/eval_bench.log > $O/eval_bench.jsonl
