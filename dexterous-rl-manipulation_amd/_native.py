@@ -32,6 +32,7 @@ ABI_VERSION = 1
 EVAL_POLICY_SIMPLE = 0
 EVAL_POLICY_HEURISTIC = 1
 EVAL_POLICY_RANDOM = 2
+EVAL_POLICY_MLP = 3
 
 
 class Curriculum(C.Structure):
@@ -137,6 +138,10 @@ class EvalArgs(C.Structure):
                                           "policy_used", "status", "obs_traj", "act_traj", "work_queue")]
 
 
+class EvalMlp(C.Structure):
+    _fields_ = [("packed", C.c_void_p), ("params", C.c_void_p), ("action_std", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I32, _I64, _F64 = C.c_int32, C.c_int64, C.c_double
 _SIGS = {
@@ -180,6 +185,7 @@ _SIGS = {
     "dxrl_pg_rollout_kernel": (C.c_int, [C.c_void_p, _I32, C.POINTER(_I32)]),
     "dxrl_pg_gnorm_blocks": (C.c_int, [C.POINTER(_I32)]),
     "dxrl_evaluate": (C.c_int, [_P, C.POINTER(EvalArgs), _P]),
+    "dxrl_evaluate_mlp": (C.c_int, [_P, C.POINTER(EvalArgs), C.POINTER(EvalMlp), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

@@ -9,7 +9,7 @@
 // the env state, the frozen policy and both random streams live in registers
 // for the whole chain.  Records go out once per episode; the optional
 // per-step contact history is one byte per step.
-#include "dxrl_internal.h"
+#include "dxrl_eval.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,19 +17,6 @@
 using namespace dxrl;
 
 namespace dxrl {
-
-constexpr uint32_t kStreamEvalNoise = 0x45564e00u;
-
-struct EvalParams {
-    Weights w;
-    int max_episode_steps;  // env truncation (ME:245)
-    int dense;
-    int has_object;         // env constructed with object_position (ME:28, :156-161)
-    int n_curricula;
-    double obj[3];
-    dxrl_eval_args a;
-    unsigned long long* diag_iters;  // DXRL_EVAL_DIAG: step iterations executed per wave, summed
-};
 
 // Draw-by-draw reader over a tape row or a Philox stream.  Philox blocks are
 // consumed four u32 at a time: two 53-bit uniforms, or four f32 normals.
@@ -258,7 +245,6 @@ __global__ __launch_bounds__(64) void k_eval(const dxrl_curriculum* __restrict__
 // Every draw is the one k_eval takes (tape cursors advance by the step's draw count; Philox
 // blocks are addressed by their position in the lane's stream), so records, histories,
 // trajectories and tape consumption are identical (test_lane_split_eval_matches_one_lane_kernel).
-constexpr int kEvalRows = 16, kEvalThreads = 16 * kEvalRows;
 
 template <bool kTape>
 __global__ __launch_bounds__(kEvalThreads) void k_eval_ls(const dxrl_curriculum* __restrict__ curricula,

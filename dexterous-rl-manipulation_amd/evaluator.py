@@ -24,12 +24,17 @@ resolves random streams and assembles result dicts.  Two execution forms:
   draws (throughput form; distributionally equivalent, not the reference's
   numbers).
 
-The kernel compiles the reference's three policies (all obs-independent): a
-frozen SimpleLearner (its ``mean_action`` + exploration noise), HeuristicPolicy
-and RandomPolicy.  Any other object with ``select_action`` runs the same plan
-through the Gymnasium facade (device env steps, host policy calls, the
-reference's loop as written).  With a ``failure_logger``
-(failures.FailureLogger) the kernel also records observation / action
+The kernels compile the reference's three policies -- a frozen SimpleLearner
+(its ``mean_action`` + exploration noise), HeuristicPolicy and RandomPolicy
+(``dxrl_evaluate``) -- and the frozen MLP actor of ``PGTrainer``
+(``policies.MLPActorPolicy``: ``dxrl_evaluate_mlp``, the network on bf16 MFMA
+tiles inside the episode kernel, fed the observation the loop hands its policy).
+A deterministic MLP actor consumes no random draws, so its exact-order runs need
+no serial lane: every episode (Evaluator) or noise level (RobustnessTester) is a
+lane of its own, with identical results.  Any other object with
+``select_action`` runs the same plan through the Gymnasium facade (device env
+steps, host policy calls, the reference's loop as written).  With a
+``failure_logger`` (failures.FailureLogger) the kernel also records observation / action
 trajectories and every failed episode is logged as evaluator.py:101-179 does.
 """
 from __future__ import annotations
@@ -83,6 +88,18 @@ def _legacy_global(method: str) -> _HostStream:
     return _HostStream(peek, lambda k: getattr(np.random, method)(k))
 
 
+def _generator_normals(gen: np.random.Generator) -> _HostStream:
+    """Generator.standard_normal: the MLP actor's own stream (policies.MLPActorPolicy.rng)."""
+
+    def peek(n):
+        st = gen.bit_generator.state
+        v = gen.standard_normal(n)
+        gen.bit_generator.state = st
+        return v
+
+    return _HostStream(peek, lambda k: gen.standard_normal(k))
+
+
 def _generator_doubles(gen: np.random.Generator) -> _HostStream:
     """Generator.uniform(low, high) consumes one next_double per element (Box.sample)."""
 
@@ -102,6 +119,8 @@ class _PolicyProgram:
     sigma: float
     stream: _HostStream
     seeded: Any  # seed -> fresh per-episode stream tape of n values
+    mlp: Any = None  # EVAL_POLICY_MLP: the policies.MLPActorPolicy
+    draws: int = ACTION_DIM  # raw policy draws per step (0: a deterministic MLP actor)
 
 
 def compiled_program(policy) -> Optional[_PolicyProgram]:
@@ -115,6 +134,10 @@ def compiled_program(policy) -> Optional[_PolicyProgram]:
 def policy_program(policy) -> _PolicyProgram:
     """Map a reference policy object onto a DXRL_EVAL_POLICY_* program."""
     name = type(policy).__name__
+    from .policies import MLPActorPolicy
+    if isinstance(policy, MLPActorPolicy):
+        return _PolicyProgram(N.EVAL_POLICY_MLP, None, 0.0, _generator_normals(policy.rng), policy.seeded,
+                              mlp=policy, draws=0 if policy.deterministic else ACTION_DIM)
     space = getattr(policy, "action_space", None)
     if space is not None:
         low, high = np.asarray(space.low), np.asarray(space.high)
@@ -132,7 +155,7 @@ def policy_program(policy) -> _PolicyProgram:
         return _PolicyProgram(N.EVAL_POLICY_RANDOM, None, 0.0, _generator_doubles(space.np_random),
                               lambda s, n: _pcg(int(s)).random(n))
     raise TypeError(f"{name}: the device evaluator runs the reference's frozen SimpleLearner, HeuristicPolicy and "
-                    "RandomPolicy (obs-independent policies)")
+                    "RandomPolicy, and policies.MLPActorPolicy")
 
 
 # ------------------------------------------------------------------ episode programs
@@ -304,6 +327,13 @@ class EpisodeProgram:
         a.ep_contacts, a.contact_hist = N.ptr(out_con), N.ptr(out_hist)
         a.policy_used, a.status = N.ptr(used), N.ptr(status)
         a.obs_traj, a.act_traj, a.work_queue = N.ptr(o_traj), N.ptr(a_traj), N.ptr(queue)
+        mlp_t = ()
+        if prog.kind == N.EVAL_POLICY_MLP:
+            if prog.draws == 0 and policy_tapes is not None:
+                raise ValueError("a deterministic MLP actor consumes no draws: no policy tape")
+            packed, params, std = mlp_t = prog.mlp.device_tensors(dev)
+            m = N.EvalMlp()
+            m.packed, m.params, m.action_std = N.ptr(packed), N.ptr(params), N.ptr(std) if prog.draws else None
         with torch.cuda.device(dev):
             st = stream if stream is not None else torch.cuda.current_stream(dev)
             # the inputs were written on the current stream; the launch stream waits for them
@@ -311,15 +341,18 @@ class EpisodeProgram:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(st)
             for _ in range(max(1, int(repeat))):
-                N.call("dxrl_evaluate", env.handle, C.byref(a), st.cuda_stream)
+                if prog.kind == N.EVAL_POLICY_MLP:
+                    N.call("dxrl_evaluate_mlp", env.handle, C.byref(a), C.byref(m), st.cuda_stream)
+                else:
+                    N.call("dxrl_evaluate", env.handle, C.byref(a), st.cuda_stream)
             e1.record(st)
-        keep = (env, a, d_lane, d_seg, mean, d_pol, d_noise, d_reset, queue)  # alive until the stream is done
+        keep = (env, a, d_lane, d_seg, mean, d_pol, d_noise, d_reset, queue) + mlp_t  # alive until the stream is done
         outs = (out_ret, out_len, out_suc, out_con, out_hist, used, o_traj, a_traj)
         if st != torch.cuda.current_stream(dev):
             # allocated on the current stream, used on `st`: the caching allocator must not hand
             # these blocks out again before `st` has passed the launch, even if the _PendingRun
             # is dropped without result()
-            for x in outs + (status, d_lane, d_seg, mean, d_pol, d_noise, d_reset, queue, env._slab_owner):
+            for x in outs + (status, d_lane, d_seg, mean, d_pol, d_noise, d_reset, queue, env._slab_owner) + mlp_t:
                 if isinstance(x, torch.Tensor):
                     x.record_stream(st)
         return _PendingRun(st, e0, e1, max(1, int(repeat)), status, plan.props, keep_history, trajectories, outs,
@@ -414,16 +447,20 @@ class _PendingRun:
                            a_traj.cpu().numpy() if self.trajectories else None)
 
 
-def _exact_tape(prog: _PolicyProgram, program: EpisodeProgram) -> np.ndarray:
+def _exact_tape(prog: _PolicyProgram, program: EpisodeProgram) -> Optional[np.ndarray]:
+    if prog.draws == 0:
+        return None
     need = program.total_episodes * program.max_steps * ACTION_DIM
     if need > _MAX_TAPE:
         raise ValueError(f"exact-order evaluation would need a {need}-draw policy tape; use parallel=True")
     return prog.stream.draw(need)[None, :]
 
 
-def _seeded_tapes(prog: _PolicyProgram, program: EpisodeProgram, policy_seeds) -> np.ndarray:
+def _seeded_tapes(prog: _PolicyProgram, program: EpisodeProgram, policy_seeds) -> Optional[np.ndarray]:
     if len(policy_seeds) != len(program.lanes):
         raise ValueError("one policy seed per episode")
+    if prog.draws == 0:
+        return None
     return np.stack([prog.seeded(s, program.max_steps * ACTION_DIM) for s in policy_seeds])
 
 
@@ -552,7 +589,9 @@ class Evaluator:
         if not self._policy_frozen:
             self.freeze_policy()
         prog = compiled_program(self.policy)
-        p = self.heldout_program(num_episodes_per_object, seed, parallel and prog is not None)
+        # a program without draws has no serial stream to honour: exact order as one lane per episode
+        no_draws = prog is not None and prog.draws == 0
+        p = self.heldout_program(num_episodes_per_object, seed, (parallel or no_draws) and prog is not None)
         traj = self.failure_logger is not None
         if prog is None:  # host policy: the reference's sequential loop on the facade
             rec = p.run_facade(self.policy, trajectories=traj)
@@ -642,13 +681,18 @@ class RobustnessTester:
                     keys.append(("combined_noise", f"obs_{o:.3f}_dyn_{d:.3f}"))
         return levels, keys
 
-    def levels_program(self, levels, num_episodes: int, seed: Optional[int], parallel: bool) -> EpisodeProgram:
+    def levels_program(self, levels, num_episodes: int, seed: Optional[int], parallel: bool,
+                       lane_per_level: bool = False) -> EpisodeProgram:
         """One segment per noise level (a fresh base env, CombinedNoiseWrapper(seed)
         when a level is noisy, robustness_tests.py:266-278); exact order = one lane
-        through all levels, parallel = one lane (fresh env) per episode."""
+        through all levels (or, for a policy without draws, one lane per level: the
+        same episodes), parallel = one lane (fresh env) per episode."""
         p = EpisodeProgram([self.eval_config], self.reward_type, self.max_episode_steps, device=self.device)
         segs = [self._level_segment(o, d, num_episodes, seed) for o, d in levels]
-        if not parallel:
+        if not parallel and lane_per_level:
+            for s in segs:
+                p.add_lane([s])
+        elif not parallel:
             p.add_lane(segs)
         else:
             for s in segs:
@@ -659,7 +703,8 @@ class RobustnessTester:
 
     def _run_levels(self, levels, num_episodes, seed, parallel, policy_seeds, device_seed):
         prog = compiled_program(self.policy)
-        p = self.levels_program(levels, num_episodes, seed, parallel and prog is not None)
+        p = self.levels_program(levels, num_episodes, seed, parallel and prog is not None,
+                                lane_per_level=prog is not None and prog.draws == 0)
         if prog is None:  # host policy: the reference's sequential loop on the facade
             rec = p.run_facade(self.policy)
         elif not parallel:

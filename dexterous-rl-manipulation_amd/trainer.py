@@ -333,6 +333,12 @@ class PGTrainer:
         N.call("dxrl_pg_pack_weights", self.dev.index, N.ptr(self.params), N.ptr(self.packed), self._s())
         self._h2a_fresh = self._h2c_fresh = False  # new weights: the stored activations are stale
 
+    def policy(self, deterministic: bool = True, seed: Optional[int] = None):
+        """A snapshot of the current actor as a frozen policies.MLPActorPolicy (for Evaluator /
+        RobustnessTester, select_action and save): later updates do not change it."""
+        from .policies import MLPActorPolicy
+        return MLPActorPolicy.from_params(self.params, deterministic=deterministic, seed=seed)
+
     def _s(self):
         return N.stream_of(self.dev)
 

@@ -540,9 +540,10 @@ int dxrl_pg_gnorm_blocks(int32_t* blocks);
  * consecutive reset(seed) -> loop{select_action, step} episodes, each stopping
  * at terminated / truncated / max_steps with success = terminated
  * (evaluator.py:150-158, robustness_tests.py:288-303).  The policy is frozen
- * (evaluator.py:50-70: no update) and obs-independent, as every reference
- * policy is; its random stream runs on across the lane's segments, the noise
- * stream restarts with each segment's wrapper.
+ * (evaluator.py:50-70: no update): one of the reference's three, which never
+ * read the observation (dxrl_evaluate), or the MLP actor (dxrl_evaluate_mlp);
+ * its random stream runs on across the lane's segments, the noise stream
+ * restarts with each segment's wrapper.
  *
  * Exact reference order = ONE lane whose segments are the driver's loop (the
  * global np.random stream is consumed serially); the vectorised form = one lane
@@ -601,6 +602,34 @@ typedef struct dxrl_eval_args {
 } dxrl_eval_args;
 
 int dxrl_evaluate(dxrl_env* env, const dxrl_eval_args* args, void* stream);
+
+/* The same episode programs with the frozen MLP actor of the policy-gradient learner as the
+ * policy (no reference counterpart for the network; the loops are
+ * evaluator.py:71-181 / robustness_tests.py:240-310 as above).  At every step the action is
+ *   deterministic (action_std NULL):  a = clip(mu(obs), -1, 1), no policy draw, policy_used 0;
+ *   stochastic:                       a = clip(mu(obs) + nz, -1, 1) with, per action dim k,
+ *     tape mode    nz_k = f32(0 + (double)action_std[k] g_k), 15 raw normals of the lane's
+ *                  policy_tape per step;
+ *     device mode  nz_k = action_std[k] z_k from the lane's Philox policy stream (Box-Muller,
+ *                  addressed like DXRL_EVAL_POLICY_SIMPLE's),
+ * where mu = tanh(tanh(x W1^T) W2^T + b2) W3^T + b3 on bf16 MFMA tiles exactly as dxrl_pg_rollout
+ * computes it (the 16 env rows of a workgroup are one M = 16 tile; weights from `packed`, b2 / b3
+ * from `params`) and x is the bf16-rounded observation the loop hands its policy: the env's 45
+ * elements, inside a noisy segment plus the wrapper's observation noise f32(0 + std g)
+ * (robustness_tests.py:199-207) -- in tape mode the 45 normals per observation at the cursor
+ * positions dxrl_evaluate only skips, in device mode the segment's Philox noise stream.  The
+ * kernel evaluates no exp: the caller passes exp(log_std).  obs_traj holds the observation the
+ * policy saw (noisy when the segment is), act_traj the policy's clipped action.
+ * args keeps dxrl_evaluate's layout: args->policy must be DXRL_EVAL_POLICY_MLP, mean_action and
+ * exploration_noise are ignored, work_queue is required, and a policy_tape in deterministic mode
+ * is an error.  dxrl_evaluate itself does not accept DXRL_EVAL_POLICY_MLP. */
+#define DXRL_EVAL_POLICY_MLP 3
+typedef struct dxrl_eval_mlp {
+    const void*  packed;      /* bf16 pack of dxrl_pg_pack_weights (16-byte aligned)            */
+    const float* params;      /* f32 master (layer-2 / head biases)                              */
+    const float* action_std;  /* f32 [15]; NULL = deterministic (no policy draws)                */
+} dxrl_eval_mlp;
+int dxrl_evaluate_mlp(dxrl_env* env, const dxrl_eval_args* args, const dxrl_eval_mlp* mlp, void* stream);
 
 #ifdef __cplusplus
 }
