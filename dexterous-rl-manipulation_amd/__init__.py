@@ -4,7 +4,9 @@ Drop-in surfaces (same names as the reference modules):
   envs.DexterousManipulationEnv, rewards.{RewardShaping,SparseReward},
   policies.{SimpleLearner,RandomPolicy,HeuristicPolicy}, training.{run_episode,run_training_episode},
   experiments.{CurriculumConfig,CurriculumScheduler,StepBasedScheduler,ExperimentConfig,load_config,...},
-  evaluation.{HeldOutObjectSet,CombinedNoiseWrapper,Evaluator,RobustnessTester,EvaluationMetrics,...}
+  evaluation.{HeldOutObjectSet,CombinedNoiseWrapper,Evaluator,RobustnessTester,EvaluationMetrics,...},
+  ablation.{train_with_config,run_component_ablation,...},
+  curriculum_ablation.{train_with_curriculum,train_without_curriculum,compute_convergence_metrics,run_ablation_study}
 Batched device API: envs.VecEnv, policies.VecSimpleLearner, training.SimpleLearnerRollout.
 The compute runs in libdxrl.so (HIP, gfx950; C ABI in include/dxrl.h).  No CPU fallback.
 """
@@ -17,6 +19,6 @@ __version__ = "0.1.0"
 def __getattr__(name):
     import importlib
     if name in ("envs", "policies", "training", "evaluation", "build", "_native", "trainer",
-                "evaluator", "metrics"):
+                "evaluator", "metrics", "curriculum_ablation"):
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -74,6 +74,27 @@ class RolloutIO(C.Structure):
                 ("episode_budget", C.c_void_p)]
 
 
+STUDY_MAX_GROUPS = 16      # DXRL_STUDY_MAX_GROUPS
+STUDY_MAX_MILESTONES = 64  # DXRL_STUDY_MAX_MILESTONES
+STUDY_FIXED, STUDY_SUCCESS_WINDOW, STUDY_STEP_MILESTONES = 0, 1, 2
+
+
+class StudyGroup(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("window", C.c_int32), ("min_successes", C.c_int32),
+                ("num_levels", C.c_int32), ("first_row", C.c_int32), ("num_milestones", C.c_int32),
+                ("min_episodes", C.c_int64), ("milestones", C.c_int64 * STUDY_MAX_MILESTONES)]
+
+
+class StudyLayout(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("total_bytes", "window_mask", "total_steps", "total_episodes", "level",
+                                         "milestone")]
+
+
+class StudyArgs(C.Structure):
+    _fields_ = [("groups", C.c_void_p), ("num_groups", C.c_int32), ("lane_group", C.c_void_p),
+                ("sched_state", C.c_void_p), ("ep_level", C.c_void_p), ("lane_stream", C.c_void_p)]
+
+
 class PgRolloutArgs(C.Structure):
     _fields_ = [("horizon", C.c_int32), ("max_steps", C.c_int32), ("policy_seed", C.c_uint64),
                 ("iteration", C.c_uint64), ("obs_noise_std", C.c_double), ("dyn_noise_std", C.c_double)] + \
@@ -165,6 +186,11 @@ _SIGS = {
     "dxrl_learner_update": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_double, C.c_double, _P, _P, _P, _P]),
     "dxrl_rollout_simple": (C.c_int, [_P, _P, C.POINTER(LearnerConfig), C.c_int32, C.c_int32, C.c_int32,
                                       C.POINTER(RolloutIO), _P]),
+    "dxrl_study_layout_for": (C.c_int, [C.c_int32, C.POINTER(StudyLayout)]),
+    "dxrl_study_init": (C.c_int, [C.c_int32, C.c_int32, _P, _P]),
+    "dxrl_study_set_groups": (C.c_int, [_P, C.POINTER(StudyGroup), C.c_int32, _P, _P]),
+    "dxrl_rollout_curriculum": (C.c_int, [_P, _P, C.POINTER(LearnerConfig), C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(RolloutIO), C.POINTER(StudyArgs), _P]),
     "dxrl_gemm_bf16": (C.c_int, [_I32, _P, _I64, _P, _I64, _I64, _I32, _I32, _P, _I64, _I32, _P, _I64, _P, _I64,
                                  _P, _I64, _P, _I64, _P, _I64, _I32, _P, _P]),
     "dxrl_wgrad_bf16": (C.c_int, [_I32, _P, _I64, _I32, _P, _I64, _I32, _I64, _I32, _P, _P, _P]),

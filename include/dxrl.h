@@ -223,6 +223,82 @@ int dxrl_rollout_simple(dxrl_env* env, void* learner_state, const dxrl_learner_c
                         const dxrl_rollout_io* io, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Curriculum-ablation study (evaluation/curriculum_ablation.py:25-134): dxrl_rollout_simple
+ * with one CurriculumScheduler per lane, applied on the device where the lane's episodes end,
+ * so a run whose difficulty changes between two of its own episodes -- and a whole study of
+ * thousands of such runs, both arms -- is one launch.
+ *
+ * A lane belongs to a GROUP (an arm of the study).  The group names the progression rule and
+ * the rows first_row .. first_row + num_levels of the env's curriculum table that hold the
+ * arm's levels: the host builds them by stepping a real scheduler (_progress /
+ * _interpolate_config, experiments/curriculum_scheduler.py:90-139,188-222), so no f64 level
+ * arithmetic runs on the device.  At every episode end the lane runs scheduler.update(success,
+ * steps) (curriculum_scheduler.py:141-161) in integers; on a progression its env's row becomes
+ * first_row + level, read by the next reset exactly as `env.curriculum_config =
+ * scheduler.get_current_config()` (curriculum_ablation.py:67-68) is.
+ * ------------------------------------------------------------------------ */
+#define DXRL_STUDY_MAX_GROUPS 16
+#define DXRL_STUDY_MAX_MILESTONES 64
+#define DXRL_STUDY_FIXED 0           /* no scheduler: train_without_curriculum (curriculum_ablation.py:86-134) */
+#define DXRL_STUDY_SUCCESS_WINDOW 1  /* CurriculumScheduler._should_progress (curriculum_scheduler.py:163-186)  */
+#define DXRL_STUDY_STEP_MILESTONES 2 /* StepBasedScheduler._should_progress  (curriculum_scheduler.py:304-310)  */
+
+/* One arm's scheduler constants (the CurriculumScheduler constructor arguments,
+ * curriculum_scheduler.py:22-57, :284-302, reduced to integers by the host). */
+typedef struct dxrl_study_group {
+    int32_t mode;           /* DXRL_STUDY_*                                                      */
+    int32_t window;         /* window_size, 1..64 (SUCCESS_WINDOW)                               */
+    int32_t min_successes;  /* smallest count c with c / window >= success_rate_threshold in f64
+                               (np.mean of the window's bools, :182-186); 0 when the threshold is
+                               <= 0, window + 1 when no count reaches it                          */
+    int32_t num_levels;     /* progressions that raise the level (:195-222): the lane stops at
+                               level num_levels, where current_difficulty_level >= 1.0 (:175)     */
+    int32_t first_row;      /* curriculum-table row of level 0; level k is row first_row + k      */
+    int32_t num_milestones; /* STEP_MILESTONES: == num_levels, <= DXRL_STUDY_MAX_MILESTONES       */
+    int64_t min_episodes;   /* min_episodes_before_progression (:171)                             */
+    int64_t milestones[DXRL_STUDY_MAX_MILESTONES]; /* sorted step_milestones (:301)               */
+} dxrl_study_group;
+
+/* Byte offsets of the per-lane scheduler state (device slab, 256-B aligned); persists across
+ * calls like the env and learner slabs.  The fields of CurriculumScheduler.reset (:265-273). */
+typedef struct dxrl_study_layout {
+    int64_t total_bytes;
+    int64_t window_mask;    /* u64 [N] episode_successes, newest episode in bit 0                 */
+    int64_t total_steps;    /* i64 [N]                                                           */
+    int64_t total_episodes; /* i32 [N]                                                           */
+    int64_t level;          /* i32 [N] level index k (current_difficulty_level = the host's table[k]) */
+    int64_t milestone;      /* i32 [N] current_milestone_idx (:302)                               */
+} dxrl_study_layout;
+
+typedef struct dxrl_study_args {
+    const dxrl_study_group* groups; /* DEVICE [num_groups], written by dxrl_study_set_groups      */
+    int32_t num_groups;
+    const int32_t* lane_group;      /* device i32 [N] group of each lane                          */
+    void* sched_state;              /* device slab of dxrl_study_layout_for(N)                     */
+    int32_t* ep_level;              /* device i32 [N][record_cap] (nullable): the level index after
+                                       that episode's update -- difficulty_levels.append(
+                                       scheduler.get_difficulty_level()) (curriculum_ablation.py:73) */
+    const int64_t* lane_stream;     /* device i64 [N] (nullable = global_env_offset + lane): the id
+                                       that keys the lane's Philox streams, so a run's streams do
+                                       not depend on the lane it occupies                          */
+} dxrl_study_args;
+
+int dxrl_study_layout_for(int32_t num_envs, dxrl_study_layout* out);
+/* CurriculumScheduler.reset() for every lane (curriculum_scheduler.py:265-273). */
+int dxrl_study_init(int32_t device, int32_t num_envs, void* sched_state, void* stream);
+/* Checks the groups (host array) against the env's curriculum table and copies them to
+ * groups_dev (device, num_groups entries); returns after the copy completed. */
+int dxrl_study_set_groups(const dxrl_env* env, const dxrl_study_group* groups, int32_t num_groups,
+                          void* groups_dev, void* stream);
+/* dxrl_rollout_simple (same tapes / Philox streams, rewards, success rules, episode_budget,
+ * record_cap, gauss_used, resumable state) with the lanes' schedulers.  A DXRL_STUDY_FIXED lane
+ * computes what dxrl_rollout_simple computes, bit for bit.  Status word: bit 0 a tape ran out,
+ * bit 1 a lane's group or row lies outside its table (the lane then does not progress). */
+int dxrl_rollout_curriculum(dxrl_env* env, void* learner_state, const dxrl_learner_config* lcfg,
+                            int32_t num_steps, int32_t max_steps, int32_t success_rule,
+                            const dxrl_rollout_io* io, const dxrl_study_args* study, void* stream);
+
+/* ------------------------------------------------------------------------
  * bf16 MFMA GEMM used by the actor-critic learner (no reference counterpart;
  * exported for tests and diagnostics).  C[M][N] = epi(A[M][K] . Bt[N][K]^T):
  * bias (bias[n*bias_stride]), act (0 identity / 1 tanh), gate (multiply by
