@@ -6,7 +6,8 @@ Drop-in surfaces (same names as the reference modules):
   experiments.{CurriculumConfig,CurriculumScheduler,StepBasedScheduler,ExperimentConfig,load_config,...},
   evaluation.{HeldOutObjectSet,CombinedNoiseWrapper,Evaluator,RobustnessTester,EvaluationMetrics,...},
   ablation.{train_with_config,run_component_ablation,...},
-  curriculum_ablation.{train_with_curriculum,train_without_curriculum,compute_convergence_metrics,run_ablation_study}
+  curriculum_ablation.{train_with_curriculum,train_without_curriculum,compute_convergence_metrics,run_ablation_study},
+  seed_variance.{SeedVarianceAnalyzer,analyze_seed_variance,plot_seed_variance,print_variance_report,run_seed_variance}
 Batched device API: envs.VecEnv, policies.VecSimpleLearner, training.SimpleLearnerRollout.
 The compute runs in libdxrl.so (HIP, gfx950; C ABI in include/dxrl.h).  No CPU fallback.
 """
@@ -19,6 +20,6 @@ __version__ = "0.1.0"
 def __getattr__(name):
     import importlib
     if name in ("envs", "policies", "training", "evaluation", "build", "_native", "trainer",
-                "evaluator", "metrics", "curriculum_ablation"):
+                "evaluator", "metrics", "curriculum_ablation", "seed_variance"):
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

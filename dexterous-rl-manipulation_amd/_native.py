@@ -163,8 +163,19 @@ class EvalMlp(C.Structure):
     _fields_ = [("packed", C.c_void_p), ("params", C.c_void_p), ("action_std", C.c_void_p)]
 
 
+SUMMARY_MAX_STEPS = 4096  # DXRL_SUMMARY_MAX_STEPS (metrics._EXACT_VAR_MAX_N)
+
+
+class EvalSummaryArgs(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("total_episodes", "max_steps", "success_threshold", "num_groups",
+                                         "num_members", "tie_cap")] + \
+               [(k, C.c_void_p) for k in ("ep_length", "ep_success", "ep_contacts", "ep_return", "contact_hist",
+                                          "group_offsets", "group_episodes", "ep_work", "ep_code", "ep_moments",
+                                          "group_stats", "group_return", "tie_count", "tie_list", "status")]
+
+
 _P = C.c_void_p
-_I32, _I64, _F64 = C.c_int32, C.c_int64, C.c_double
+_I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
 _SIGS = {
     "dxrl_abi_version": (C.c_int, []),
     "dxrl_last_error": (C.c_char_p, []),
@@ -212,6 +223,7 @@ _SIGS = {
     "dxrl_pg_gnorm_blocks": (C.c_int, [C.POINTER(_I32)]),
     "dxrl_evaluate": (C.c_int, [_P, C.POINTER(EvalArgs), _P]),
     "dxrl_evaluate_mlp": (C.c_int, [_P, C.POINTER(EvalArgs), C.POINTER(EvalMlp), _P]),
+    "dxrl_eval_summarize": (C.c_int, [_I32, C.POINTER(EvalSummaryArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

@@ -12,7 +12,8 @@
   rollout kernel instead.
 * ``Evaluator`` / ``RobustnessTester`` (evaluator.py) and ``EvaluationMetrics`` /
   ``FailureType`` / ``format_metrics_report`` (metrics.py) are re-exported here
-  under the reference's module path (evaluation/__init__.py).
+  under the reference's module path (evaluation/__init__.py), as are
+  ``SeedVarianceAnalyzer`` / ``analyze_seed_variance`` (seed_variance.py).
 """
 from __future__ import annotations
 
@@ -205,7 +206,9 @@ class CombinedNoiseWrapper(_NoiseBase):
 _LAZY = {"Evaluator": "evaluator", "RobustnessTester": "evaluator", "EvaluationMetrics": "metrics",
          "FailureType": "metrics", "format_metrics_report": "metrics", "FailureMode": "failures",
          "FailureModeDefinition": "failures", "FAILURE_MODE_DEFINITIONS": "failures", "FailureClassifier": "failures",
-         "FailureLogger": "failures", "EpisodeRecorder": "failures"}
+         "FailureLogger": "failures", "EpisodeRecorder": "failures", "SeedVarianceAnalyzer": "seed_variance",
+         "analyze_seed_variance": "seed_variance", "plot_seed_variance": "seed_variance",
+         "print_variance_report": "seed_variance"}
 
 
 def __getattr__(name):

@@ -36,6 +36,13 @@ lane of its own, with identical results.  Any other object with
 steps, host policy calls, the reference's loop as written).  With a
 ``failure_logger`` (failures.FailureLogger) the kernel also records observation / action
 trajectories and every failed episode is logged as evaluator.py:101-179 does.
+
+``device_summary=True`` (``EpisodeProgram.launch(groups=...)``) leaves the episode
+records on the device: ``dxrl_eval_summarize`` (csrc/dxrl_eval_summary.hip) runs
+behind the episode kernel on its stream, applies the failure rules of metrics.py
+per episode and reduces the aggregates per group of a CSR group table, and only
+the group tables, the rows whose variance is exactly 2.0 (np.var settles those,
+``settle_ties``) and ``policy_used`` cross to the host (``EvalSummary``).
 """
 from __future__ import annotations
 
@@ -48,7 +55,8 @@ import torch
 
 from . import _native as N
 from .envs import ACTION_DIM, RESET_SLOTS, VecEnv, resolve_reset_draws
-from .metrics import EvaluationMetrics, HistoryMoments, aggregate_columns, classify_columns, failure_names
+from .metrics import (FAILURE_CODES, EvaluationMetrics, HistoryMoments, aggregate_columns, aggregate_sums,
+                      classify_columns, failure_names)
 
 OBS_DIM = 45
 _MAX_TAPE = 1 << 26  # f64 draws per host tape (512 MB); beyond it use parallel=True
@@ -277,18 +285,27 @@ class EpisodeProgram:
 
     def run(self, prog: _PolicyProgram, policy_tapes: Optional[np.ndarray] = None, host_resets: bool = True,
             host_noise: bool = True, device_seed: int = 0, keep_history: bool = True,
-            repeat: int = 1, timing: Optional[Dict] = None, trajectories: bool = False) -> EvalRecords:
+            repeat: int = 1, timing: Optional[Dict] = None, trajectories: bool = False,
+            groups: Optional[Sequence[Sequence[int]]] = None):
         """Launch the plan (``repeat`` back-to-back launches; ``timing['kernel_ms']`` =
-        HIP-event time per launch on the launch stream)."""
+        HIP-event time per launch on the launch stream).  With ``groups`` (episode-index lists)
+        the records are reduced on the device and an ``EvalSummary`` comes back instead of
+        ``EvalRecords`` (``timing['summary_ms']`` = event time of the two summary launches)."""
         return self.launch(prog, policy_tapes, host_resets, host_noise, device_seed, keep_history, repeat,
-                           trajectories).result(timing)
+                           trajectories, groups=groups).result(timing)
 
     def launch(self, prog: _PolicyProgram, policy_tapes: Optional[np.ndarray] = None, host_resets: bool = True,
                host_noise: bool = True, device_seed: int = 0, keep_history: bool = True, repeat: int = 1,
-               trajectories: bool = False, stream: Optional[torch.cuda.Stream] = None) -> "_PendingRun":
+               trajectories: bool = False, stream: Optional[torch.cuda.Stream] = None,
+               groups: Optional[Sequence[Sequence[int]]] = None):
         """Enqueue the plan on ``stream`` (default: the device's current stream) without waiting;
         ``.result()`` synchronises and returns the records.  Every launch owns its buffers,
-        including the work-queue counter, so launches on different streams may overlap."""
+        including the work-queue counter, so launches on different streams may overlap.
+        With ``groups``, ``dxrl_eval_summarize`` is enqueued behind the last launch and
+        ``.result()`` returns an ``EvalSummary``: only the group tables and the tie rows cross
+        to the host, ``contact_hist`` stays on the device."""
+        if groups is not None and (trajectories or not keep_history):
+            raise ValueError("a device summary reads contact_hist and returns no trajectories")
         plan = self.plan(host_resets, host_noise)
         dev = self.device = N.require_gpu(self.device)
         nl, E = len(self.lanes), plan.total_episodes
@@ -334,6 +351,9 @@ class EpisodeProgram:
             packed, params, std = mlp_t = prog.mlp.device_tensors(dev)
             m = N.EvalMlp()
             m.packed, m.params, m.action_std = N.ptr(packed), N.ptr(params), N.ptr(std) if prog.draws else None
+        summary = None
+        if groups is not None:
+            summary = _prepare_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out_hist)
         with torch.cuda.device(dev):
             st = stream if stream is not None else torch.cuda.current_stream(dev)
             # the inputs were written on the current stream; the launch stream waits for them
@@ -346,6 +366,8 @@ class EpisodeProgram:
                 else:
                     N.call("dxrl_evaluate", env.handle, C.byref(a), st.cuda_stream)
             e1.record(st)
+            if summary is not None:
+                _enqueue_summary(summary, dev, st)
         keep = (env, a, d_lane, d_seg, mean, d_pol, d_noise, d_reset, queue) + mlp_t  # alive until the stream is done
         outs = (out_ret, out_len, out_suc, out_con, out_hist, used, o_traj, a_traj)
         if st != torch.cuda.current_stream(dev):
@@ -355,6 +377,10 @@ class EpisodeProgram:
             for x in outs + (status, d_lane, d_seg, mean, d_pol, d_noise, d_reset, queue, env._slab_owner) + mlp_t:
                 if isinstance(x, torch.Tensor):
                     x.record_stream(st)
+            for x in (summary.tensors if summary is not None else ()):
+                x.record_stream(st)
+        if summary is not None:
+            return _PendingSummary(st, e0, e1, max(1, int(repeat)), status, used, outs, keep, summary)
         return _PendingRun(st, e0, e1, max(1, int(repeat)), status, plan.props, keep_history, trajectories, outs,
                            keep, E)
 
@@ -445,6 +471,137 @@ class _PendingRun:
                            p[:, 0], p[:, 1], p[:, 2], used.cpu().numpy(),
                            o_traj.cpu().numpy() if self.trajectories else None,
                            a_traj.cpu().numpy() if self.trajectories else None)
+
+
+# ------------------------------------------------------------------ device summaries
+def group_table(groups: Sequence[Sequence[int]]):
+    """CSR form of a list of episode-index lists: (offsets i32 [G + 1], members i32)."""
+    rows = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+    off = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=off[1:])
+    if off[-1] >= 2**31:
+        raise ValueError("group table too large")
+    mem = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    return off.astype(np.int32), mem.astype(np.int32)
+
+
+@dataclass
+class EvalSummary:
+    """What crosses to the host after ``dxrl_eval_summarize``: the group tables (tie rows
+    already settled by np.var, see ``settle_ties``), the tie rows and ``policy_used``."""
+    group_stats: np.ndarray    # i64 [G][16]  (include/dxrl.h)
+    group_return: np.ndarray   # f64 [G][3]   count, mean, M2 of ep_return
+    tie_rows: np.ndarray       # i32 episode indices whose variance is exactly 2.0 in integers
+    tie_unstable: np.ndarray   # bool, np.var(row) > 2.0 of each tie row
+    policy_used: np.ndarray
+    host_bytes: int = 0        # bytes copied device -> host for this result
+
+    def metrics(self, g: int) -> Dict:
+        """The aggregate_columns dict of group g (no reward keys: the reference's has none)."""
+        return aggregate_sums(self.group_stats[g])
+
+    def mean_reward(self, g: int) -> float:
+        return float(self.group_return[g, 1])
+
+    def std_reward(self, g: int) -> float:
+        n, _, m2 = self.group_return[g]
+        return float(np.sqrt(m2 / n)) if n else float("nan")
+
+
+def settle_ties(group_stats: np.ndarray, offsets: np.ndarray, members: np.ndarray, tie_rows, tie_codes,
+                tie_hist, tie_len) -> np.ndarray:
+    """The host half of the variance rule: for every tie row np.var itself decides (its rounding
+    does, metrics.py:74-77); where it says unstable, one count moves from the row's provisional
+    failure code to UNSTABLE_CONTACTS in each group that holds the episode.  Returns the
+    per-row decisions; ``group_stats`` is updated in place."""
+    unstable_code = FAILURE_CODES["unstable_contacts"]
+    out = np.zeros(len(tie_rows), bool)
+    for k, e in enumerate(tie_rows):
+        out[k] = bool(np.var(np.asarray(tie_hist[k][:int(tie_len[k])], dtype=np.int64)) > 2.0)
+        if not out[k]:
+            continue
+        for m in np.flatnonzero(members == e):
+            g = int(np.searchsorted(offsets, m, side="right")) - 1
+            group_stats[g, 7 + int(tie_codes[k])] -= 1
+            group_stats[g, 7 + unstable_code] += 1
+    return out
+
+
+class _Summary:
+    """Device buffers of one enqueued dxrl_eval_summarize."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def tensors(self):
+        return [v for v in self.__dict__.values() if isinstance(v, torch.Tensor)]
+
+
+def _prepare_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out_hist, success_threshold=3,
+                     tie_cap=None):
+    """Group table upload and output buffers of a summary, made before the episode launch so
+    that nothing but the call itself sits between the episode kernel and the summary launches."""
+    off, mem = group_table(groups)
+    G = len(off) - 1
+    t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    z = lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
+    cap = max(1, E) if tie_cap is None else int(tie_cap)
+    s = _Summary(off=off, mem=mem, E=E, ms=ms, d_off=t(off), d_mem=t(mem) if len(mem) else None,
+                 work=z(max(1, E), dt=torch.uint8), code=z(max(1, E), dt=torch.int8),
+                 stats=z(max(1, G), 16, dt=torch.int64), ret=z(max(1, G), 3, dt=torch.float64),
+                 flags=z(2, dt=torch.int32), ties=z(cap, dt=torch.int32), hist=out_hist, length=out_len)
+    a = N.EvalSummaryArgs()
+    a.total_episodes, a.max_steps, a.success_threshold, a.num_groups = E, ms, success_threshold, G
+    a.num_members, a.tie_cap = len(mem), cap
+    a.ep_length, a.ep_success, a.ep_contacts = N.ptr(out_len), N.ptr(out_suc), N.ptr(out_con)
+    a.ep_return, a.contact_hist = N.ptr(out_ret), N.ptr(out_hist)
+    a.group_offsets, a.group_episodes = N.ptr(s.d_off), N.ptr(s.d_mem)
+    a.ep_work, a.ep_code, a.ep_moments = N.ptr(s.work), N.ptr(s.code), None
+    a.group_stats, a.group_return = N.ptr(s.stats), N.ptr(s.ret)
+    a.status, a.tie_count, a.tie_list = s.flags.data_ptr(), s.flags.data_ptr() + 4, N.ptr(s.ties)
+    s.e2 = torch.cuda.Event(enable_timing=True)
+    s.args = a
+    return s
+
+
+def _enqueue_summary(s, dev, st):
+    N.call("dxrl_eval_summarize", dev.index, C.byref(s.args), st.cuda_stream)
+    s.e2.record(st)
+
+
+class _PendingSummary:
+    """An enqueued episode launch with its summary behind it; result() waits for the stream."""
+
+    def __init__(self, stream, e0, e1, repeat, status, used, outs, keep, summary):
+        self.stream, self.e0, self.e1, self.repeat = stream, e0, e1, repeat
+        self.status, self.used, self.outs, self.keep, self.summary = status, used, outs, keep, summary
+
+    def result(self, timing: Optional[Dict] = None) -> EvalSummary:
+        self.stream.synchronize()
+        s = self.summary
+        if timing is not None:
+            timing["kernel_ms"] = self.e0.elapsed_time(self.e1) / self.repeat
+            timing["summary_ms"] = self.e1.elapsed_time(s.e2)
+        if int(self.status.item()):
+            raise N.NativeError("dxrl_evaluate: a parity tape ran out or a segment was malformed")
+        self.keep[0].close()
+        flags = s.flags.cpu().numpy()
+        if int(flags[0]):
+            raise N.NativeError(f"dxrl_eval_summarize: status {int(flags[0])} (group table out of range)")
+        stats, ret, used = s.stats.cpu().numpy(), s.ret.cpu().numpy(), self.used.cpu().numpy()
+        nbytes = 4 + flags.nbytes + stats.nbytes + ret.nbytes + used.nbytes
+        nt = int(flags[1])
+        ties, unstable = np.zeros(0, np.int32), np.zeros(0, bool)
+        if nt:  # only those rows' histories cross to the host
+            idx = s.ties[:nt]
+            ties = idx.cpu().numpy()
+            li = idx.long()
+            codes, hist, length = s.code[li].cpu().numpy(), s.hist[li].cpu().numpy(), s.length[li].cpu().numpy()
+            nbytes += ties.nbytes + codes.nbytes + hist.nbytes + length.nbytes
+            unstable = settle_ties(stats, s.off, s.mem, ties, codes, hist, length)
+        G = len(s.off) - 1
+        return EvalSummary(stats[:G], ret[:G], ties, unstable, used, nbytes)
 
 
 def _exact_tape(prog: _PolicyProgram, program: EpisodeProgram) -> Optional[np.ndarray]:
@@ -584,25 +741,42 @@ class Evaluator:
 
     def evaluate_heldout_set(self, num_episodes_per_object: int = 5, seed: Optional[int] = None,
                              parallel: bool = False, policy_seeds: Optional[Sequence[int]] = None,
-                             device_seed: int = 0, return_episodes: bool = True) -> Dict:
-        """evaluator.py:183-262 (see heldout_program for the episode layout)."""
+                             device_seed: int = 0, return_episodes: bool = True,
+                             device_summary: bool = False, timing: Optional[Dict] = None) -> Dict:
+        """evaluator.py:183-262 (see heldout_program for the episode layout).
+
+        ``device_summary=True`` reduces the episode records on the device
+        (``dxrl_eval_summarize``: one group per object plus one overall) and builds the same
+        result dict from the group tables; no per-episode data crosses to the host, so it
+        requires ``return_episodes=False`` and no ``failure_logger``."""
+        if device_summary and (return_episodes or self.failure_logger is not None):
+            raise ValueError("device_summary=True returns no episodes: pass return_episodes=False and use no "
+                             "failure_logger")
+        prog = compiled_program(self.policy)
+        if device_summary and prog is None:
+            raise ValueError("device_summary=True needs a policy the episode kernel compiles")
         if not self._policy_frozen:
             self.freeze_policy()
-        prog = compiled_program(self.policy)
         # a program without draws has no serial stream to honour: exact order as one lane per episode
         no_draws = prog is not None and prog.draws == 0
         p = self.heldout_program(num_episodes_per_object, seed, (parallel or no_draws) and prog is not None)
         traj = self.failure_logger is not None
+        K, n_obj = int(num_episodes_per_object), len(self.heldout_set.heldout_objects)
+        kw: Dict[str, Any] = dict(trajectories=traj, timing=timing)
+        if device_summary:
+            kw["groups"] = [np.arange(o * K, (o + 1) * K) for o in range(n_obj)] + [np.arange(n_obj * K)]
         if prog is None:  # host policy: the reference's sequential loop on the facade
             rec = p.run_facade(self.policy, trajectories=traj)
         elif not parallel:
-            rec = p.run(prog, policy_tapes=_exact_tape(prog, p), trajectories=traj)
+            rec = p.run(prog, policy_tapes=_exact_tape(prog, p), **kw)
             prog.stream.commit(int(rec.policy_used[0]))
         elif policy_seeds is not None:
-            rec = p.run(prog, policy_tapes=_seeded_tapes(prog, p, policy_seeds), trajectories=traj)
+            rec = p.run(prog, policy_tapes=_seeded_tapes(prog, p, policy_seeds), **kw)
         else:
-            rec = p.run(prog, host_resets=False, host_noise=False, device_seed=device_seed, trajectories=traj)
-        res = self.results(rec, int(num_episodes_per_object), return_episodes or traj)
+            rec = p.run(prog, host_resets=False, host_noise=False, device_seed=device_seed, **kw)
+        if device_summary:
+            return self.summary_results(rec, K)
+        res = self.results(rec, K, return_episodes or traj)
         if traj:
             segs = [lane_seg for lane in p.lanes for lane_seg in lane]
             self._log_failures(rec, res["all_episodes"], [p.configs[s.row] for s in segs],
@@ -643,6 +817,34 @@ class Evaluator:
         if not return_episodes:
             out["records"] = rec
         return out
+
+    def summary_results(self, summ: EvalSummary, K: int, object_groups: Optional[Sequence[int]] = None,
+                        overall_group: Optional[int] = None) -> Dict:
+        """The result dict of ``results`` from the group tables of a device summary:
+        ``object_groups[o]`` is object o's group, ``overall_group`` the one over all episodes
+        (default: the layout evaluate_heldout_set builds, objects first, then overall)."""
+        objs = self.heldout_set.heldout_objects
+        n_obj = len(objs)
+        og = list(range(n_obj)) if object_groups is None else list(object_groups)
+        ag = n_obj if overall_group is None else int(overall_group)
+        per_object, per_object_metrics = {}, {}
+        for o in range(n_obj):
+            m = summ.metrics(og[o])
+            entry = {"object_properties": {"size": objs[o].size, "mass": objs[o].mass, "friction": objs[o].friction}}
+            # np.mean of an empty slice is nan in `results`
+            entry["mean_reward"] = summ.mean_reward(og[o]) if m else float("nan")
+            entry["mean_steps"] = m.get("mean_episode_length", float("nan"))
+            entry["success_rate"] = m.get("grasp_success_rate", float("nan"))
+            per_object[o] = entry
+            if K:
+                per_object_metrics[o] = m
+        agg = summ.metrics(ag)
+        overall = {"num_objects": n_obj, "total_episodes": n_obj * K,
+                   "overall_success_rate": agg.get("grasp_success_rate"),
+                   "mean_reward": summ.mean_reward(ag) if agg else float("nan"),
+                   "std_reward": summ.std_reward(ag), "mean_steps": agg.get("mean_episode_length")}
+        return {"overall_stats": overall, "per_object_results": per_object, "all_episodes": None,
+                "metrics": agg, "per_object_metrics": per_object_metrics, "summary": summ}
 
 
 # ------------------------------------------------------------------ RobustnessTester
@@ -701,19 +903,28 @@ class RobustnessTester:
                                         noise_seed=None if s.noise_seed is None else (s.noise_seed, k))])
         return p
 
-    def _run_levels(self, levels, num_episodes, seed, parallel, policy_seeds, device_seed):
+    def _run_levels(self, levels, num_episodes, seed, parallel, policy_seeds, device_seed, device_summary=False):
         prog = compiled_program(self.policy)
+        if device_summary and prog is None:
+            raise ValueError("device_summary=True needs a policy the episode kernel compiles")
         p = self.levels_program(levels, num_episodes, seed, parallel and prog is not None,
                                 lane_per_level=prog is not None and prog.draws == 0)
+        kw: Dict[str, Any] = {}
+        if device_summary:  # one group per noise level
+            kw["groups"] = [np.arange(li * num_episodes, (li + 1) * num_episodes) for li in range(len(levels))]
         if prog is None:  # host policy: the reference's sequential loop on the facade
             rec = p.run_facade(self.policy)
         elif not parallel:
-            rec = p.run(prog, policy_tapes=_exact_tape(prog, p))
+            rec = p.run(prog, policy_tapes=_exact_tape(prog, p), **kw)
             prog.stream.commit(int(rec.policy_used[0]))
         elif policy_seeds is not None:
-            rec = p.run(prog, policy_tapes=_seeded_tapes(prog, p, policy_seeds))
+            rec = p.run(prog, policy_tapes=_seeded_tapes(prog, p, policy_seeds), **kw)
         else:
-            rec = p.run(prog, host_resets=False, host_noise=False, device_seed=device_seed)
+            rec = p.run(prog, host_resets=False, host_noise=False, device_seed=device_seed, **kw)
+        if device_summary:
+            return [{"episodes": [], "metrics": rec.metrics(li),
+                     "noise_levels": {"observation_noise_std": o, "dynamics_noise_std": d}}
+                    for li, (o, d) in enumerate(levels)]
         return self.level_results(rec, levels, num_episodes)
 
     def level_results(self, rec: EvalRecords, levels, num_episodes: int) -> List[Dict]:
@@ -731,17 +942,21 @@ class RobustnessTester:
 
     def evaluate_with_noise(self, observation_noise_std: float = 0.0, dynamics_noise_std: float = 0.0,
                             num_episodes: int = 20, seed: Optional[int] = None, parallel: bool = False,
-                            policy_seeds: Optional[Sequence[int]] = None, device_seed: int = 0) -> Dict:
-        """robustness_tests.py:240-310."""
+                            policy_seeds: Optional[Sequence[int]] = None, device_seed: int = 0,
+                            device_summary: bool = False) -> Dict:
+        """robustness_tests.py:240-310.  ``device_summary=True``: the level's metrics come from
+        ``dxrl_eval_summarize`` and its ``episodes`` list is empty."""
         return self._run_levels([(observation_noise_std, dynamics_noise_std)], num_episodes, seed, parallel,
-                                policy_seeds, device_seed)[0]
+                                policy_seeds, device_seed, device_summary)[0]
 
     def run_robustness_sweep(self, observation_noise_levels: List[float], dynamics_noise_levels: List[float],
                              num_episodes: int = 20, seed: Optional[int] = None, parallel: bool = False,
-                             policy_seeds: Optional[Sequence[int]] = None, device_seed: int = 0) -> Dict:
-        """robustness_tests.py:312-407: every level of the sweep as a segment of one launch."""
+                             policy_seeds: Optional[Sequence[int]] = None, device_seed: int = 0,
+                             device_summary: bool = False) -> Dict:
+        """robustness_tests.py:312-407: every level of the sweep as a segment of one launch
+        (``device_summary=True``: one summary group per level, empty ``episodes`` lists)."""
         levels, keys = self.sweep_levels(observation_noise_levels, dynamics_noise_levels)
-        res = self._run_levels(levels, num_episodes, seed, parallel, policy_seeds, device_seed)
+        res = self._run_levels(levels, num_episodes, seed, parallel, policy_seeds, device_seed, device_summary)
         out: Dict[str, Any] = {"baseline": None, "observation_noise": {}, "dynamics_noise": {}, "combined_noise": {}}
         for (grp, k), r in zip(keys, res):
             if grp == "baseline":
@@ -751,5 +966,6 @@ class RobustnessTester:
         return out
 
 
-__all__ = ["Evaluator", "RobustnessTester", "EpisodeProgram", "Segment", "EvalRecords", "EvaluationMetrics",
+__all__ = ["Evaluator", "RobustnessTester", "EpisodeProgram", "Segment", "EvalRecords", "EvalSummary",
+           "EvaluationMetrics",
            "policy_program", "failure_names"]

@@ -138,6 +138,44 @@ def aggregate_columns(success, steps, num_contacts, codes) -> Dict:
     }
 
 
+FAILURE_CODES = {t.value: k for k, t in enumerate(_TYPES)}
+
+
+def aggregate_sums(stats, ret=None) -> Dict:
+    """The aggregate_columns dict from one ``group_stats`` row of ``dxrl_eval_summarize``
+    (include/dxrl.h: episodes, successes, sum steps, sum steps^2, sum contacts, sum steps / sum
+    contacts over successes, episodes per failure code) and, when given, its ``group_return`` row
+    (count, mean, M2), which adds ``mean_reward`` / ``std_reward``.  Means are ``float(S) / n`` of
+    the integer sums -- what np.mean gives on the int64 columns -- and the std is
+    sqrt(n S2 - S1^2) / n with the radicand exact in integers."""
+    s = [int(x) for x in stats]
+    total, ok = s[0], s[1]
+    if total == 0:
+        return {}
+    bad = total - ok
+    ratio = lambda a, n: float(a) / n if n else None  # noqa: E731
+    out = {
+        "grasp_success_rate": float(ok) / total,
+        "mean_episode_length": float(s[2]) / total,
+        "std_episode_length": float(np.sqrt(float(total * s[3] - s[2] * s[2]))) / total,
+        "failure_type_frequency": {t.value: {"count": s[7 + k], "frequency": float(s[7 + k] / total)}
+                                   for k, t in enumerate(_TYPES)},
+        "total_episodes": total,
+        "successful_episodes": ok,
+        "failed_episodes": bad,
+        "mean_contacts": float(s[4]) / total,
+        "mean_success_length": ratio(s[5], ok),
+        "mean_success_contacts": ratio(s[6], ok),
+        "mean_failure_length": ratio(s[2] - s[5], bad),
+        "mean_failure_contacts": ratio(s[4] - s[6], bad),
+    }
+    if ret is not None:
+        n, mean, m2 = (float(x) for x in ret)
+        out["mean_reward"] = mean
+        out["std_reward"] = float(np.sqrt(m2 / n)) if n else None
+    return out
+
+
 def _history_counts(h) -> List[int]:
     """contact_history rows are 5-element 0/1 lists (evaluator.py:148-149); the
     rule counts entries > 0.5 (metrics.py:73)."""

@@ -707,6 +707,73 @@ typedef struct dxrl_eval_mlp {
 } dxrl_eval_mlp;
 int dxrl_evaluate_mlp(dxrl_env* env, const dxrl_eval_args* args, const dxrl_eval_mlp* mlp, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Episode summaries on the device: evaluation/metrics.py:39-103,128-206
+ * (EvaluationMetrics.classify_failure in rule order and the sums behind
+ * compute_aggregate_metrics), over the record buffers dxrl_evaluate /
+ * dxrl_evaluate_mlp wrote on the same stream.  Two launches, stream-ordered
+ * behind the episode kernel, no host synchronisation: a per-episode pass (all
+ * the contact_hist traffic; failure code and history moments of every episode)
+ * and a per-group pass over a CSR group table.  An episode may belong to several
+ * groups or to none ("per object", "per seed" and "overall" are three sets of
+ * groups of one table).
+ *
+ * ep_code: -1 = success, else the index into the FailureType enumeration in its
+ * declaration order (0 slippage, 1 unstable_contacts, 2 misaligned_grasp,
+ * 3 timeout, 4 object_dropped, 5 insufficient_contacts); rules in the order
+ * TIMEOUT, OBJECT_DROPPED, UNSTABLE_CONTACTS (n > 5), SLIPPAGE (n > 10),
+ * MISALIGNED_GRASP, INSUFFICIENT_CONTACTS.  np.var(counts) > 2.0 is decided
+ * exactly in integers, n S2 - S1^2 > 2 n^2; the slippage rule is the f64
+ * expression (L / 5.0) - (F / 5.0) < -1.0.
+ * TIE ROWS: an episode still open at the variance rule with n > 5 and
+ * n S2 - S1^2 == 2 n^2.  np.var's own rounding decides those, so the kernel
+ * classifies them as not unstable, lists them in tie_list (ascending) and
+ * counts them in slot 13 of every group that holds them; the caller settles them
+ * with np.var on those rows' histories and moves one failure-code count per
+ * holding group where np.var says unstable.
+ *
+ * group_stats i64 [G][16]: 0 episodes, 1 successes, 2 sum steps, 3 sum steps^2,
+ * 4 sum contacts, 5 sum steps over successes, 6 sum contacts over successes,
+ * 7..12 episodes per failure code 0..5, 13 tie rows, 14-15 zero.
+ * group_return f64 [G][3]: count, mean, M2 (sum of squared deviations) of
+ * ep_return, accumulated about the group's first member's return and merged
+ * with Chan et al.'s update in a fixed order: bit-identical from run to run (no
+ * floating-point atomics), and no cancellation for returns of the form
+ * big + small.
+ * status i32 [1] (zeroed on the stream by the call): bit 0 = a group offset or a
+ * member episode index was out of range (that group / member is skipped, nothing
+ * is written out of bounds); bit 1 = more tie rows than tie_cap (tie_count still
+ * holds the true count).
+ * ------------------------------------------------------------------------ */
+#define DXRL_SUMMARY_MAX_STEPS 4096 /* larger max_steps -> DXRL_E_INVALID */
+typedef struct dxrl_eval_summary_args {
+    int32_t total_episodes;          /* E                                                    */
+    int32_t max_steps;               /* contact_hist row pitch and the TIMEOUT bound         */
+    int32_t success_threshold;       /* MISALIGNED_GRASP: 0 < num_contacts < threshold       */
+    int32_t num_groups;              /* G                                                    */
+    int32_t num_members;             /* entries of group_episodes (bounds check)             */
+    int32_t tie_cap;                 /* entries of tie_list                                  */
+    /* device inputs: the episode kernel's records */
+    const int32_t* ep_length;        /* i32 [E]                                              */
+    const uint8_t* ep_success;       /* u8  [E]                                              */
+    const uint8_t* ep_contacts;      /* u8  [E] num_contacts == final_contacts               */
+    const double*  ep_return;        /* f64 [E]                                              */
+    const uint8_t* contact_hist;     /* u8  [E][max_steps]; rows need not be 4-byte aligned  */
+    const int32_t* group_offsets;    /* i32 [G + 1] CSR offsets into group_episodes          */
+    const int32_t* group_episodes;   /* i32 [num_members] episode indices                    */
+    /* device outputs */
+    uint8_t* ep_work;                /* u8  [E] scratch between the two launches (required)  */
+    int8_t*  ep_code;                /* i8  [E]    (nullable)                                */
+    int32_t* ep_moments;             /* i32 [E][4] S1, S2, first-five sum, last-five sum (nullable) */
+    int64_t* group_stats;            /* i64 [G][16]                                          */
+    double*  group_return;           /* f64 [G][3]                                           */
+    int32_t* tie_count;              /* i32 [1]                                              */
+    int32_t* tie_list;               /* i32 [tie_cap]                                        */
+    int32_t* status;                 /* i32 [1]                                              */
+} dxrl_eval_summary_args;
+
+int dxrl_eval_summarize(int32_t device, const dxrl_eval_summary_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
