@@ -117,32 +117,39 @@ def _gae_segmented(rew, done, V, n, T, gamma, lam):
 
 
 def loss_and_grads(params, obs_rm, act, logp_old, rew, done, n, T, cfg, bf16=True, norm_stats=None, total=None,
-                   world=1, scales=None):
+                   world=1, scales=None, rows=None):
     """Manual forward/backward of the PPO objective as the HIP pipeline computes it.
+    rows = (start, count): one minibatch pass as PGTrainer runs it -- V, GAE and the advantage
+    moments over the whole tape, the gradient, the loss and info["terms"] over the samples
+    start .. start + count - 1 alone, scaled by 1 / count (info["V"/"adv"/"ret"] stay whole).
     Sharded use (as PGTrainer with world > 1): norm_stats(adv) -> (mean, std) computed
     across ranks, total = global sample count, world = number of ranks; or
     scales = (per-sample loss scale, per-rank entropy coefficient) as
     distributed.loss_scales returns them (what the trainer hands the kernels).
     Returns (grads [NPARAMS], info dict)."""
     M = n * T
-    total = M if total is None else total
+    start, count = (0, M) if rows is None else rows
+    sl = slice(start, start + count)
+    total = count if total is None else total
     inv_total, ent = (1.0 / total, cfg["ent_coef"] / world) if scales is None else scales
     Wd = unpack(params)
     dt = params.dtype
     X = obs_rm.to(dt)
     H1c, H2c, vhead = mlp_forward(X, Wd, "c", bf16)
-    V = vhead[:, 0]
-    adv, ret = gae(rew.to(dt), done, V, n, T, cfg["gamma"], cfg["lam"])
+    V_all = vhead[:, 0]
+    adv_all, ret_all = gae(rew.to(dt), done, V_all, n, T, cfg["gamma"], cfg["lam"])
     if norm_stats is None:
-        mean, std = adv.double().mean(), adv.double().std()
+        mean, std = adv_all.double().mean(), adv_all.double().std()
     else:
-        mean, std = norm_stats(adv)
-    A = ((adv.double() - mean) / (std + 1e-8)).to(dt)
-    Xa = X[:M]
+        mean, std = norm_stats(adv_all)
+    A = ((adv_all.double() - mean) / (std + 1e-8)).to(dt)[sl]
+    V, ret = V_all[sl], ret_all[sl]
+    Xa = X[sl]
     H1a, H2a, muh = mlp_forward(Xa, Wd, "a", bf16)
     mu = muh[:, :ACT]
     ls = Wd["logstd"]
-    a = act[:, :ACT]
+    a = act[sl, :ACT]
+    logp_old = logp_old[sl]
     iv = torch.exp(-2.0 * ls)
     z = (a - mu) * torch.exp(-ls)
     lp = (-0.5 * z * z - ls - 0.5 * LOG2PI).sum(1)
@@ -153,11 +160,11 @@ def loss_and_grads(params, obs_rm, act, logp_old, rew, done, n, T, cfg, bf16=Tru
     d = a - mu
     dmu = gsel[:, None] * d * iv
     dls = (gsel[:, None] * (d * d * iv - 1.0)).sum(0) - ent
-    dv = 2.0 * cfg["vf_coef"] * (V[:M] - ret) * inv_total
+    dv = 2.0 * cfg["vf_coef"] * (V - ret) * inv_total
     grads = torch.zeros(NPARAMS, dtype=dt, device=params.device)
     G = unpack(grads)
     G["logstd"].copy_(dls)
-    for net, dY, H1, H2 in (("a", dmu, H1a, H2a), ("c", dv[:, None], H1c[:M], H2c[:M])):
+    for net, dY, H1, H2 in (("a", dmu, H1a, H2a), ("c", dv[:, None], H1c[sl], H2c[sl])):
         k = dY.shape[1]
         dYr = _r(dY, bf16)
         W2_, W3_ = _r(Wd[f"W2{net}"], bf16), _r(Wd[f"W3{net}"], bf16)
@@ -168,29 +175,36 @@ def loss_and_grads(params, obs_rm, act, logp_old, rew, done, n, T, cfg, bf16=Tru
         G[f"W2{net}"][:, H] = dH2.sum(0)
         dH1 = _r((dH2 @ W2_[:, :H]) * (1 - H1 * H1), bf16)
         G[f"W1{net}"][:, :] = dH1.T @ Xa
-    loss = (-torch.minimum(s1, s2)).mean() + cfg["vf_coef"] * ((V[:M] - ret) ** 2).mean() - cfg["ent_coef"] * (
+    # per-sample loss terms (what the kernels sum into policy_loss, value_mse, clip_frac, approx_kl)
+    terms = {"policy": -torch.minimum(s1, s2), "value": (V - ret) ** 2,
+             "clip": (ratio - 1).abs() > cfg["clip_eps"], "kl": logp_old - lp}
+    loss = terms["policy"].mean() + cfg["vf_coef"] * terms["value"].mean() - cfg["ent_coef"] * (
         ls.sum() + 0.5 * ACT * (1 + LOG2PI))
-    return grads, {"V": V, "adv": adv, "ret": ret, "mu": muh, "mean": mean, "std": std, "loss": loss,
-                   "ratio": ratio}
+    return grads, {"V": V_all, "adv": adv_all, "ret": ret_all, "mu": muh, "mean": mean, "std": std, "loss": loss,
+                   "ratio": ratio, "lp": lp, "logp_old": logp_old, "A": A, "terms": terms}
 
 
-def autograd_loss(params, obs_rm, act, logp_old, rew, done, n, T, cfg):
-    """The same objective through torch autograd (fp64 OK); adv/ret/normalisation are constants."""
+def autograd_loss(params, obs_rm, act, logp_old, rew, done, n, T, cfg, rows=None):
+    """The same objective through torch autograd (fp64 OK); adv/ret/normalisation are constants.
+    rows = (start, count): the mean loss over that slice of samples (moments over the whole tape)."""
     M = n * T
+    start, count = (0, M) if rows is None else rows
+    sl = slice(start, start + count)
     params = params.detach().clone().requires_grad_(True)
     Wd = unpack(params)
     X = obs_rm.to(params.dtype)
     with torch.no_grad():
         _, _, vh = mlp_forward(X, {k: v.detach() for k, v in Wd.items()}, "c", False)
         adv, ret = gae(rew.to(params.dtype), done, vh[:, 0], n, T, cfg["gamma"], cfg["lam"])
-        A = (adv - adv.mean()) / (adv.std() + 1e-8)
-    _, _, vh = mlp_forward(X, Wd, "c", False)
-    V = vh[:M, 0]
-    _, _, muh = mlp_forward(X[:M], Wd, "a", False)
+        A = ((adv - adv.mean()) / (adv.std() + 1e-8))[sl]
+        ret = ret[sl]
+    _, _, vh = mlp_forward(X[sl], Wd, "c", False)
+    V = vh[:, 0]
+    _, _, muh = mlp_forward(X[sl], Wd, "a", False)
     mu, ls = muh[:, :ACT], Wd["logstd"]
-    a = act[:, :ACT].to(params.dtype)
+    a = act[sl, :ACT].to(params.dtype)
     lp = (-0.5 * ((a - mu) * torch.exp(-ls)) ** 2 - ls - 0.5 * LOG2PI).sum(1)
-    ratio = torch.exp(lp - logp_old.to(params.dtype))
+    ratio = torch.exp(lp - logp_old[sl].to(params.dtype))
     s1 = ratio * A
     s2 = torch.clamp(ratio, 1 - cfg["clip_eps"], 1 + cfg["clip_eps"]) * A
     loss = (-torch.minimum(s1, s2)).mean() + cfg["vf_coef"] * ((V - ret) ** 2).mean() - cfg["ent_coef"] * (
@@ -199,22 +213,125 @@ def autograd_loss(params, obs_rm, act, logp_old, rew, done, n, T, cfg):
     return params.grad.detach()
 
 
+BIAS_BLOCKS = {f"b{k}{net}": (f"W{k}{net}", OBS_IN if k == 1 else H) for k in (1, 2, 3) for net in "ac"}
+GRAD_BLOCKS = ("W1a", "W2a", "W3a", "W1c", "W2c", "W3c")
+ALL_BLOCKS = GRAD_BLOCKS + tuple(BIAS_BLOCKS) + ("logstd",)
+
+
+def pin_block(grads, name):
+    """A named piece of a [NPARAMS] vector: a weight block (its bias column included), a bias column
+    on its own (b1a .. b3c: column 45 of W1, column 256 of W2 / W3) or logstd."""
+    Wd = unpack(grads)
+    if name in BIAS_BLOCKS:
+        blk, col = BIAS_BLOCKS[name]
+        return Wd[blk][:, col]
+    return Wd[name]
+
+
 def fp64_pin(got_grads, got_V, got_adv, params, obs_rm, act, logp_old, rew, done, n, T, cfg, g_bf16, info_bf16,
-             factor=1.5, blocks=("W1a", "W2a", "W3a", "W1c", "W2c", "W3c")):
+             factor=1.5, blocks=GRAD_BLOCKS, rows=None, logp=None, truth=None, factors=None, extra=None):
     """Pin the HIP learner to fp64 truth, not just to the bf16 restatement:
     the same objective on the same tapes in float64 with no bf16 rounding anywhere is the truth;
     for every gradient block and for V / adv the HIP result's distance to it must be at most
     `factor` x the bf16-emulating torch reference's distance (both carry the same bf16 storage
     points, so a kernel regression that adds error shows as a ratio above 1).  Returns the
-    ratios {name: |hip - truth| / |bf16 ref - truth|}."""
-    g64, info64 = loss_and_grads(params.double(), obs_rm, act, logp_old, rew, done, n, T, cfg, bf16=False)
-    got_b, ref_b, tru_b = unpack(got_grads), unpack(g_bf16), unpack(g64)
-    ratios = {}
-    pairs = [(b, got_b[b].double(), ref_b[b].double(), tru_b[b]) for b in blocks]
+    ratios {name: |hip - truth| / |bf16 ref - truth|}.
+    blocks may also name the bias columns on their own (b1a, b2a, b3a, b1c, b2c, b3c: one column of
+    257 barely moves its block's norm) and logstd; rows = (start, count) is the minibatch slice of
+    loss_and_grads; logp = (got, ref, truth) pins log pi the same way, extra = {name: (got, ref,
+    truth)} any further quantity (the GEMM chain's mu); truth = (grads, info) of the fp64 run when
+    the caller already has it; factors = {name: factor} overrides `factor` for the
+    named quantities (each with its cause written down where it is raised).  Every ratio is
+    computed before the first assertion, so a failure reports all of them."""
+    if truth is None:
+        truth = loss_and_grads(params.double(), obs_rm, act, logp_old, rew, done, n, T, cfg, bf16=False, rows=rows)
+    g64, info64 = truth
+    ratios, bad = {}, []
+    pairs = [(b, pin_block(got_grads, b).double(), pin_block(g_bf16, b).double(), pin_block(g64, b)) for b in blocks]
     pairs += [("V", got_V.double(), info_bf16["V"].double(), info64["V"]),
               ("adv", got_adv.double(), info_bf16["adv"].double(), info64["adv"])]
+    if logp is not None:
+        pairs.append(("logp",) + tuple(t.double() for t in logp))
+    pairs += [(k,) + tuple(t.double() for t in v) for k, v in (extra or {}).items()]
     for name, got, ref, tru in pairs:
         e_hip, e_ref = (got - tru).norm().item(), (ref - tru).norm().item()
         ratios[name] = e_hip / max(e_ref, 1e-300)
-        assert e_hip <= factor * e_ref, (name, e_hip, e_ref)
+        if not e_hip <= (factors or {}).get(name, factor) * e_ref:
+            bad.append((name, e_hip, e_ref))
+    assert not bad, (bad, ratios)
     return ratios
+
+
+def trained_like_params(seed):
+    """A [NPARAMS] f32 master away from the initial state, where much of the learner's arithmetic
+    is degenerate (every bias exactly 0, actor head gain 0.01 so mu ~ 0, one log_std for all 15
+    actions): both networks built as PGTrainer._init_params builds them (orthogonal, gain sqrt 2
+    on the hidden layers, 1.0 on the value head) but actor head gain 0.5 (log pi of the bf16
+    restatement then sits within ~0.02 of fp64; gain 2.0 gives up to 0.13, too close to the clip
+    margins of offpolicy_logp), the W1 bias column and b2 ~ U(-0.1, 0.1), b3 ~ U(-0.3, 0.3) on the
+    live head rows, log_std = linspace(-1.0, -0.2, 15)."""
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    params = torch.zeros(NPARAMS, dtype=torch.float32)
+    Wd = unpack(params)
+    for net, head_rows, head_gain in (("a", ACT, 0.5), ("c", 1, 1.0)):
+        for name, r, c, gain in ((f"W1{net}", H, OBS_IN, math.sqrt(2)), (f"W2{net}", H, H, math.sqrt(2)),
+                                 (f"W3{net}", head_rows, H, head_gain)):
+            w = torch.empty(r, c)
+            torch.nn.init.orthogonal_(w, gain=gain, generator=g)
+            Wd[name][:r, :c] = w
+        u = lambda k, a: (2 * torch.rand(k, generator=g) - 1) * a  # noqa: E731
+        Wd[f"W1{net}"][:, OBS_IN] = u(H, 0.1)
+        Wd[f"W2{net}"][:, H] = u(H, 0.1)
+        Wd[f"W3{net}"][:head_rows, H] = u(head_rows, 0.3)
+    Wd["logstd"][:] = torch.linspace(-1.0, -0.2, ACT)
+    return params
+
+
+def clip_bounds(clip_eps):
+    """The clip range's boundaries in log-ratio space: (hi, lo) = (log(1 + eps), -log(1 - eps)),
+    the ratio being clipped above hi and below -lo."""
+    return math.log1p(clip_eps), -math.log1p(-clip_eps)
+
+
+def offpolicy_logp(logp, clip_eps, seed, band=0.08, reach=0.7, positive=0.65):
+    """Old log-probabilities that put the ratio exp(lp - logp_old) on both sides of both clip
+    boundaries with a dead band around each: logp + pert, half of the samples with
+    |pert| ~ U(0, hi - band) (inside the clip range), the other half with
+    |pert| ~ U(lo + band, lo + reach) (outside it; lo > hi, so either sign clears its boundary by
+    `band`), signs + for 65 % and - for 35 %, so that approx_kl = mean(pert) is clearly nonzero.
+    reach and the sign split are sized by the GPU tests' own input condition |approx_kl| >= 10 x its
+    tolerance (2 x the mean |log pi| gap between the bf16 restatement and fp64, 0.0050 on the
+    rollout's tapes under trained_like_params): mean(pert) = (2 positive - 1) x mean |pert|, which
+    the dead band's width does not move.  reach 0.4 with 60 / 40 gave approx_kl 0.037 (eps 0.1) to
+    0.053 (eps 0.2) on those tapes against the 0.050 needed; 0.7 with 65 / 35 gives about 0.075 and
+    0.10, while the rarest sign x side combination keeps 0.5 x 0.35 x P(sign A) > 5 % of the samples
+    for P(sign A) down to 0.3."""
+    hi, lo = clip_bounds(clip_eps)
+    assert hi > band and reach > band
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    M = logp.numel()
+    u = torch.rand(M, generator=g, dtype=torch.float64)
+    outside = torch.rand(M, generator=g) < 0.5
+    sign = torch.where(torch.rand(M, generator=g) < positive, 1.0, -1.0).double()
+    mag = torch.where(outside, lo + band + u * (reach - band), u * (hi - band))
+    pert = (sign * mag).to(logp.dtype).to(logp.device)
+    return logp + pert.view_as(logp)
+
+
+def ratio_margin(info, clip_eps):
+    """Smallest distance, in log space, of any sample's ratio (info of loss_and_grads) to either clip
+    boundary: above it a computation whose log pi differs from the reference's by less still puts
+    every sample on the same side."""
+    hi, lo = clip_bounds(clip_eps)
+    lr = (info["lp"] - info["logp_old"]).double()
+    return torch.minimum((lr - hi).abs(), (lr + lo).abs()).min().item()
+
+
+def clip_quadrants(info, clip_eps):
+    """Fractions of the samples in the four combinations of advantage sign and clipped side:
+    {(A > 0, above), (A > 0, below), (A < 0, above), (A < 0, below)}."""
+    A, r = info["A"], info["ratio"]
+    above, below = r > 1 + clip_eps, r < 1 - clip_eps
+    f = lambda m: m.double().mean().item()  # noqa: E731
+    return {"A+above": f((A > 0) & above), "A+below": f((A > 0) & below),
+            "A-above": f((A < 0) & above), "A-below": f((A < 0) & below)}
