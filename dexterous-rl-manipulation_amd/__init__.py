@@ -7,7 +7,10 @@ Drop-in surfaces (same names as the reference modules):
   evaluation.{HeldOutObjectSet,CombinedNoiseWrapper,Evaluator,RobustnessTester,EvaluationMetrics,...},
   ablation.{train_with_config,run_component_ablation,...},
   curriculum_ablation.{train_with_curriculum,train_without_curriculum,compute_convergence_metrics,run_ablation_study},
-  seed_variance.{SeedVarianceAnalyzer,analyze_seed_variance,plot_seed_variance,print_variance_report,run_seed_variance}
+  seed_variance.{SeedVarianceAnalyzer,analyze_seed_variance,plot_seed_variance,print_variance_report,run_seed_variance},
+  failure_analysis.{print_failure_taxonomy,print_failure_statistics,analyze_failure_modes},
+  failure_statistics.{load_failure_logs,compute_failure_distribution,compute_correlations,generate_failure_report,
+                      plot_failure_distribution,plot_failure_correlations,run_failure_study}
 Batched device API: envs.VecEnv, policies.VecSimpleLearner, training.SimpleLearnerRollout.
 The compute runs in libdxrl.so (HIP, gfx950; C ABI in include/dxrl.h).  No CPU fallback.
 """
@@ -20,6 +23,6 @@ __version__ = "0.1.0"
 def __getattr__(name):
     import importlib
     if name in ("envs", "policies", "training", "evaluation", "build", "_native", "trainer",
-                "evaluator", "metrics", "curriculum_ablation", "seed_variance"):
+                "evaluator", "metrics", "curriculum_ablation", "seed_variance", "failure_analysis", "failure_statistics"):
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

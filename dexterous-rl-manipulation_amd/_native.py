@@ -156,7 +156,8 @@ class EvalArgs(C.Structure):
                 ("policy_stride", C.c_int64), ("noise_tape", C.c_void_p), ("reset_tape", C.c_void_p),
                 ("policy_seed", C.c_uint64), ("noise_seed", C.c_uint64), ("reset_seed", C.c_uint64)] + \
                [(k, C.c_void_p) for k in ("ep_return", "ep_length", "ep_success", "ep_contacts", "contact_hist",
-                                          "policy_used", "status", "obs_traj", "act_traj", "work_queue")]
+                                          "policy_used", "status", "obs_traj", "act_traj", "work_queue",
+                                          "hist_moments")]
 
 
 class EvalMlp(C.Structure):
@@ -172,6 +173,18 @@ class EvalSummaryArgs(C.Structure):
                [(k, C.c_void_p) for k in ("ep_length", "ep_success", "ep_contacts", "ep_return", "contact_hist",
                                           "group_offsets", "group_episodes", "ep_work", "ep_code", "ep_moments",
                                           "group_stats", "group_return", "tie_count", "tie_list", "status")]
+
+
+FAILURE_MODES = 6  # DXRL_FAILURE_MODES
+
+
+class FailureSummaryArgs(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("total_episodes", "max_steps", "timeout_steps", "success_threshold",
+                                         "num_groups", "num_members", "tie_cap", "reserved")] + \
+               [(k, C.c_void_p) for k in ("ep_length", "ep_success", "ep_contacts", "ep_props", "contact_hist",
+                                          "hist_moments", "group_offsets", "group_episodes", "ep_work", "ep_mode",
+                                          "ep_confidence", "mode_stats", "group_totals", "mode_props", "tie_count",
+                                          "tie_list", "status")]
 
 
 _P = C.c_void_p
@@ -224,6 +237,7 @@ _SIGS = {
     "dxrl_evaluate": (C.c_int, [_P, C.POINTER(EvalArgs), _P]),
     "dxrl_evaluate_mlp": (C.c_int, [_P, C.POINTER(EvalArgs), C.POINTER(EvalMlp), _P]),
     "dxrl_eval_summarize": (C.c_int, [_I32, C.POINTER(EvalSummaryArgs), _P]),
+    "dxrl_failure_summarize": (C.c_int, [_I32, C.POINTER(FailureSummaryArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

@@ -193,6 +193,7 @@ __global__ __launch_bounds__(64) void k_eval(const dxrl_curriculum* __restrict__
             uint32_t nc = 0;
             int steps = 0;
             uint8_t* hist = a.contact_hist ? a.contact_hist + rec * a.max_steps : nullptr;
+            HistAcc hm{0u, 0u};
             for (int step = 0; step < a.max_steps; ++step) {
                 float nz[kD], act[kD];
                 if (!policy_terms<kTape>(a.policy, a.exploration_noise, ps, nz)) {
@@ -221,6 +222,7 @@ __global__ __launch_bounds__(64) void k_eval(const dxrl_curriculum* __restrict__
                 steps = step + 1;
                 nc = (uint32_t)__popc(e.flags & 0x1Fu);
                 if (hist) hist[step] = (uint8_t)nc;
+                hist_acc_step(hm, nc, step);
                 if (otraj) write_obs(e, otraj + (int64_t)(step + 1) * kObs);
                 if (te || tr) break;
             }
@@ -229,6 +231,7 @@ __global__ __launch_bounds__(64) void k_eval(const dxrl_curriculum* __restrict__
             a.ep_length[rec] = steps;
             a.ep_success[rec] = (uint8_t)te;  // success = terminated (EV:157, RT:303)
             if (a.ep_contacts) a.ep_contacts[rec] = (uint8_t)nc;
+            if (a.hist_moments) hist_acc_store(hm, a.hist_moments + 5 * rec);
         }
         if (!ns.ok) ok = false;
     }
@@ -281,6 +284,7 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_ls(const dxrl_curriculum*
     int64_t rec = 0;
     float *otraj = nullptr, *atraj = nullptr;
     uint8_t* hist = nullptr;
+    HistAcc hm{0u, 0u};
     double ret = 0.0;
     bool te = false;
     uint32_t nc = 0;
@@ -411,6 +415,7 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_ls(const dxrl_curriculum*
         steps = 0;
         step = 0;
         hist = a.contact_hist ? a.contact_hist + rec * a.max_steps : nullptr;
+        hm = HistAcc{0u, 0u};
         phase = kStep;
     };
     const auto end_episode = [&]() {
@@ -419,6 +424,7 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_ls(const dxrl_curriculum*
             a.ep_length[rec] = steps;
             a.ep_success[rec] = (uint8_t)te;  // success = terminated (EV:157, RT:303)
             if (a.ep_contacts) a.ep_contacts[rec] = (uint8_t)nc;
+            if (a.hist_moments) hist_acc_store(hm, a.hist_moments + 5 * rec);
         }
         ++ep;
         next_episode();
@@ -567,6 +573,7 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_ls(const dxrl_curriculum*
         steps = step + 1;
         nc = (uint32_t)__popc(c);
         if (hist && s == 0) hist[step] = (uint8_t)nc;
+        hist_acc_step(hm, nc, step);
         if (otraj) write_obs_row(otraj + (int64_t)(step + 1) * kObs);
         ++step;
         if (te || tr || step >= a.max_steps) end_episode();
@@ -590,6 +597,8 @@ extern "C" int dxrl_evaluate(dxrl_env* env, const dxrl_eval_args* args, void* st
     DXRL_REQUIRE(a.max_steps > 0 && a.total_episodes >= 0, "max_steps must be > 0, total_episodes >= 0");
     DXRL_REQUIRE(a.lane_segments && a.segments, "null segment table");
     DXRL_REQUIRE(a.ep_return && a.ep_length && a.ep_success, "null episode record buffers");
+    DXRL_REQUIRE(!a.hist_moments || a.max_steps <= kHistMomentsMaxSteps,
+                 "hist_moments packs its sums for max_steps <= %d, got %d", kHistMomentsMaxSteps, a.max_steps);
     const bool tape = a.policy_tape != nullptr;
     DXRL_REQUIRE(!tape || a.policy_stride >= 0, "bad policy tape stride");
     EvalParams p{weights_of(env->cfg),

@@ -125,6 +125,7 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
     int64_t rec = 0;
     float *otraj = nullptr, *atraj = nullptr;
     uint8_t* hist = nullptr;
+    HistAcc hm{0u, 0u};
     double ret = 0.0;
     bool te = false;
     uint32_t nc = 0;
@@ -290,6 +291,7 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
                 otraj = a.obs_traj ? a.obs_traj + rec * (int64_t)(a.max_steps + 1) * kObs : nullptr;
                 atraj = a.act_traj ? a.act_traj + rec * (int64_t)a.max_steps * kD : nullptr;
                 hist = a.contact_hist ? a.contact_hist + rec * a.max_steps : nullptr;
+                hm = HistAcc{0u, 0u};
                 ret = 0.0;
                 te = false;
                 nc = 0;
@@ -366,6 +368,7 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
                     a.ep_length[rec] = steps;
                     a.ep_success[rec] = (uint8_t)te;  // success = terminated (EV:157, RT:303)
                     if (a.ep_contacts) a.ep_contacts[rec] = (uint8_t)nc;
+                    if (a.hist_moments) hist_acc_store(hm, a.hist_moments + 5 * rec);
                 }
                 ++ep;
                 phase = kNeedEp;
@@ -518,6 +521,7 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
         steps = step + 1;
         nc = (uint32_t)__popc(c);
         if (hist && s == 0) hist[step] = (uint8_t)nc;
+        hist_acc_step(hm, nc, step);
         // the observation this step returns (trajectory slot step + 1, the policy's next input) is
         // written by the next part A, then the episode goes on or ends there
         emit_dst = otraj ? otraj + (int64_t)(step + 1) * kObs : nullptr;
@@ -541,6 +545,8 @@ extern "C" int dxrl_evaluate_mlp(dxrl_env* env, const dxrl_eval_args* args, cons
     DXRL_REQUIRE(a.max_steps > 0 && a.total_episodes >= 0, "max_steps must be > 0, total_episodes >= 0");
     DXRL_REQUIRE(a.lane_segments && a.segments, "null segment table");
     DXRL_REQUIRE(a.ep_return && a.ep_length && a.ep_success, "null episode record buffers");
+    DXRL_REQUIRE(!a.hist_moments || a.max_steps <= kHistMomentsMaxSteps,
+                 "hist_moments packs its sums for max_steps <= %d, got %d", kHistMomentsMaxSteps, a.max_steps);
     const bool stochastic = mlp->action_std != nullptr, tape = a.policy_tape != nullptr;
     DXRL_REQUIRE(stochastic || !tape, "a policy tape was given in deterministic mode (action_std == NULL takes no draws)");
     DXRL_REQUIRE(!tape || a.policy_stride >= 0, "bad policy tape stride");

@@ -12,6 +12,7 @@
 //                       that fixed order, so group_return is bit-identical from run to run (no
 //                       floating-point atomics).  One extra
 //                       workgroup compacts the tie rows into tie_list in ascending order.
+#include "dxrl_hist_row.h"
 #include "dxrl_internal.h"
 
 namespace dxrl {
@@ -36,38 +37,8 @@ __global__ __launch_bounds__(kSumThreads) void k_summary_episodes(
     const int len = ep_length[e];
     const int n = len < 0 ? 0 : (len > max_steps ? max_steps : len);  // bytes of the row that are read
     const uint8_t* row = hist + (size_t)e * (size_t)max_steps;
-    const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 3);
-    const int ndw = (mis + n + 3) >> 2;
-    int s1 = 0, s2 = 0, f5 = 0, l5 = 0;
-    for (int j = lane; j < ndw; j += 64) {
-        const int o = 4 * j - mis;  // row offset of this dword's byte 0
-        uint32_t w = 0;
-        if (o >= 0 && o + 4 <= n) {
-            w = *reinterpret_cast<const uint32_t*>(row + o);
-        } else {  // head / tail: only the bytes inside [0, n)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = o + k;
-                if (t >= 0 && t < n) w |= (uint32_t)row[t] << (8 * k);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int t = o + k;
-            const int c = (int)((w >> (8 * k)) & 0xffu);  // 0 outside [0, n)
-            s1 += c;
-            s2 += c * c;
-            if (t < 5) f5 += c;
-            if (t >= n - 5) l5 += c;
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        s1 += __shfl_xor(s1, m, 64);
-        s2 += __shfl_xor(s2, m, 64);
-        f5 += __shfl_xor(f5, m, 64);
-        l5 += __shfl_xor(l5, m, 64);
-    }
+    const HistRow h = hist_row_reduce<false>(row, n, lane);
+    const int s1 = h.s1, s2 = h.s2, f5 = h.f5, l5 = h.l5;
     if (lane != 0) return;
     int code = -1, tie = 0;
     if (!ep_success[e]) {

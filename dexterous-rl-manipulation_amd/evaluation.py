@@ -13,7 +13,9 @@
 * ``Evaluator`` / ``RobustnessTester`` (evaluator.py) and ``EvaluationMetrics`` /
   ``FailureType`` / ``format_metrics_report`` (metrics.py) are re-exported here
   under the reference's module path (evaluation/__init__.py), as are
-  ``SeedVarianceAnalyzer`` / ``analyze_seed_variance`` (seed_variance.py).
+  ``SeedVarianceAnalyzer`` / ``analyze_seed_variance`` (seed_variance.py) and the failure
+  analysis (failure_analysis.py, failure_statistics.py: ``analyze_failure_modes``,
+  ``generate_failure_report``, ..., and the device study ``run_failure_study``).
 """
 from __future__ import annotations
 
@@ -208,7 +210,12 @@ _LAZY = {"Evaluator": "evaluator", "RobustnessTester": "evaluator", "EvaluationM
          "FailureModeDefinition": "failures", "FAILURE_MODE_DEFINITIONS": "failures", "FailureClassifier": "failures",
          "FailureLogger": "failures", "EpisodeRecorder": "failures", "SeedVarianceAnalyzer": "seed_variance",
          "analyze_seed_variance": "seed_variance", "plot_seed_variance": "seed_variance",
-         "print_variance_report": "seed_variance"}
+         "print_variance_report": "seed_variance",
+         "print_failure_taxonomy": "failure_analysis", "print_failure_statistics": "failure_analysis",
+         "analyze_failure_modes": "failure_analysis", "load_failure_logs": "failure_statistics",
+         "compute_failure_distribution": "failure_statistics", "compute_correlations": "failure_statistics",
+         "plot_failure_distribution": "failure_statistics", "plot_failure_correlations": "failure_statistics",
+         "generate_failure_report": "failure_statistics", "run_failure_study": "failure_statistics"}
 
 
 def __getattr__(name):

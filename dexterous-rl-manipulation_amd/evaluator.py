@@ -191,6 +191,7 @@ class EvalRecords:
     policy_used: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
     obs_traj: Optional[np.ndarray] = None  # f32 [E][max_steps + 1][45] (trajectories=True)
     act_traj: Optional[np.ndarray] = None  # f32 [E][max_steps][15]
+    hist_moments: Optional[np.ndarray] = None  # i32 [E][5] S1, S2, first-five, last-five, peak (hist_moments=True)
 
     def moments(self) -> HistoryMoments:
         return HistoryMoments.from_padded(self.contact_hist, self.ep_length)
@@ -286,27 +287,40 @@ class EpisodeProgram:
     def run(self, prog: _PolicyProgram, policy_tapes: Optional[np.ndarray] = None, host_resets: bool = True,
             host_noise: bool = True, device_seed: int = 0, keep_history: bool = True,
             repeat: int = 1, timing: Optional[Dict] = None, trajectories: bool = False,
-            groups: Optional[Sequence[Sequence[int]]] = None):
+            groups: Optional[Sequence[Sequence[int]]] = None, summary: str = "metrics",
+            summary_options: Optional[Dict] = None, hist_moments: bool = False):
         """Launch the plan (``repeat`` back-to-back launches; ``timing['kernel_ms']`` =
         HIP-event time per launch on the launch stream).  With ``groups`` (episode-index lists)
         the records are reduced on the device and an ``EvalSummary`` comes back instead of
         ``EvalRecords`` (``timing['summary_ms']`` = event time of the two summary launches)."""
         return self.launch(prog, policy_tapes, host_resets, host_noise, device_seed, keep_history, repeat,
-                           trajectories, groups=groups).result(timing)
+                           trajectories, groups=groups, summary=summary,
+                           summary_options=summary_options, hist_moments=hist_moments).result(timing)
 
     def launch(self, prog: _PolicyProgram, policy_tapes: Optional[np.ndarray] = None, host_resets: bool = True,
                host_noise: bool = True, device_seed: int = 0, keep_history: bool = True, repeat: int = 1,
                trajectories: bool = False, stream: Optional[torch.cuda.Stream] = None,
-               groups: Optional[Sequence[Sequence[int]]] = None):
+               groups: Optional[Sequence[Sequence[int]]] = None, summary: str = "metrics",
+               summary_options: Optional[Dict] = None, hist_moments: bool = False):
         """Enqueue the plan on ``stream`` (default: the device's current stream) without waiting;
         ``.result()`` synchronises and returns the records.  Every launch owns its buffers,
         including the work-queue counter, so launches on different streams may overlap.
         With ``groups``, ``dxrl_eval_summarize`` is enqueued behind the last launch and
         ``.result()`` returns an ``EvalSummary``: only the group tables and the tie rows cross
-        to the host, ``contact_hist`` stays on the device."""
-        if groups is not None and (trajectories or not keep_history):
+        to the host, ``contact_hist`` stays on the device.  ``summary="failure"`` enqueues
+        ``dxrl_failure_summarize`` instead (``summary_options``: ``classify_max_steps``,
+        ``success_threshold``) and ``.result()`` returns a ``FailureSummary``; with
+        ``keep_history=False`` the episode kernel accumulates ``hist_moments`` and no history
+        is allocated.  ``hist_moments=True`` asks for those moments in ``EvalRecords`` too."""
+        if summary not in ("metrics", "failure"):
+            raise ValueError(f"unknown summary kind {summary!r}")
+        failure = groups is not None and summary == "failure"
+        if groups is not None and (trajectories or not (keep_history or failure)):
             raise ValueError("a device summary reads contact_hist and returns no trajectories")
         plan = self.plan(host_resets, host_noise)
+        if failure and np.isnan(plan.props).any():
+            raise ValueError("a failure study tabulates object properties per mode: device-drawn properties "
+                             "(a curriculum with ranges and no host reset draws) are not known to the host")
         dev = self.device = N.require_gpu(self.device)
         nl, E = len(self.lanes), plan.total_episodes
         env = VecEnv(nl, reward_type=self.reward_type, reward_shaping=self.reward_shaping,
@@ -327,6 +341,10 @@ class EpisodeProgram:
         out_suc = torch.empty(E, dtype=torch.uint8, device=dev)
         out_con = torch.empty(E, dtype=torch.uint8, device=dev)
         out_hist = torch.zeros(E, ms, dtype=torch.uint8, device=dev) if keep_history else None
+        want_mom = hist_moments or (failure and not keep_history)
+        if want_mom and ms > N.SUMMARY_MAX_STEPS:
+            raise ValueError(f"hist_moments needs max_steps <= {N.SUMMARY_MAX_STEPS}")
+        out_mom = torch.zeros(max(1, E), 5, dtype=torch.int32, device=dev) if want_mom else None
         used = torch.zeros(nl, dtype=torch.int32, device=dev)
         o_traj = torch.zeros(E, ms + 1, OBS_DIM, dtype=torch.float32, device=dev) if trajectories else None
         a_traj = torch.zeros(E, ms, ACTION_DIM, dtype=torch.float32, device=dev) if trajectories else None
@@ -344,6 +362,7 @@ class EpisodeProgram:
         a.ep_contacts, a.contact_hist = N.ptr(out_con), N.ptr(out_hist)
         a.policy_used, a.status = N.ptr(used), N.ptr(status)
         a.obs_traj, a.act_traj, a.work_queue = N.ptr(o_traj), N.ptr(a_traj), N.ptr(queue)
+        a.hist_moments = N.ptr(out_mom)
         mlp_t = ()
         if prog.kind == N.EVAL_POLICY_MLP:
             if prog.draws == 0 and policy_tapes is not None:
@@ -351,8 +370,11 @@ class EpisodeProgram:
             packed, params, std = mlp_t = prog.mlp.device_tensors(dev)
             m = N.EvalMlp()
             m.packed, m.params, m.action_std = N.ptr(packed), N.ptr(params), N.ptr(std) if prog.draws else None
-        summary = None
-        if groups is not None:
+        kind, summary = summary, None
+        if failure:
+            summary = _prepare_failure_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_hist,
+                                               None if keep_history else out_mom, plan.props, **(summary_options or {}))
+        elif groups is not None:
             summary = _prepare_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out_hist)
         with torch.cuda.device(dev):
             st = stream if stream is not None else torch.cuda.current_stream(dev)
@@ -369,7 +391,7 @@ class EpisodeProgram:
             if summary is not None:
                 _enqueue_summary(summary, dev, st)
         keep = (env, a, d_lane, d_seg, mean, d_pol, d_noise, d_reset, queue) + mlp_t  # alive until the stream is done
-        outs = (out_ret, out_len, out_suc, out_con, out_hist, used, o_traj, a_traj)
+        outs = (out_ret, out_len, out_suc, out_con, out_hist, used, o_traj, a_traj, out_mom)
         if st != torch.cuda.current_stream(dev):
             # allocated on the current stream, used on `st`: the caching allocator must not hand
             # these blocks out again before `st` has passed the launch, even if the _PendingRun
@@ -379,6 +401,8 @@ class EpisodeProgram:
                     x.record_stream(st)
             for x in (summary.tensors if summary is not None else ()):
                 x.record_stream(st)
+        if kind == "failure" and summary is not None:
+            return _PendingFailureSummary(st, e0, e1, max(1, int(repeat)), status, used, outs, keep, summary)
         if summary is not None:
             return _PendingSummary(st, e0, e1, max(1, int(repeat)), status, used, outs, keep, summary)
         return _PendingRun(st, e0, e1, max(1, int(repeat)), status, plan.props, keep_history, trajectories, outs,
@@ -463,14 +487,15 @@ class _PendingRun:
         if int(self.status.item()):
             raise N.NativeError("dxrl_evaluate: a parity tape ran out or a segment was malformed")
         self.keep[0].close()
-        out_ret, out_len, out_suc, out_con, out_hist, used, o_traj, a_traj = self.outs
+        out_ret, out_len, out_suc, out_con, out_hist, used, o_traj, a_traj, out_mom = self.outs
         p = self.props
         return EvalRecords(out_ret.cpu().numpy(), out_len.cpu().numpy(), out_suc.cpu().numpy().astype(bool),
                            out_con.cpu().numpy(),
                            out_hist.cpu().numpy() if self.keep_history else np.zeros((self.E, 0), np.uint8),
                            p[:, 0], p[:, 1], p[:, 2], used.cpu().numpy(),
                            o_traj.cpu().numpy() if self.trajectories else None,
-                           a_traj.cpu().numpy() if self.trajectories else None)
+                           a_traj.cpu().numpy() if self.trajectories else None,
+                           out_mom.cpu().numpy()[:self.E] if out_mom is not None else None)
 
 
 # ------------------------------------------------------------------ device summaries
@@ -550,7 +575,8 @@ def _prepare_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out
     s = _Summary(off=off, mem=mem, E=E, ms=ms, d_off=t(off), d_mem=t(mem) if len(mem) else None,
                  work=z(max(1, E), dt=torch.uint8), code=z(max(1, E), dt=torch.int8),
                  stats=z(max(1, G), 16, dt=torch.int64), ret=z(max(1, G), 3, dt=torch.float64),
-                 flags=z(2, dt=torch.int32), ties=z(cap, dt=torch.int32), hist=out_hist, length=out_len)
+                 flags=z(2, dt=torch.int32), ties=z(cap, dt=torch.int32), hist=out_hist, length=out_len,
+                 entry="dxrl_eval_summarize")
     a = N.EvalSummaryArgs()
     a.total_episodes, a.max_steps, a.success_threshold, a.num_groups = E, ms, success_threshold, G
     a.num_members, a.tie_cap = len(mem), cap
@@ -566,7 +592,7 @@ def _prepare_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out
 
 
 def _enqueue_summary(s, dev, st):
-    N.call("dxrl_eval_summarize", dev.index, C.byref(s.args), st.cuda_stream)
+    N.call(s.entry, dev.index, C.byref(s.args), st.cuda_stream)
     s.e2.record(st)
 
 
@@ -602,6 +628,127 @@ class _PendingSummary:
             unstable = settle_ties(stats, s.off, s.mem, ties, codes, hist, length)
         G = len(s.off) - 1
         return EvalSummary(stats[:G], ret[:G], ties, unstable, used, nbytes)
+
+
+# ------------------------------------------------------------------ device failure studies
+@dataclass
+class FailureSummary:
+    """What crosses to the host after ``dxrl_failure_summarize`` (include/dxrl.h): the per
+    (group, mode) tables, tie rows already merged (``settle_failure_ties``)."""
+    mode_stats: np.ndarray     # i64 [G][6][8]  count, sum steps, sum steps^2, sum contacts, sum contacts^2
+    group_totals: np.ndarray   # i64 [G][4]     episodes, successes, tie rows
+    mode_props: np.ndarray     # f64 [G][6][3][5] count, mean, M2, min, max of size, mass, friction
+    tie_rows: np.ndarray       # i32 episode indices np.var's rounding could decide otherwise
+    policy_used: np.ndarray
+    from_history: bool = True  # False: hist_moments form (tie rows decided by the exact comparison)
+    host_bytes: int = 0
+
+
+def merge_failure_row(mode_stats, mode_props, g: int, mode: int, length: int, contacts: int, props) -> None:
+    """One episode added to the (g, mode) tables on the host: the integer sums, and a Welford step
+    (Chan's merge with a single value) on the property moments."""
+    length, contacts = int(length), int(contacts)
+    mode_stats[g, mode, :5] += (1, length, length * length, contacts, contacts * contacts)
+    for q in range(3):
+        n, mean, m2, lo, hi = mode_props[g, mode, q]
+        x = float(props[q])
+        if n == 0:
+            mode_props[g, mode, q] = (1.0, x, 0.0, x, x)
+            continue
+        d = x - mean
+        mean += d / (n + 1.0)
+        mode_props[g, mode, q] = (n + 1.0, mean, m2 + d * (x - mean), min(lo, x), max(hi, x))
+
+
+def settle_failure_ties(mode_stats, mode_props, offsets, members, tie_rows, tie_hist, tie_len, tie_contacts,
+                        tie_props, classify_max_steps: int, success_threshold: int) -> np.ndarray:
+    """The host half of the history form: ``FailureClassifier.classify`` (np.var itself) on the tie
+    rows only, merged into every group that holds the episode, in ascending episode order.
+    Returns each row's mode index; the tables are updated in place."""
+    from .failures import FailureClassifier, FailureMode
+    order = list(FailureMode)
+    clf = FailureClassifier(success_threshold=success_threshold)
+    out = np.zeros(len(tie_rows), np.int8)
+    for k in np.argsort(np.asarray(tie_rows), kind="stable"):
+        e, n, nc = int(tie_rows[k]), int(tie_len[k]), int(tie_contacts[k])
+        counts = np.asarray(tie_hist[k][:n]).tolist()
+        mode, _ = clf.classify({"success": False, "episode_steps": n, "num_contacts": nc, "final_contacts": nc,
+                                "contact_history": [[1.0 if j < c else 0.0 for j in range(5)] for c in counts]},
+                               classify_max_steps)
+        out[k] = order.index(mode)
+        for m in np.flatnonzero(members == e):
+            g = int(np.searchsorted(offsets, m, side="right")) - 1
+            merge_failure_row(mode_stats, mode_props, g, int(out[k]), n, nc, tie_props[k])
+    return out
+
+
+def _prepare_failure_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_hist, out_mom, props,
+                             classify_max_steps: int = 200, success_threshold: int = 3, tie_cap=None):
+    """Group table, property upload and output buffers of a failure summary, made before the
+    episode launch (as ``_prepare_summary``)."""
+    off, mem = group_table(groups)
+    G = len(off) - 1
+    t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    z = lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
+    cap = max(1, E) if tie_cap is None else int(tie_cap)
+    M = N.FAILURE_MODES
+    s = _Summary(off=off, mem=mem, E=E, ms=ms, d_off=t(off), d_mem=t(mem) if len(mem) else None,
+                 d_props=t(np.ascontiguousarray(props, dtype=np.float64).reshape(-1, 3)),
+                 work=z(max(1, E), dt=torch.uint8), stats=z(max(1, G), M, 8, dt=torch.int64),
+                 totals=z(max(1, G), 4, dt=torch.int64), mprops=z(max(1, G), M, 3, 5, dt=torch.float64),
+                 flags=z(2, dt=torch.int32), ties=z(cap, dt=torch.int32), hist=out_hist, length=out_len,
+                 contacts=out_con, classify_max_steps=int(classify_max_steps),
+                 success_threshold=int(success_threshold), entry="dxrl_failure_summarize")
+    a = N.FailureSummaryArgs()
+    a.total_episodes, a.max_steps, a.timeout_steps, a.success_threshold = E, ms, int(classify_max_steps), \
+        int(success_threshold)
+    a.num_groups, a.num_members, a.tie_cap = G, len(mem), cap
+    a.ep_length, a.ep_success, a.ep_contacts = N.ptr(out_len), N.ptr(out_suc), N.ptr(out_con)
+    a.ep_props = N.ptr(s.d_props)
+    a.contact_hist, a.hist_moments = (N.ptr(out_hist), None) if out_mom is None else (None, N.ptr(out_mom))
+    a.group_offsets, a.group_episodes = N.ptr(s.d_off), N.ptr(s.d_mem)
+    a.ep_work, a.ep_mode, a.ep_confidence = N.ptr(s.work), None, None
+    a.mode_stats, a.group_totals, a.mode_props = N.ptr(s.stats), N.ptr(s.totals), N.ptr(s.mprops)
+    a.status, a.tie_count, a.tie_list = s.flags.data_ptr(), s.flags.data_ptr() + 4, N.ptr(s.ties)
+    s.from_history = out_mom is None
+    s.mom = out_mom
+    s.e2 = torch.cuda.Event(enable_timing=True)
+    s.args = a
+    return s
+
+
+class _PendingFailureSummary(_PendingSummary):
+    """An enqueued episode launch with ``dxrl_failure_summarize`` behind it."""
+
+    def result(self, timing: Optional[Dict] = None) -> FailureSummary:
+        self.stream.synchronize()
+        s = self.summary
+        if timing is not None:
+            timing["kernel_ms"] = self.e0.elapsed_time(self.e1) / self.repeat
+            timing["summary_ms"] = self.e1.elapsed_time(s.e2)
+        if int(self.status.item()):
+            raise N.NativeError("dxrl_evaluate: a parity tape ran out or a segment was malformed")
+        self.keep[0].close()
+        flags = s.flags.cpu().numpy()
+        if int(flags[0]):
+            raise N.NativeError(f"dxrl_failure_summarize: status {int(flags[0])} (group table out of range)")
+        stats, totals, mprops = s.stats.cpu().numpy(), s.totals.cpu().numpy(), s.mprops.cpu().numpy()
+        used = self.used.cpu().numpy()
+        nbytes = 4 + flags.nbytes + stats.nbytes + totals.nbytes + mprops.nbytes + used.nbytes
+        nt = int(flags[1])
+        ties = np.zeros(0, np.int32)
+        if nt:
+            idx = s.ties[:nt]
+            ties = idx.cpu().numpy()
+            nbytes += ties.nbytes
+            if s.from_history:  # only those rows' histories and records cross to the host
+                li = idx.long()
+                hist, length, cont = (x[li].cpu().numpy() for x in (s.hist, s.length, s.contacts))
+                nbytes += hist.nbytes + length.nbytes + cont.nbytes
+                settle_failure_ties(stats, mprops, s.off, s.mem, ties, hist, length, cont,
+                                    s.d_props[li].cpu().numpy(), s.classify_max_steps, s.success_threshold)
+        G = len(s.off) - 1
+        return FailureSummary(stats[:G], totals[:G], mprops[:G], ties, used, s.from_history, nbytes)
 
 
 def _exact_tape(prog: _PolicyProgram, program: EpisodeProgram) -> Optional[np.ndarray]:
@@ -782,6 +929,41 @@ class Evaluator:
             self._log_failures(rec, res["all_episodes"], [p.configs[s.row] for s in segs],
                                [s.episode_seeds[0] for s in segs])
         return res
+
+    def failure_study(self, num_episodes_per_object: int = 5, seed: Optional[int] = None, *,
+                      classify_max_steps: int = 200, parallel: bool = True,
+                      policy_seeds: Optional[Sequence[int]] = None, device_seed: int = 0, keep_history: bool = True,
+                      per_object: bool = True, success_threshold: int = 3,
+                      timing: Optional[Dict] = None) -> FailureSummary:
+        """The held-out evaluation of ``evaluate_heldout_set`` reduced to failure-mode tables on
+        the device: one episode launch and one ``dxrl_failure_summarize`` behind it.  Groups:
+        one per object (``per_object``), then one over all episodes.  ``classify_max_steps`` is
+        the classifier's timeout bound, which may exceed the loop bound ``max_episode_steps``;
+        ``keep_history=False`` accumulates the history moments inside the episode kernel and
+        allocates no history.  ``failure_statistics.run_failure_study`` builds the reference's
+        dictionaries from the returned tables."""
+        prog = compiled_program(self.policy)
+        if prog is None:
+            raise ValueError("a device failure study needs a policy the episode kernel compiles")
+        if self.failure_logger is not None:
+            raise ValueError("a device failure study returns no episodes: use no failure_logger")
+        if not self._policy_frozen:
+            self.freeze_policy()
+        K, n_obj = int(num_episodes_per_object), len(self.heldout_set.heldout_objects)
+        p = self.heldout_program(K, seed, parallel or prog.draws == 0)
+        groups = [np.arange(o * K, (o + 1) * K) for o in range(n_obj)] if per_object else []
+        groups.append(np.arange(n_obj * K))
+        kw: Dict[str, Any] = dict(groups=groups, summary="failure", keep_history=keep_history, timing=timing,
+                                  summary_options=dict(classify_max_steps=classify_max_steps,
+                                                       success_threshold=success_threshold))
+        if not parallel:
+            summ = p.run(prog, policy_tapes=_exact_tape(prog, p), **kw)
+            prog.stream.commit(int(summ.policy_used[0]))
+        elif policy_seeds is not None:
+            summ = p.run(prog, policy_tapes=_seeded_tapes(prog, p, policy_seeds), **kw)
+        else:
+            summ = p.run(prog, host_resets=False, host_noise=False, device_seed=device_seed, **kw)
+        return summ
 
     def results(self, rec: EvalRecords, K: int, return_episodes: bool = True) -> Dict:
         """evaluator.py:229-262 result dicts from the episode records."""
@@ -967,5 +1149,6 @@ class RobustnessTester:
 
 
 __all__ = ["Evaluator", "RobustnessTester", "EpisodeProgram", "Segment", "EvalRecords", "EvalSummary",
+           "FailureSummary",
            "EvaluationMetrics",
            "policy_program", "failure_names"]

@@ -675,6 +675,12 @@ typedef struct dxrl_eval_args {
        the stream by the call).  Required by the default (work-queue) kernel; give each launch
        that may run concurrently with another its own counter. */
     int32_t* work_queue;
+    /* i32 [total_episodes][5] (nullable): S1 = sum c, S2 = sum c^2, first-five sum, last-five sum
+       and peak of the episode's per-step num_contacts c, accumulated inside the step loop and
+       written once with the episode's other records -- what dxrl_failure_summarize needs of the
+       history, so contact_hist may then be NULL and nothing per step reaches memory for it.
+       Needs max_steps <= 4096 (the packed accumulators), else DXRL_E_INVALID. */
+    int32_t* hist_moments;
 } dxrl_eval_args;
 
 int dxrl_evaluate(dxrl_env* env, const dxrl_eval_args* args, void* stream);
@@ -773,6 +779,87 @@ typedef struct dxrl_eval_summary_args {
 } dxrl_eval_summary_args;
 
 int dxrl_eval_summarize(int32_t device, const dxrl_eval_summary_args* args, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Failure-mode study on the device: the taxonomy of
+ * evaluation/failure_taxonomy.py:156-239 (FailureClassifier.classify: mode and
+ * confidence of every episode) and, per group and failure mode, the sums
+ * behind evaluation/failure_statistics.py:34-159 (compute_failure_distribution,
+ * compute_correlations) and evaluation/failure_analysis.py:61-99
+ * (analyze_failure_modes), over the record buffers of dxrl_evaluate /
+ * dxrl_evaluate_mlp.  Two launches, stream-ordered behind the episode kernel, no
+ * host synchronisation; the group table has dxrl_eval_summarize's semantics.
+ *
+ * The history of an episode enters either as its contact_hist row or as the five
+ * words the episode kernels accumulate (dxrl_eval_args.hist_moments: S1, S2,
+ * first-five sum F, last-five sum L, peak); exactly one of the two is given.
+ * n = ep_length clamped to [0, max_steps], num = n S2 - S1^2, nc = ep_contacts
+ * (num_contacts == final_contacts in these records; peak = nc when n == 0).
+ * ep_mode: -1 = success, else the index into list(FailureMode) (0 slippage,
+ * 1 unstable_grasp, 2 misalignment, 3 timeout, 4 object_dropped,
+ * 5 insufficient_contacts), by the rules in this order:
+ *   1 ep_length >= timeout_steps                       timeout        1.0
+ *   2 nc == 0 and peak > 0                             object_dropped 1.0
+ *   3 n > 10, trend = L / 5.0 - F / 5.0 < -1.0 (f64),
+ *     peak >= 1                                        slippage       min(1, |trend| / 2)
+ *   4 n > 5, num > 2 n^2                               unstable_grasp min(1, var / 5),
+ *                                                      var = (double)num / (double)(n n)
+ *   5 1 <= nc <= 2 and (n <= 1 or num < n^2)           misalignment   0.8
+ *   6 peak < success_threshold                         insufficient_contacts 1.0
+ *   7 otherwise                                        insufficient_contacts 0.5
+ * timeout_steps is classify's max_steps argument, not the history pitch: a study
+ * may classify at a larger bound than its episode loop ran to.
+ * TIE ROWS: an episode that reaches rule 4 with n > 5 and num == 2 n^2, or rule 5
+ * with 1 <= nc <= 2, n > 1 and num == n^2; np.var's own rounding decides those.
+ * ep_mode / ep_confidence hold the exact comparison's answer (not unstable, not
+ * misaligned).  With contact_hist the tie rows are left out of mode_stats and
+ * mode_props (the caller classifies those rows and merges them); with
+ * hist_moments there is no row to settle with and they are included as decided.
+ * In both forms they are listed ascending in tie_list and counted per group.
+ *
+ * mode_stats i64 [G][6][8]: 0 episodes, 1 sum steps, 2 sum steps^2, 3 sum final
+ * contacts, 4 sum final contacts^2, 5-7 zero.
+ * group_totals i64 [G][4]: 0 episodes, 1 successes, 2 tie rows, 3 zero.
+ * mode_props f64 [G][6][3][5]: count, mean, M2, min, max of object size, mass and
+ * friction (ep_props columns), accumulated about the first member of the (group,
+ * mode) and merged with Chan et al.'s update in a fixed tree (no floating-point
+ * atomics: bit-identical from run to run); min and max are exact.  All zero for an
+ * empty (group, mode).
+ * status: as dxrl_eval_summarize (bit 0 group table out of range, bit 1 more tie
+ * rows than tie_cap; tie_count holds the true count).
+ * ------------------------------------------------------------------------ */
+#define DXRL_FAILURE_MODES 6
+typedef struct dxrl_failure_summary_args {
+    int32_t total_episodes;          /* E                                                    */
+    int32_t max_steps;               /* contact_hist row pitch (<= DXRL_SUMMARY_MAX_STEPS)   */
+    int32_t timeout_steps;           /* the timeout bound of rule 1                          */
+    int32_t success_threshold;       /* rule 6                                               */
+    int32_t num_groups;              /* G                                                    */
+    int32_t num_members;             /* entries of group_episodes (bounds check)             */
+    int32_t tie_cap;                 /* entries of tie_list                                  */
+    int32_t reserved;
+    /* device inputs */
+    const int32_t* ep_length;        /* i32 [E]                                              */
+    const uint8_t* ep_success;       /* u8  [E]                                              */
+    const uint8_t* ep_contacts;      /* u8  [E]                                              */
+    const double*  ep_props;         /* f64 [E][3] object size, mass, friction               */
+    const uint8_t* contact_hist;     /* u8  [E][max_steps], or NULL                          */
+    const int32_t* hist_moments;     /* i32 [E][5] S1, S2, F, L, peak, or NULL               */
+    const int32_t* group_offsets;    /* i32 [G + 1]                                          */
+    const int32_t* group_episodes;   /* i32 [num_members]                                    */
+    /* device outputs */
+    uint8_t* ep_work;                /* u8  [E] scratch between the two launches (required)  */
+    int8_t*  ep_mode;                /* i8  [E]  (nullable)                                  */
+    double*  ep_confidence;          /* f64 [E]  (nullable; 0 for a success)                 */
+    int64_t* mode_stats;             /* i64 [G][6][8]                                        */
+    int64_t* group_totals;           /* i64 [G][4]                                           */
+    double*  mode_props;             /* f64 [G][6][3][5]                                     */
+    int32_t* tie_count;              /* i32 [1]                                              */
+    int32_t* tie_list;               /* i32 [tie_cap]                                        */
+    int32_t* status;                 /* i32 [1]                                              */
+} dxrl_failure_summary_args;
+
+int dxrl_failure_summarize(int32_t device, const dxrl_failure_summary_args* args, void* stream);
 
 #ifdef __cplusplus
 }
