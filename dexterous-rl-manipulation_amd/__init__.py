@@ -10,7 +10,9 @@ Drop-in surfaces (same names as the reference modules):
   seed_variance.{SeedVarianceAnalyzer,analyze_seed_variance,plot_seed_variance,print_variance_report,run_seed_variance},
   failure_analysis.{print_failure_taxonomy,print_failure_statistics,analyze_failure_modes},
   failure_statistics.{load_failure_logs,compute_failure_distribution,compute_correlations,generate_failure_report,
-                      plot_failure_distribution,plot_failure_correlations,run_failure_study}
+                      plot_failure_distribution,plot_failure_correlations,run_failure_study},
+  robustness_analysis.{analyze_robustness_results,plot_robustness_results,print_robustness_report,
+                       run_robustness_study}
 Batched device API: envs.VecEnv, policies.VecSimpleLearner, training.SimpleLearnerRollout.
 The compute runs in libdxrl.so (HIP, gfx950; C ABI in include/dxrl.h).  No CPU fallback.
 """
@@ -23,6 +25,7 @@ __version__ = "0.1.0"
 def __getattr__(name):
     import importlib
     if name in ("envs", "policies", "training", "evaluation", "build", "_native", "trainer",
-                "evaluator", "metrics", "curriculum_ablation", "seed_variance", "failure_analysis", "failure_statistics"):
+                "evaluator", "metrics", "curriculum_ablation", "seed_variance", "failure_analysis", "failure_statistics",
+                "robustness_analysis"):
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -187,6 +187,15 @@ class FailureSummaryArgs(C.Structure):
                                           "tie_list", "status")]
 
 
+class RobustnessSummaryArgs(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("total_episodes", "max_steps", "success_threshold", "num_groups",
+                                         "num_members", "tie_cap")] + \
+               [(k, C.c_void_p) for k in ("ep_length", "ep_success", "ep_contacts", "ep_return", "hist_moments",
+                                          "group_offsets", "group_episodes", "baseline_group", "group_stats",
+                                          "group_return", "level_table", "ep_code", "tie_count", "tie_list",
+                                          "status")]
+
+
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
 _SIGS = {
@@ -238,6 +247,7 @@ _SIGS = {
     "dxrl_evaluate_mlp": (C.c_int, [_P, C.POINTER(EvalArgs), C.POINTER(EvalMlp), _P]),
     "dxrl_eval_summarize": (C.c_int, [_I32, C.POINTER(EvalSummaryArgs), _P]),
     "dxrl_failure_summarize": (C.c_int, [_I32, C.POINTER(FailureSummaryArgs), _P]),
+    "dxrl_robustness_summarize": (C.c_int, [_I32, C.POINTER(RobustnessSummaryArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

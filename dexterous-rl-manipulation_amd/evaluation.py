@@ -15,7 +15,9 @@
   under the reference's module path (evaluation/__init__.py), as are
   ``SeedVarianceAnalyzer`` / ``analyze_seed_variance`` (seed_variance.py) and the failure
   analysis (failure_analysis.py, failure_statistics.py: ``analyze_failure_modes``,
-  ``generate_failure_report``, ..., and the device study ``run_failure_study``).
+  ``generate_failure_report``, ..., and the device study ``run_failure_study``) and the
+  robustness analysis (robustness_analysis.py: ``analyze_robustness_results``, ...,
+  and the device study ``run_robustness_study``).
 """
 from __future__ import annotations
 
@@ -215,7 +217,9 @@ _LAZY = {"Evaluator": "evaluator", "RobustnessTester": "evaluator", "EvaluationM
          "analyze_failure_modes": "failure_analysis", "load_failure_logs": "failure_statistics",
          "compute_failure_distribution": "failure_statistics", "compute_correlations": "failure_statistics",
          "plot_failure_distribution": "failure_statistics", "plot_failure_correlations": "failure_statistics",
-         "generate_failure_report": "failure_statistics", "run_failure_study": "failure_statistics"}
+         "generate_failure_report": "failure_statistics", "run_failure_study": "failure_statistics",
+         "analyze_robustness_results": "robustness_analysis", "plot_robustness_results": "robustness_analysis",
+         "print_robustness_report": "robustness_analysis", "run_robustness_study": "robustness_analysis"}
 
 
 def __getattr__(name):

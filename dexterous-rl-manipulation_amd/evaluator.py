@@ -43,6 +43,11 @@ behind the episode kernel on its stream, applies the failure rules of metrics.py
 per episode and reduces the aggregates per group of a CSR group table, and only
 the group tables, the rows whose variance is exactly 2.0 (np.var settles those,
 ``settle_ties``) and ``policy_used`` cross to the host (``EvalSummary``).
+``summary="failure"`` puts ``dxrl_failure_summarize`` there instead (``FailureSummary``),
+``summary="robustness"`` ``dxrl_robustness_summarize`` (csrc/dxrl_robustness_summary.hip),
+which works from the history moments the episode kernel accumulates -- no history is
+allocated -- and adds every group's degradation against its baseline group
+(``RobustnessSummary``; ``RobustnessTester.robustness_study``).
 """
 from __future__ import annotations
 
@@ -285,7 +290,7 @@ class EpisodeProgram:
         return ProgramPlan(lane_off, table, reset, props, noise, self.total_episodes)
 
     def run(self, prog: _PolicyProgram, policy_tapes: Optional[np.ndarray] = None, host_resets: bool = True,
-            host_noise: bool = True, device_seed: int = 0, keep_history: bool = True,
+            host_noise: bool = True, device_seed: int = 0, keep_history: Optional[bool] = None,
             repeat: int = 1, timing: Optional[Dict] = None, trajectories: bool = False,
             groups: Optional[Sequence[Sequence[int]]] = None, summary: str = "metrics",
             summary_options: Optional[Dict] = None, hist_moments: bool = False):
@@ -298,7 +303,7 @@ class EpisodeProgram:
                            summary_options=summary_options, hist_moments=hist_moments).result(timing)
 
     def launch(self, prog: _PolicyProgram, policy_tapes: Optional[np.ndarray] = None, host_resets: bool = True,
-               host_noise: bool = True, device_seed: int = 0, keep_history: bool = True, repeat: int = 1,
+               host_noise: bool = True, device_seed: int = 0, keep_history: Optional[bool] = None, repeat: int = 1,
                trajectories: bool = False, stream: Optional[torch.cuda.Stream] = None,
                groups: Optional[Sequence[Sequence[int]]] = None, summary: str = "metrics",
                summary_options: Optional[Dict] = None, hist_moments: bool = False):
@@ -311,11 +316,20 @@ class EpisodeProgram:
         ``dxrl_failure_summarize`` instead (``summary_options``: ``classify_max_steps``,
         ``success_threshold``) and ``.result()`` returns a ``FailureSummary``; with
         ``keep_history=False`` the episode kernel accumulates ``hist_moments`` and no history
-        is allocated.  ``hist_moments=True`` asks for those moments in ``EvalRecords`` too."""
-        if summary not in ("metrics", "failure"):
+        is allocated.  ``hist_moments=True`` asks for those moments in ``EvalRecords`` too.
+        ``summary="robustness"`` enqueues ``dxrl_robustness_summarize`` (``summary_options``:
+        ``baseline_group``, one group index or -1 per group, ``success_threshold``, and
+        ``returns`` / ``policy_used`` = False to leave those tables on the device), which
+        reads the moments alone, and ``.result()`` returns a ``RobustnessSummary``; its
+        ``keep_history`` defaults to False (every other launch: True), and True writes the
+        history beside the moments."""
+        if summary not in ("metrics", "failure", "robustness"):
             raise ValueError(f"unknown summary kind {summary!r}")
         failure = groups is not None and summary == "failure"
-        if groups is not None and (trajectories or not (keep_history or failure)):
+        robust = groups is not None and summary == "robustness"
+        if keep_history is None:
+            keep_history = not robust
+        if groups is not None and (trajectories or not (keep_history or failure or robust)):
             raise ValueError("a device summary reads contact_hist and returns no trajectories")
         plan = self.plan(host_resets, host_noise)
         if failure and np.isnan(plan.props).any():
@@ -341,7 +355,7 @@ class EpisodeProgram:
         out_suc = torch.empty(E, dtype=torch.uint8, device=dev)
         out_con = torch.empty(E, dtype=torch.uint8, device=dev)
         out_hist = torch.zeros(E, ms, dtype=torch.uint8, device=dev) if keep_history else None
-        want_mom = hist_moments or (failure and not keep_history)
+        want_mom = hist_moments or (failure and not keep_history) or robust
         if want_mom and ms > N.SUMMARY_MAX_STEPS:
             raise ValueError(f"hist_moments needs max_steps <= {N.SUMMARY_MAX_STEPS}")
         out_mom = torch.zeros(max(1, E), 5, dtype=torch.int32, device=dev) if want_mom else None
@@ -374,6 +388,9 @@ class EpisodeProgram:
         if failure:
             summary = _prepare_failure_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_hist,
                                                None if keep_history else out_mom, plan.props, **(summary_options or {}))
+        elif robust:
+            summary = _prepare_robustness_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out_mom,
+                                                  **(summary_options or {}))
         elif groups is not None:
             summary = _prepare_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out_hist)
         with torch.cuda.device(dev):
@@ -403,6 +420,8 @@ class EpisodeProgram:
                 x.record_stream(st)
         if kind == "failure" and summary is not None:
             return _PendingFailureSummary(st, e0, e1, max(1, int(repeat)), status, used, outs, keep, summary)
+        if kind == "robustness" and summary is not None:
+            return _PendingRobustnessSummary(st, e0, e1, max(1, int(repeat)), status, used, outs, keep, summary)
         if summary is not None:
             return _PendingSummary(st, e0, e1, max(1, int(repeat)), status, used, outs, keep, summary)
         return _PendingRun(st, e0, e1, max(1, int(repeat)), status, plan.props, keep_history, trajectories, outs,
@@ -749,6 +768,93 @@ class _PendingFailureSummary(_PendingSummary):
                                     s.d_props[li].cpu().numpy(), s.classify_max_steps, s.success_threshold)
         G = len(s.off) - 1
         return FailureSummary(stats[:G], totals[:G], mprops[:G], ties, used, s.from_history, nbytes)
+
+
+# ------------------------------------------------------------------ device robustness studies
+@dataclass
+class RobustnessSummary(EvalSummary):
+    """What crosses to the host after ``dxrl_robustness_summarize`` (include/dxrl.h): the group
+    tables of an ``EvalSummary`` and the degradation columns of every group against its baseline.
+    The tie rows stay as the exact comparison decided them (not unstable): there is no history
+    row np.var could settle them with, so ``tie_unstable`` is empty."""
+    level_table: np.ndarray = field(default_factory=lambda: np.zeros((0, 4)))  # f64 [G][4] success_rate,
+    #                                    mean_episode_length, degradation, degradation_percentage
+    baseline_group: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))  # i32 [G], -1 = none
+
+    def level(self, g: int) -> Dict:
+        """Group g's row in the key order of robustness_analysis.py:42-47."""
+        rate, length, deg, pct = (float(x) for x in self.level_table[g])
+        return {"success_rate": rate, "degradation": deg, "degradation_percentage": pct,
+                "mean_episode_length": length}
+
+
+def _prepare_robustness_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out_mom,
+                                baseline_group=None, success_threshold: int = 3, tie_cap=None,
+                                returns: bool = True, policy_used: bool = True):
+    """Group table, baseline upload and output buffers of a robustness summary, made before the
+    episode launch (as ``_prepare_summary``).  ``returns=False`` / ``policy_used=False`` leave
+    ``group_return`` / the per-lane draw counts on the device (empty arrays in the result): the
+    degradation tables read neither, and the draw counts are four bytes per lane."""
+    off, mem = group_table(groups)
+    G = len(off) - 1
+    base = np.full(G, -1, np.int32) if baseline_group is None else np.asarray(baseline_group, np.int64).reshape(-1)
+    if len(base) != G or ((base < -1) | (base >= G)).any():
+        raise ValueError(f"baseline_group needs one entry in [-1, {G}) per group")
+    base = base.astype(np.int32)
+    t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    z = lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
+    cap = max(1, E) if tie_cap is None else int(tie_cap)
+    s = _Summary(off=off, mem=mem, E=E, ms=ms, base=base, d_off=t(off), d_mem=t(mem) if len(mem) else None,
+                 d_base=t(base) if G else None, stats=z(max(1, G), 16, dt=torch.int64),
+                 ret=z(max(1, G), 3, dt=torch.float64), level=z(max(1, G), 4, dt=torch.float64),
+                 flags=z(2, dt=torch.int32), ties=z(cap, dt=torch.int32), entry="dxrl_robustness_summarize",
+                 copy_returns=bool(returns), copy_used=bool(policy_used))
+    a = N.RobustnessSummaryArgs()
+    a.total_episodes, a.max_steps, a.success_threshold, a.num_groups = E, ms, int(success_threshold), G
+    a.num_members, a.tie_cap = len(mem), cap
+    a.ep_length, a.ep_success, a.ep_contacts = N.ptr(out_len), N.ptr(out_suc), N.ptr(out_con)
+    a.ep_return, a.hist_moments = N.ptr(out_ret), N.ptr(out_mom)
+    a.group_offsets, a.group_episodes, a.baseline_group = N.ptr(s.d_off), N.ptr(s.d_mem), N.ptr(s.d_base)
+    a.group_stats, a.group_return, a.level_table = N.ptr(s.stats), N.ptr(s.ret), N.ptr(s.level)
+    a.ep_code = None
+    a.status, a.tie_count, a.tie_list = s.flags.data_ptr(), s.flags.data_ptr() + 4, N.ptr(s.ties)
+    s.e2 = torch.cuda.Event(enable_timing=True)
+    s.args = a
+    return s
+
+
+class _PendingRobustnessSummary(_PendingSummary):
+    """An enqueued episode launch with ``dxrl_robustness_summarize`` behind it."""
+
+    @property
+    def history(self) -> Optional[torch.Tensor]:
+        """The launch's contact_hist tensor (None: not allocated)."""
+        return self.outs[4]
+
+    def result(self, timing: Optional[Dict] = None) -> RobustnessSummary:
+        self.stream.synchronize()
+        s = self.summary
+        if timing is not None:
+            timing["kernel_ms"] = self.e0.elapsed_time(self.e1) / self.repeat
+            timing["summary_ms"] = self.e1.elapsed_time(s.e2)
+        if int(self.status.item()):
+            raise N.NativeError("dxrl_evaluate: a parity tape ran out or a segment was malformed")
+        self.keep[0].close()
+        flags = s.flags.cpu().numpy()
+        if int(flags[0]):
+            raise N.NativeError(f"dxrl_robustness_summarize: status {int(flags[0])} (group table or baseline "
+                                "out of range)")
+        G = len(s.off) - 1
+        stats, level = s.stats.cpu().numpy(), s.level.cpu().numpy()
+        ret = s.ret.cpu().numpy()[:G] if s.copy_returns else np.zeros((0, 3))
+        used = self.used.cpu().numpy() if s.copy_used else np.zeros(0, np.int32)
+        nbytes = 4 + flags.nbytes + stats.nbytes + ret.nbytes + level.nbytes + used.nbytes
+        nt = int(flags[1])
+        ties = np.zeros(0, np.int32)
+        if nt:
+            ties = s.ties[:nt].cpu().numpy()
+            nbytes += ties.nbytes
+        return RobustnessSummary(stats[:G], ret, ties, np.zeros(0, bool), used, nbytes, level[:G], s.base)
 
 
 def _exact_tape(prog: _PolicyProgram, program: EpisodeProgram) -> Optional[np.ndarray]:
@@ -1147,8 +1253,51 @@ class RobustnessTester:
                 out[grp][k] = r
         return out
 
+    def robustness_study(self, observation_noise_levels: List[float], dynamics_noise_levels: List[float],
+                         num_episodes: int = 20, seed: Optional[int] = None, *, parallel: bool = True,
+                         policy_seeds: Optional[Sequence[int]] = None, device_seed: int = 0,
+                         timing: Optional[Dict] = None) -> Dict:
+        """The sweep and ``analyze_robustness_results`` on the device: one episode launch without a
+        history and one ``dxrl_robustness_summarize`` (``robustness_analysis.run_robustness_study``,
+        of which this is the method form; ``self.eval_config`` may be a list of configs)."""
+        from .robustness_analysis import run_robustness_study
+        return run_robustness_study(self.policy, self.eval_config, observation_noise_levels, dynamics_noise_levels,
+                                    num_episodes, seed, parallel=parallel, policy_seeds=policy_seeds,
+                                    device_seed=device_seed, reward_type=self.reward_type,
+                                    max_episode_steps=self.max_episode_steps, timing=timing)
+
+    def failure_study(self, observation_noise_levels: List[float], dynamics_noise_levels: List[float],
+                      num_episodes: int = 20, seed: Optional[int] = None, *, classify_max_steps: int = 200,
+                      keep_history: bool = True, parallel: bool = True,
+                      policy_seeds: Optional[Sequence[int]] = None, device_seed: int = 0,
+                      success_threshold: int = 3, timing: Optional[Dict] = None):
+        """The failure-mode tables of a sweep on the device: the sweep's episode launch with one
+        ``dxrl_failure_summarize`` behind it, one group per noise level in ``sweep_levels`` order
+        (``Evaluator.failure_study`` for the meaning of ``classify_max_steps`` and
+        ``keep_history``).  Returns ``(FailureSummary, level keys)``.  As every failure study, it
+        needs object properties the host knows: a config without ranges, or host reset draws
+        (``parallel=False``, or ``policy_seeds``); otherwise ``ValueError``."""
+        prog = compiled_program(self.policy)
+        if prog is None:
+            raise ValueError("a device failure study needs a policy the episode kernel compiles")
+        levels, keys = self.sweep_levels(observation_noise_levels, dynamics_noise_levels)
+        K = int(num_episodes)
+        p = self.levels_program(levels, K, seed, parallel, lane_per_level=prog.draws == 0)
+        kw: Dict[str, Any] = dict(groups=[np.arange(li * K, (li + 1) * K) for li in range(len(levels))],
+                                  summary="failure", keep_history=keep_history, timing=timing,
+                                  summary_options=dict(classify_max_steps=classify_max_steps,
+                                                       success_threshold=success_threshold))
+        if not parallel:
+            summ = p.run(prog, policy_tapes=_exact_tape(prog, p), **kw)
+            prog.stream.commit(int(summ.policy_used[0]))
+        elif policy_seeds is not None:
+            summ = p.run(prog, policy_tapes=_seeded_tapes(prog, p, policy_seeds), **kw)
+        else:
+            summ = p.run(prog, host_resets=False, host_noise=False, device_seed=device_seed, **kw)
+        return summ, keys
+
 
 __all__ = ["Evaluator", "RobustnessTester", "EpisodeProgram", "Segment", "EvalRecords", "EvalSummary",
-           "FailureSummary",
+           "FailureSummary", "RobustnessSummary",
            "EvaluationMetrics",
            "policy_program", "failure_names"]

@@ -861,6 +861,70 @@ typedef struct dxrl_failure_summary_args {
 
 int dxrl_failure_summarize(int32_t device, const dxrl_failure_summary_args* args, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Robustness study on the device: evaluation/robustness_analysis.py:12-77
+ * (analyze_robustness_results: the degradation of every noise level against its
+ * baseline) on top of the episode rules and group sums of
+ * evaluation/metrics.py:39-103,128-206, over the record buffers of dxrl_evaluate /
+ * dxrl_evaluate_mlp.  Two launches, stream-ordered behind the episode kernel, no
+ * host synchronisation: a per-group pass that classifies its members inline, and
+ * a per-group degradation pass behind it.  The group table has
+ * dxrl_eval_summarize's semantics.
+ *
+ * The history of an episode enters only as the five words the episode kernels
+ * accumulate (dxrl_eval_args.hist_moments: S1, S2, first-five sum F, last-five
+ * sum L, peak; the peak is not read): there is no contact_hist argument.  ep_code
+ * and the rules are dxrl_eval_summarize's, applied to (ep_length, ep_success,
+ * ep_contacts, S1, S2, F, L), np.var(counts) > 2.0 again decided as
+ * n S2 - S1^2 > 2 n^2.
+ * TIE ROWS (n > 5 and n S2 - S1^2 == 2 n^2 at the variance rule) are classified
+ * as not unstable, counted in slot 13 and listed ascending in tie_list, and they
+ * stay so decided: without a history row the caller cannot ask np.var (the stance
+ * of dxrl_failure_summarize's hist_moments form).
+ *
+ * group_stats i64 [G][16] and group_return f64 [G][3]: dxrl_eval_summarize's
+ * tables, same member-to-thread assignment, accumulation and merge order --
+ * bit-identical to it on the same records (tie rows before its caller's fix-up).
+ * level_table f64 [G][4], b = baseline_group[g], each column formed with exactly
+ * these f64 operations in this order (the reference's Python floats, bit for bit):
+ *   0 success_rate           = successes / episodes
+ *   1 mean_episode_length    = sum steps / episodes
+ *   2 degradation            = success_rate[b] - success_rate[g]
+ *   3 degradation_percentage = success_rate[b] > 0
+ *                                ? degradation / success_rate[b] * 100 : 0.0
+ * Columns 0-1 are NaN for an empty group; columns 2-3 are NaN when b == -1 (no
+ * baseline) or when either group is empty.  b may equal g or exceed it.
+ * status: bits 0 and 1 as dxrl_eval_summarize; bit 2 = a baseline_group entry
+ * outside [-1, G) (that row's columns 2-3 are NaN, nothing is read out of bounds).
+ * ------------------------------------------------------------------------ */
+typedef struct dxrl_robustness_summary_args {
+    int32_t total_episodes;          /* E                                                    */
+    int32_t max_steps;               /* the TIMEOUT bound (1..DXRL_SUMMARY_MAX_STEPS)        */
+    int32_t success_threshold;       /* MISALIGNED_GRASP: 0 < num_contacts < threshold       */
+    int32_t num_groups;              /* G                                                    */
+    int32_t num_members;             /* entries of group_episodes (bounds check)             */
+    int32_t tie_cap;                 /* entries of tie_list                                  */
+    /* device inputs: the episode kernel's records */
+    const int32_t* ep_length;        /* i32 [E]                                              */
+    const uint8_t* ep_success;       /* u8  [E]                                              */
+    const uint8_t* ep_contacts;      /* u8  [E] num_contacts == final_contacts               */
+    const double*  ep_return;        /* f64 [E]                                              */
+    const int32_t* hist_moments;     /* i32 [E][5] S1, S2, F, L, peak                        */
+    const int32_t* group_offsets;    /* i32 [G + 1] CSR offsets into group_episodes          */
+    const int32_t* group_episodes;   /* i32 [num_members] episode indices                    */
+    const int32_t* baseline_group;   /* i32 [G] group each level is compared with, -1 = none */
+    /* device outputs */
+    int64_t* group_stats;            /* i64 [G][16]                                          */
+    double*  group_return;           /* f64 [G][3]                                           */
+    double*  level_table;            /* f64 [G][4]                                           */
+    int8_t*  ep_code;                /* i8  [E]    (nullable)                                */
+    int32_t* tie_count;              /* i32 [1]                                              */
+    int32_t* tie_list;               /* i32 [tie_cap]                                        */
+    int32_t* status;                 /* i32 [1]                                              */
+} dxrl_robustness_summary_args;
+
+int dxrl_robustness_summarize(int32_t device, const dxrl_robustness_summary_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
