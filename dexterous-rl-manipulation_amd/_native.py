@@ -196,6 +196,18 @@ class RobustnessSummaryArgs(C.Structure):
                                           "status")]
 
 
+STUDY_LANE_INTS, STUDY_LANE_REALS, STUDY_METRICS = 8, 4, 5  # DXRL_STUDY_LANE_INTS / _LANE_REALS / _METRICS
+
+
+class StudySummaryArgs(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("num_lanes", "record_cap", "lane_offset", "total_lanes", "window",
+                                         "min_count", "num_groups", "num_members", "tie_cap", "reserved")] + \
+               [("reward_threshold", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("ep_return", "ep_length", "ep_success", "ep_level", "lane_episodes",
+                                          "group_offsets", "group_lanes", "lane_ints", "lane_reals", "group_stats",
+                                          "group_metrics", "tie_count", "tie_list", "status")]
+
+
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
 _SIGS = {
@@ -248,6 +260,7 @@ _SIGS = {
     "dxrl_eval_summarize": (C.c_int, [_I32, C.POINTER(EvalSummaryArgs), _P]),
     "dxrl_failure_summarize": (C.c_int, [_I32, C.POINTER(FailureSummaryArgs), _P]),
     "dxrl_robustness_summarize": (C.c_int, [_I32, C.POINTER(RobustnessSummaryArgs), _P]),
+    "dxrl_study_summarize": (C.c_int, [_I32, C.POINTER(StudySummaryArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

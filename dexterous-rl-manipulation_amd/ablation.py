@@ -16,6 +16,13 @@ Quirk kept: run_episode reports success = info.get("success", False) = False
 (episode_utils.py:52), so the CurriculumScheduler of a curriculum run never
 progresses and every success rate is 0 -- the lane keeps the scheduler's
 initial configuration, exactly as the reference does.
+
+``train_study`` / ``run_component_study`` (and ``python -m dexterous_rl_manipulation_amd.ablation``)
+are the same study on ``dxrl_rollout_curriculum``: every run is a lane with a real scheduler, a
+dense and a sparse ``DeviceStudy`` on two streams write one lane table, and
+``dxrl_study_summarize`` reduces it to ``compute_ablation_statistics``' dictionary on the device.
+There the scheduler moves whenever its rule says so (``success_rule="terminated"``, thresholds
+<= 0); ``train_many`` above keeps its restriction.
 """
 from __future__ import annotations
 
@@ -218,6 +225,178 @@ def compute_ablation_statistics(all_results: Dict[str, List[TrainingResults]]) -
     return stats
 
 
+# ------------------------------------------------------------------ the study on the curriculum rollout
+def study_scheduler(curriculum_scheduler_config=None):
+    """The scheduler of a curriculum run (component_ablation.py:101-139): the config's difficulties
+    and constants, or easy -> hard with (0.3, 15, 20, 5)."""
+    from .experiments import CurriculumScheduler
+    c = curriculum_scheduler_config
+    if c is None:
+        return CurriculumScheduler(initial_config=CurriculumConfig.easy(), target_config=CurriculumConfig.hard(),
+                                   success_rate_threshold=0.3, window_size=15, min_episodes_before_progression=20,
+                                   progression_steps=5)
+    return CurriculumScheduler(initial_config=_DIFFICULTY[c.initial_difficulty](),
+                               target_config=_DIFFICULTY[c.target_difficulty](),
+                               success_rate_threshold=c.success_rate_threshold, window_size=c.window_size,
+                               min_episodes_before_progression=c.min_episodes_before_progression,
+                               progression_steps=c.progression_steps)
+
+
+def train_study(jobs: Sequence[Tuple[AblationConfig, int]], num_episodes: int = 200, max_episode_steps: int = 200,
+                learning_rate: float = 0.01, curriculum_scheduler_config=None, success_rule: str = "training",
+                device_streams: bool = False, env_seeds: Optional[Sequence[Optional[int]]] = None, device=None,
+                stream_seed: int = 0):
+    """Every (configuration, seed) job as one lane of ``dxrl_rollout_curriculum``: a ``DeviceStudy``
+    per reward type (dense first), each one launch on a stream of its own, the curriculum lanes with
+    a real scheduler (so it moves when its rule says so: thresholds <= 0 and
+    ``success_rule="terminated"`` work).  Nothing is copied to the host.  Returns ``(studies,
+    lane_of_job)``: ``lane_of_job[k]`` is job k's row in the lane table ``summarize_runs(studies,
+    ...)`` writes.  The caller closes the studies."""
+    from . import curriculum_ablation as CA
+    from . import _native as N
+    dev = N.require_gpu(device)
+    sched, hard = study_scheduler(curriculum_scheduler_config), CurriculumConfig.hard()
+    es = list(env_seeds) if env_seeds is not None else [None] * len(jobs)
+    studies, lane_of_job, base = [], [0] * len(jobs), 0
+    ready = torch.cuda.Event()
+    ready.record(torch.cuda.current_stream(dev))
+    try:
+        for dense in (True, False):
+            lanes = [k for k, (c, _) in enumerate(jobs) if c.use_dense_reward == dense]
+            if not lanes:
+                continue
+            side = torch.cuda.Stream(dev)
+            side.wait_event(ready)
+            with torch.cuda.stream(side):
+                st = CA.launch_runs([(sched if jobs[k][0].use_curriculum else hard, jobs[k][1]) for k in lanes],
+                                    num_episodes, max_episode_steps, learning_rate, success_rule,
+                                    [es[k] for k in lanes], dev, "dense" if dense else "sparse", device_streams,
+                                    stream_seed)
+                st.launched = torch.cuda.Event()
+                st.launched.record(side)
+            studies.append(st)
+            for j, k in enumerate(lanes):
+                lane_of_job[k] = base + j
+            base += len(lanes)
+    except Exception:
+        for st in studies:
+            st.close()
+        raise
+    return studies, lane_of_job
+
+
+def run_component_study(num_episodes: int = 200, max_episode_steps: int = 200, seeds: Optional[List[int]] = None,
+                        learning_rate: float = 0.01, curriculum_scheduler_config=None,
+                        success_rule: str = "training", device_streams: bool = False,
+                        env_seeds: Optional[Dict[Tuple[str, int], int]] = None, device_summary: bool = True,
+                        return_runs: bool = False, output_dir: Optional[str] = None, device=None):
+    """component_ablation.py:198-322 on ``train_study``: the four configurations x seeds as lanes
+    of two launches writing one lane table, reduced by ``dxrl_study_summarize`` to
+    ``compute_ablation_statistics``' dictionary (from ``group_stats``), which feeds
+    ``print_ablation_report``.  ``device_summary=False`` copies the episode records and summarises
+    on the host instead (same dictionary).  ``return_runs=True`` also returns ``{name:
+    [TrainingResults per seed]}`` (this copies the records); ``output_dir`` writes the reference's
+    component_ablation_results.json, which needs the runs."""
+    from . import curriculum_ablation as CA
+    seeds = [42, 123, 456] if seeds is None else list(seeds)
+    configs = [AblationConfig(use_curriculum=c, use_dense_reward=d, name=nm) for nm, c, d in ABLATION_CONFIGS]
+    jobs = [(c, s) for c in configs for s in seeds]
+    es = [None if env_seeds is None else env_seeds.get((c.name, s)) for c, s in jobs]
+    want_runs = return_runs or output_dir is not None or not device_summary
+    studies, lane = train_study(jobs, num_episodes, max_episode_steps, learning_rate, curriculum_scheduler_config,
+                                success_rule, device_streams, es, device)
+    try:
+        stats = None
+        if device_summary:
+            groups = {c.name: [lane[k] for k, (cj, _) in enumerate(jobs) if cj is c] for c in configs}
+            stats = CA.summarize_runs(studies, groups)["statistics"]
+        out: Dict[str, List[TrainingResults]] = {}
+        if want_runs:
+            CA.BYTES_COPIED["records"] = 0
+            for st in studies:
+                done = getattr(st, "launched", None)
+                if done is not None:
+                    torch.cuda.current_stream(st.device).wait_event(done)
+                st.check_status()
+            recs = [r for st in studies for r in st.records()]
+            for k, (c, _) in enumerate(jobs):
+                r = recs[lane[k]]
+                out.setdefault(c.name, []).append(_summarise(c, r["reward"], r["steps"], r["success"], num_episodes))
+        if stats is None:
+            stats = compute_ablation_statistics(out)
+    finally:
+        for st in studies:
+            st.close()
+    if output_dir is not None:
+        os.makedirs(output_dir, exist_ok=True)
+        path = Path(output_dir) / "component_ablation_results.json"
+        with open(path, "w") as f:
+            json.dump({k: [r.to_dict() for r in v] for k, v in out.items()}, f, indent=2)
+        print(f"\nResults saved to: {path}")
+    return (stats, out) if return_runs else stats
+
+
+def main(argv: Optional[Sequence[str]] = None):
+    """evaluation/run_component_ablation.py:24-102 on ``run_component_study`` (plots are not part of
+    this build: the reference's warning line is printed in their place)."""
+    import argparse
+    from .experiments import load_config, load_named_config
+    parser = argparse.ArgumentParser(description="Run component ablation study")
+    parser.add_argument("--config", type=str, default=None,
+                        help="Path to experiment configuration JSON file (default: use default config)")
+    parser.add_argument("--config-name", type=str, default=None,
+                        help="Name of predefined configuration (e.g., 'default', 'quick_test')")
+    parser.add_argument("--success-rule", choices=("training", "terminated"), default="training",
+                        help="training: success as run_episode reports it (always False); terminated: the episode "
+                             "terminated")
+    parser.add_argument("--device-streams", action="store_true",
+                        help="per-run Philox streams on the device instead of the reference's host streams")
+    args = parser.parse_args(argv)
+    if args.config_name:
+        exp_config = load_named_config(args.config_name)
+    elif args.config:
+        exp_config = load_config(args.config)
+    else:
+        exp_config = load_config()
+    ab = exp_config.component_ablation
+    bar = "=" * 80
+    print(bar)
+    print("Component Ablation Study")
+    print(bar)
+    print(f"Experiment: {exp_config.experiment_name}")
+    if exp_config.description:
+        print(f"Description: {exp_config.description}")
+    print("\nThis study tests all combinations of:")
+    print("  - Curriculum learning (on/off)")
+    print("  - Dense reward shaping (on/off)")
+    print("\nConfigurations tested:")
+    print("  1. Baseline: Curriculum + Dense Reward")
+    print("  2. No Curriculum: Fixed difficulty + Dense Reward")
+    print("  3. No Dense Reward: Curriculum + Sparse Reward")
+    print("  4. Minimal: Fixed difficulty + Sparse Reward")
+    print(bar)
+    print("\nConfiguration:")
+    print(f"  Episodes per run: {ab.num_episodes}")
+    print(f"  Max episode steps: {ab.max_episode_steps}")
+    print(f"  Seeds: {ab.seeds}")
+    print(f"  Learning rate: {ab.learning_rate}")
+    print(bar)
+    stats, all_results = run_component_study(
+        num_episodes=ab.num_episodes, max_episode_steps=ab.max_episode_steps, seeds=ab.seeds,
+        learning_rate=ab.learning_rate, curriculum_scheduler_config=ab.curriculum_scheduler,
+        success_rule=args.success_rule, device_streams=args.device_streams, return_runs=True,
+        output_dir=exp_config.output_dir)
+    print_ablation_report(all_results, stats)
+    print("\nGenerating visualizations...")
+    print("Warning: Could not generate plots: plotting is not part of this build")
+    print("\n" + bar)
+    print("Component Ablation Study Complete")
+    print(bar)
+    print(f"\nResults saved to: {Path(exp_config.output_dir) / 'component_ablation_results.json'}")
+    print(bar)
+    return stats
+
+
 def print_ablation_report(all_results: Dict[str, List[TrainingResults]], stats: Dict[str, Dict]):
     """component_ablation.py:325-408 (same text)."""
     bar, rule = "=" * 80, "-" * 80
@@ -252,3 +431,7 @@ def print_ablation_report(all_results: Dict[str, List[TrainingResults]], stats: 
                   f"   {label}: {d:+.3f} ({pct:+.1f}%)"]
     lines.append("\n" + bar)
     print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()

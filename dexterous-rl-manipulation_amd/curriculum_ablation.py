@@ -29,6 +29,14 @@ Quirk kept: ``run_episode`` reports ``success = info.get("success", False) = Fal
 behaviour) a scheduler with a threshold > 0 never moves and every success rate is 0.
 ``success_rule="terminated"`` (success = the episode terminated, evaluator.py:157) is this
 build's meaningful variant.
+
+Device summary (``summarize_runs``, ``run_ablation_study(device_summary=True)``): the whole study
+is one launch whose episode records stay on the device; ``dxrl_study_summarize`` reduces them to
+one row per run (the lane table) and one row per arm (the group tables), and only those reach the
+host.  ``aggregate_metrics`` also reports medians: they are taken on the host from the lane table
+-- 96 bytes per run against ``record_cap`` x 21 bytes of episode records -- which is deliberate;
+both modes report the bytes they copy (``BYTES_COPIED``).  The host scheduler replay is not run
+in this mode.
 """
 from __future__ import annotations
 
@@ -292,6 +300,7 @@ class DeviceStudy:
         cols = {"reward": self.ep_return, "steps": self.ep_length, "success": self.ep_success,
                 "level": self.ep_level, "end_step": self.ep_end}
         host = {k: v.cpu().numpy() for k, v in cols.items()}
+        BYTES_COPIED["records"] += cnt.nbytes + sum(v.nbytes for v in host.values())
         return [{k: v[i, :cnt[i]].copy() for k, v in host.items()} for i in range(self.n)]
 
     def close(self):
@@ -342,6 +351,7 @@ def train_runs(jobs: Sequence[Tuple[Any, int]], num_episodes: int, max_episode_s
             a.check_parity_rows()
     n, E = len(jobs), int(num_episodes)
     seeds = [int(s) for _, s in jobs]
+    BYTES_COPIED["records"] = 0
     study = DeviceStudy(plan, lane_arm, max_episode_steps, learning_rate, reward_type, success_rule, device,
                         env_seed=stream_seed, learner_seed=stream_seed + 1,
                         lane_stream=seeds if device_streams else None)
@@ -390,6 +400,283 @@ def train_runs(jobs: Sequence[Tuple[Any, int]], num_episodes: int, max_episode_s
             res["scheduler_stats"] = replay_scheduler(arm, rec["success"], rec["steps"], rec["level"])
         res["gauss_used"] = int(used[i])
         out.append(res)
+    return out
+
+
+# ------------------------------------------------------------------ device summary
+BYTES_COPIED = {"records": 0, "summary": 0}  # device -> host bytes of the last study, per mode
+SUMMARY_KEYS = ("convergence_episode", "convergence_steps", "reward_variance", "reward_std",
+                "coefficient_of_variation", "final_reward", "final_success_rate", "mean_reward",
+                "overall_success_rate")
+_L_E, _L_STEPS, _L_SUCC, _L_FWS, _L_CONV, _L_RCONV, _L_LEVEL, _L_FLAGS = range(8)
+
+
+def launch_runs(jobs: Sequence[Tuple[Any, int]], num_episodes: int, max_episode_steps: int = 200,
+                learning_rate: float = 0.01, success_rule: str = "training",
+                env_seeds: Optional[Sequence[Optional[int]]] = None, device=None, reward_type: str = "dense",
+                device_streams: bool = False, stream_seed: int = 0) -> DeviceStudy:
+    """``train_runs``' launch without its host tail: every job's whole run in ONE
+    ``dxrl_rollout_curriculum`` call on the current stream, the episode records left on the device
+    (``study.ep_return`` ..., ``study.ep_count``) for ``summarize_runs``.  No host synchronisation
+    after the launch; the caller closes the study.  Parity mode resolves the tapes of the whole
+    run up front (2 x 15 x num_episodes x max_episode_steps gauss values per lane)."""
+    from .training import ReferenceStreams
+    from .envs import ACTION_DIM
+    arms: List[Any] = []
+    lane_arm = []
+    for arm, _ in jobs:
+        k = next((j for j, a in enumerate(arms) if a is arm), None)
+        if k is None:
+            arms.append(arm)
+            k = len(arms) - 1
+        lane_arm.append(k)
+    plan = StudyPlan(arms)
+    if not device_streams:
+        for a in plan.arms:
+            a.check_parity_rows()
+    n, E = len(jobs), int(num_episodes)
+    steps = E * int(max_episode_steps)
+    seeds = [int(s) for _, s in jobs]
+    study = DeviceStudy(plan, lane_arm, max_episode_steps, learning_rate, reward_type, success_rule, device,
+                        env_seed=stream_seed, learner_seed=stream_seed + 1,
+                        lane_stream=seeds if device_streams else None)
+    try:
+        study.reserve(E)
+        budget = torch.full((n,), E, dtype=torch.int32, device=study.device)
+        if device_streams:
+            study.start(philox_start_draws(study, stream_seed, seeds))
+            study.launch(steps, episode_budget=budget)
+        else:
+            es = list(env_seeds) if env_seeds is not None else [None] * n
+            es = [_entropy_seed() if s is None else int(s) for s in es]
+            streams = ReferenceStreams(study.env, es, seeds)
+            study.start(streams.initial_draws(study.rows))
+            gt = streams.gauss_tape(2 * ACTION_DIM * steps)
+            rt, _ = streams.reset_tape(E, study.rows)
+            study.launch(steps, episode_budget=budget, gauss=gt, resets=rt)
+            study._tapes = (gt, rt)  # alive until the launch has run
+    except Exception:
+        study.close()
+        raise
+    study.num_episodes = E
+    return study
+
+
+def _int_moments(n: int, s1: int, s2: int, scale: float) -> Tuple[float, float]:
+    """(mean, population std) of n integers with sum s1 and sum of squares s2, each divided by
+    ``scale``: the variance numerator n s2 - s1^2 is an exact integer."""
+    return s1 / (n * scale), float(np.sqrt(float(max(n * s2 - s1 * s1, 0)))) / (n * scale)
+
+
+def lane_metrics_row(ints: np.ndarray, reals: np.ndarray, window: int) -> Dict:
+    """One lane-table row as ``compute_convergence_metrics``' dictionary."""
+    E = int(ints[_L_E])
+    conv = None if ints[_L_RCONV] < 0 else int(ints[_L_RCONV])
+    var = reals[2] / reals[0]
+    std, mean = np.sqrt(var), reals[1]
+    with np.errstate(divide="ignore"):
+        cv = std / mean if mean != 0 else np.inf
+    return {
+        "convergence_episode": conv,
+        "convergence_steps": float(conv * mean) if conv else None,
+        "reward_variance": float(var),
+        "reward_std": float(std),
+        "coefficient_of_variation": float(cv),
+        "final_reward": float(reals[3]),
+        "final_success_rate": float(int(ints[_L_FWS]) / min(window, E)),
+        "mean_reward": float(mean),
+        "overall_success_rate": float(int(ints[_L_SUCC]) / E),
+    }
+
+
+def _statistics_from_lanes(ints: np.ndarray, window: int) -> Dict:
+    """``compute_ablation_statistics``' entry of one group from its lane rows (the fall-back for a
+    group whose lanes do not share one episode count)."""
+    fsr = [int(r[_L_FWS]) / min(window, int(r[_L_E])) for r in ints]
+    mel = [int(r[_L_STEPS]) / int(r[_L_E]) for r in ints]
+    conv = [int(r[_L_CONV]) for r in ints if r[_L_CONV] >= 0]
+    return {"final_success_rate": {"mean": float(np.mean(fsr)), "std": float(np.std(fsr)), "min": float(np.min(fsr)),
+                                   "max": float(np.max(fsr))},
+            "mean_episode_length": {"mean": float(np.mean(mel)), "std": float(np.std(mel))},
+            "convergence_step": {"mean": float(np.mean(conv)) if conv else None,
+                                 "std": float(np.std(conv)) if conv else None, "num_converged": len(conv)}}
+
+
+def group_statistics(stats: np.ndarray, ints: np.ndarray, window: int) -> Dict:
+    """``compute_ablation_statistics``' entry of one group from its ``group_stats`` row (``ints``:
+    the group's lane rows, read only to see whether they share one episode count)."""
+    n = int(stats[0])
+    live = ints[ints[:, _L_E] > 0] if len(ints) else ints
+    if n == 0:
+        raise ValueError("a group without lanes has no statistics")
+    if len(set(live[:, _L_E].tolist())) != 1:
+        return _statistics_from_lanes(live, window)
+    E = int(live[0, _L_E])
+    d = min(window, E)
+    s = [int(x) for x in stats]
+    fm, fs = _int_moments(n, s[4], s[5], d)
+    lm, ls = _int_moments(n, s[2], s[3], E)
+    k = s[8]
+    cm, cs = _int_moments(k, s[9], s[10], 1) if k else (None, None)
+    return {"final_success_rate": {"mean": fm, "std": fs, "min": s[6] / d, "max": s[7] / d},
+            "mean_episode_length": {"mean": lm, "std": ls},
+            "convergence_step": {"mean": cm, "std": cs, "num_converged": k}}
+
+
+def group_aggregate(stats: np.ndarray, metrics: np.ndarray, ints: np.ndarray, reals: np.ndarray, window: int) -> Dict:
+    """``aggregate_metrics``' dictionary of one group: means and stds from the group tables, medians
+    (and the two columns the tables do not carry, convergence_steps and overall_success_rate) from
+    the group's lane rows."""
+    live = ints[:, _L_E] > 0
+    ints, reals = ints[live], reals[live]
+    rows = [lane_metrics_row(i, r, window) for i, r in zip(ints, reals)]
+    n = int(stats[0])
+    s = [int(x) for x in stats]
+    same = len(set(ints[:, _L_E].tolist())) == 1
+    out = {}
+    with np.errstate(invalid="ignore"):
+        for key in SUMMARY_KEYS:
+            vals = [m[key] for m in rows if m[key] is not None]
+            if not vals:
+                out[key] = None
+                continue
+            if key == "convergence_episode":
+                mean, std = _int_moments(s[11], s[12], s[13], 1)
+            elif key == "final_success_rate" and same:
+                mean, std = _int_moments(n, s[4], s[5], min(window, int(ints[0, _L_E])))
+            elif key in ("reward_variance", "reward_std", "coefficient_of_variation", "final_reward", "mean_reward"):
+                k = ("reward_variance", "reward_std", "coefficient_of_variation", "final_reward",
+                     "mean_reward").index(key)
+                cnt, mean, m2 = (float(x) for x in metrics[k])
+                if key == "coefficient_of_variation" and cnt != n:  # a lane with an infinite CV
+                    mean, std = float(np.mean(vals)), float(np.std(vals))
+                else:
+                    std = float(np.sqrt(m2 / cnt))
+            else:
+                mean, std = float(np.mean(vals)), float(np.std(vals))
+            out[key] = {"mean": float(mean), "std": float(std), "median": float(np.median(vals))}
+    return out
+
+
+def summarize_runs(study_or_studies, groups, window: int = 20, threshold: float = 0.5, return_runs: bool = False,
+                   timing: Optional[Dict] = None) -> Dict:
+    """``dxrl_study_summarize`` on the records one or several launched ``DeviceStudy`` objects hold
+    (stream-ordered behind their launches, no host synchronisation before the tables are read).
+    The studies' lanes are numbered through in the order given.  ``groups``: ``{name: lane
+    indices}``; a lane may be in several groups or in none.  A lane's episode count is the study's
+    ``ep_count`` (one launch).
+
+    Returns ``statistics`` (``ablation.compute_ablation_statistics``' form per group),
+    ``aggregated_metrics`` (``aggregate_metrics``' form per group), ``final_levels`` (level index
+    per lane), ``tie_lanes`` (settled with ``compute_convergence_metrics`` on those lanes' returns),
+    ``bytes_copied``, the raw tables, and with ``return_runs`` the per-lane
+    ``compute_convergence_metrics`` dictionaries (``runs``).  ``timing``: a dict that receives
+    ``summary_ms``, the HIP-event time of the summary launches."""
+    studies = [study_or_studies] if isinstance(study_or_studies, DeviceStudy) else list(study_or_studies)
+    names = list(groups)
+    members = [np.asarray(groups[k], dtype=np.int32).reshape(-1) for k in names]
+    dev = studies[0].device
+    L = sum(st.n for st in studies)
+    G = len(names)
+    w = int(window)
+    offsets = np.zeros(G + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([len(m) for m in members])
+    flat = np.concatenate(members) if members else np.zeros(0, np.int32)
+    if len(flat) and (flat.min() < 0 or flat.max() >= L):
+        raise ValueError("a group names a lane outside the studies")
+    with torch.cuda.device(dev):
+        lane_ints = torch.zeros(L, N.STUDY_LANE_INTS, dtype=torch.int64, device=dev)
+        lane_reals = torch.zeros(L, N.STUDY_LANE_REALS, dtype=torch.float64, device=dev)
+        group_stats = torch.zeros(max(G, 1), 16, dtype=torch.int64, device=dev)
+        group_metrics = torch.zeros(max(G, 1), N.STUDY_METRICS, 3, dtype=torch.float64, device=dev)
+        tie = torch.zeros(1 + L, dtype=torch.int32, device=dev)  # [0] the count, [1:] the list
+        status = torch.zeros(len(studies), dtype=torch.int32, device=dev)
+        goff = torch.from_numpy(offsets).to(dev)
+        glanes = torch.from_numpy(flat if len(flat) else np.zeros(1, np.int32)).to(dev)
+        cur = torch.cuda.current_stream(dev)
+        off = 0
+        for st in studies:
+            done = getattr(st, "launched", None)  # an event recorded on the stream of the study's launch
+            if done is not None:
+                cur.wait_event(done)
+        if timing is not None:
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(cur)
+        for k, st in enumerate(studies):
+            a = N.StudySummaryArgs()
+            a.num_lanes, a.record_cap, a.lane_offset, a.total_lanes = st.n, st.record_cap, off, L
+            a.window, a.min_count, a.reward_threshold = w, min_successes(w, 0.5), float(threshold)
+            a.ep_return, a.ep_length, a.ep_success = N.ptr(st.ep_return), N.ptr(st.ep_length), N.ptr(st.ep_success)
+            a.ep_level = N.ptr(st.ep_level)
+            a.lane_episodes = N.ptr(st.ep_count)
+            a.lane_ints, a.lane_reals, a.status = N.ptr(lane_ints), N.ptr(lane_reals), N.ptr(status[k:])
+            if k == len(studies) - 1:
+                a.num_groups, a.num_members, a.tie_cap = G, len(flat), L
+                a.group_offsets, a.group_lanes = N.ptr(goff), N.ptr(glanes)
+                a.group_stats, a.group_metrics = N.ptr(group_stats), N.ptr(group_metrics)
+                a.tie_count, a.tie_list = N.ptr(tie), N.ptr(tie[1:])
+            N.call("dxrl_study_summarize", dev.index, C.byref(a), cur.cuda_stream)
+            off += st.n
+        if timing is not None:
+            t1.record(cur)
+        host = [t.cpu().numpy() for t in (lane_ints, lane_reals, group_stats, group_metrics, tie, status)]
+        if timing is not None:
+            timing["summary_ms"] = t0.elapsed_time(t1)
+    ints, reals, gstats, gmetrics, tie_h, status_h = host
+    copied = sum(x.nbytes for x in host)
+    for st in studies:
+        st.check_status()
+        copied += 4
+    code = int(np.bitwise_or.reduce(status_h))
+    if code & 1:
+        raise N.NativeError("dxrl_study_summarize: a group offset or member lies outside its table")
+    if code & 4:
+        raise N.NativeError("dxrl_study_summarize: a lane finished no episode or more than record_cap")
+    tie_lanes = [int(x) for x in tie_h[1:1 + int(tie_h[0])]]
+    starts = np.cumsum([0] + [st.n for st in studies])
+    fetched = [0]
+
+    def fetch(row: int) -> np.ndarray:
+        k = int(np.searchsorted(starts, row, side="right")) - 1
+        r = studies[k].ep_return[row - int(starts[k]), :int(ints[row, _L_E])].cpu().numpy()
+        fetched[0] += r.nbytes
+        return r
+
+    out = form_summary(ints, reals, gstats[:G], gmetrics[:G], tie_lanes, names, members, w, threshold, fetch,
+                       return_runs)
+    out["status"] = code
+    out["bytes_copied"] = BYTES_COPIED["summary"] = copied + fetched[0]
+    return out
+
+
+def form_summary(ints: np.ndarray, reals: np.ndarray, gstats: np.ndarray, gmetrics: np.ndarray,
+                 tie_lanes: Sequence[int], names: Sequence[str], members: Sequence[np.ndarray], window: int,
+                 threshold: float, fetch_returns, return_runs: bool = False) -> Dict:
+    """The host half of ``summarize_runs``: settles the tie lanes (``fetch_returns(row)`` -> that
+    lane's returns; ``np.convolve``'s rounding decides their crossing, and the sums of every group
+    that holds them follow), then forms the dictionaries from the tables.  ``ints`` and ``gstats``
+    are updated in place."""
+    w = int(window)
+    for row in tie_lanes:
+        r = fetch_returns(int(row))
+        want = compute_convergence_metrics(list(r), [0.0] * len(r), w, threshold)["convergence_episode"]
+        new, old = (-1 if want is None else int(want)), int(ints[row, _L_RCONV])
+        ints[row, _L_RCONV] = new
+        for g, m in enumerate(members):
+            for _ in range(int((np.asarray(m) == row).sum())):
+                if old >= 0:
+                    gstats[g, 11:14] -= (1, old, old * old)
+                if new >= 0:
+                    gstats[g, 11:14] += (1, new, new * new)
+    out = {"statistics": {}, "aggregated_metrics": {}, "tie_lanes": [int(x) for x in tie_lanes],
+           "final_levels": ints[:, _L_LEVEL].tolist(), "lane_ints": ints, "lane_reals": reals,
+           "group_stats": gstats, "group_metrics": gmetrics}
+    for g, name in enumerate(names):
+        gi, gr = ints[np.asarray(members[g], dtype=np.int64)], reals[np.asarray(members[g], dtype=np.int64)]
+        out["statistics"][name] = group_statistics(gstats[g], gi, w)
+        out["aggregated_metrics"][name] = group_aggregate(gstats[g], gmetrics[g], gi, gr, w)
+    if return_runs:
+        out["runs"] = [lane_metrics_row(i, r, w) for i, r in zip(ints, reals)]
     return out
 
 
@@ -483,13 +770,14 @@ def _pm(agg: Dict, key: str, fmt: str) -> str:
 
 def run_ablation_study(num_episodes: int = 200, num_runs: int = 5, output_dir: str = "logs",
                        env_seeds: Optional[Sequence[Optional[int]]] = None, success_rule: str = "training",
-                       device_streams: bool = False, device=None) -> Dict:
+                       device_streams: bool = False, device=None, device_summary: bool = False) -> Dict:
     """curriculum_ablation.py:206-357: ``num_runs`` runs with the curriculum (seeds 42 + run) and
     ``num_runs`` on the fixed hard config, all 2 x num_runs runs as lanes of one ``train_runs``
     call; same JSON keys in <output_dir>/curriculum_ablation.json and the same report text.
     ``env_seeds``: the with-curriculum runs' env seeds, then the fixed runs' (None = entropy).
     Where the reference would raise on an aggregate that is None (no run converged), the report
-    prints ``n/a``."""
+    prints ``n/a``.  ``device_summary=True``: one launch, ``summarize_runs`` and host medians
+    instead of ``train_runs`` and the per-run host metrics (same dictionary, JSON and text)."""
     bar = "=" * 60
     print(bar)
     print("Curriculum Learning Ablation Study")
@@ -497,11 +785,21 @@ def run_ablation_study(num_episodes: int = 200, num_runs: int = 5, output_dir: s
     os.makedirs(output_dir, exist_ok=True)
     sched, hard = reference_scheduler(), CurriculumConfig.hard()
     jobs = [(sched, 42 + r) for r in range(num_runs)] + [(hard, 42 + r) for r in range(num_runs)]
-    runs = train_runs(jobs, num_episodes, success_rule=success_rule, env_seeds=env_seeds, device=device,
-                      device_streams=device_streams)
-    for r in runs:
-        r.pop("gauss_used")
-    cur_results, no_cur_results = runs[:num_runs], runs[num_runs:]
+    summary = None
+    if device_summary:
+        study = launch_runs(jobs, num_episodes, success_rule=success_rule, env_seeds=env_seeds, device=device,
+                            device_streams=device_streams)
+        try:
+            summary = summarize_runs(study, {"with": range(num_runs), "without": range(num_runs, 2 * num_runs)},
+                                     return_runs=True)
+        finally:
+            study.close()
+    else:
+        runs = train_runs(jobs, num_episodes, success_rule=success_rule, env_seeds=env_seeds, device=device,
+                          device_streams=device_streams)
+        for r in runs:
+            r.pop("gauss_used")
+        cur_results, no_cur_results = runs[:num_runs], runs[num_runs:]
     print(f"\nRunning {num_runs} independent runs...")
     print("Training with curriculum...")
     for run in range(num_runs):
@@ -512,9 +810,14 @@ def run_ablation_study(num_episodes: int = 200, num_runs: int = 5, output_dir: s
     print("\n" + bar)
     print("Computing metrics...")
     print(bar)
-    cur_metrics = [compute_convergence_metrics(r["episode_rewards"], r["success_rates"]) for r in cur_results]
-    no_cur_metrics = [compute_convergence_metrics(r["episode_rewards"], r["success_rates"]) for r in no_cur_results]
-    cur_agg, no_cur_agg = aggregate_metrics(cur_metrics), aggregate_metrics(no_cur_metrics)
+    if summary is not None:
+        cur_metrics, no_cur_metrics = summary["runs"][:num_runs], summary["runs"][num_runs:]
+        cur_agg, no_cur_agg = summary["aggregated_metrics"]["with"], summary["aggregated_metrics"]["without"]
+    else:
+        cur_metrics = [compute_convergence_metrics(r["episode_rewards"], r["success_rates"]) for r in cur_results]
+        no_cur_metrics = [compute_convergence_metrics(r["episode_rewards"], r["success_rates"])
+                          for r in no_cur_results]
+        cur_agg, no_cur_agg = aggregate_metrics(cur_metrics), aggregate_metrics(no_cur_metrics)
     improvements = compute_improvements(cur_agg, no_cur_agg)
     print("\n" + bar)
     print("Ablation Study Results")

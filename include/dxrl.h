@@ -925,6 +925,101 @@ typedef struct dxrl_robustness_summary_args {
 
 int dxrl_robustness_summarize(int32_t device, const dxrl_robustness_summary_args* args, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Training-run summaries on the device: evaluation/curriculum_ablation.py:137-203,
+ * 269-282 (compute_convergence_metrics, aggregate_metrics) and
+ * evaluation/component_ablation.py:168-186,285-322 (the window-20 convergence step,
+ * the final success rate, compute_ablation_statistics), over the episode records
+ * dxrl_rollout_simple / dxrl_rollout_curriculum wrote on the same stream.  Up to two
+ * launches, stream-ordered behind the rollout, no host synchronisation: a LANE PASS
+ * (a wavefront per lane = per training run) that writes rows lane_offset ..
+ * lane_offset + num_lanes of a study-wide lane table, and a GROUP PASS over the whole
+ * lane table with a CSR group table (dxrl_eval_summarize's semantics: a lane may be in
+ * several groups or in none).  A study whose runs lie in several record buffers (a
+ * dense and a sparse env handle) calls once per buffer; the group pass runs in the
+ * calls that give group_stats (the last one), the lane pass in those with num_lanes > 0.
+ *
+ * Lane pass, E = lane_episodes[lane] (ep_count of a one-launch study), w = window,
+ * r / steps / success = the lane's first E records:
+ * lane_ints i64 [total_lanes][8]:
+ *   0 episodes E                  1 sum of steps          2 successes
+ *   3 final_window_successes: successes among the last min(w, E) episodes
+ *   4 convergence_step: the first i in [w, E) with popcount(success[i-w : i]) >=
+ *     min_count, else -1 (np.mean(window) >= 0.5 decided in integers when min_count is
+ *     the smallest c with c / w >= 0.5)
+ *   5 reward_convergence_episode: the first i with ma_i >= reward_threshold, reported as
+ *     i + w - 1, else -1.  E >= w: ma_i = sum over j < w, left to right in f64, of
+ *     r[i+j] * (1.0 / w), i in [0, E - w].  E < w: ma_i = r[i] (an exact comparison).
+ *   6 final_level: ep_level[E - 1], -1 without ep_level
+ *   7 flags: bit 0 tie lane, bit 1 skipped lane (every other column 0 / -1)
+ * lane_reals f64 [total_lanes][4]: 0 count, 1 mean, 2 M2 of the returns (accumulated
+ *   about r[0]: episode e on wave lane e % 64 in ascending order, Welford; then Chan et
+ *   al.'s merge over the 64 partials in a fixed tree), 3 final_reward = the left-to-right
+ *   sum of the last min(w, E) returns, divided by their number.
+ * TIE LANES (E >= w only): np.convolve does not sum in this order, so a crossing that
+ * lies within rounding is not decided here.  A lane is a tie lane if some i at or before
+ * its first crossing (any i if it has none) has
+ *   |ma_i - reward_threshold| <= 64 eps w max_j |r[i+j] * (1.0 / w)|,  eps = 2^-52.
+ * Column 5 then holds the left-to-right answer; tie lanes are listed ascending (lane
+ * table rows) in tie_list, counted in tie_count and in slot 14 of every group holding
+ * them; the caller settles them with compute_convergence_metrics on those lanes'
+ * returns and adjusts the group sums.
+ *
+ * Group pass (skipped lanes are left out):
+ * group_stats i64 [G][16]: 0 lanes, 1 sum E, 2 sum steps_l, 3 sum steps_l^2 (steps_l =
+ *   column 1), 4 sum / 5 sum of squares / 6 min / 7 max of final_window_successes,
+ *   8 converged lanes, 9 sum / 10 sum of squares of convergence_step, 11 reward-converged
+ *   lanes, 12 sum / 13 sum of squares of reward_convergence_episode, 14 tie lanes,
+ *   15 sum of successes.
+ * group_metrics f64 [G][5][3]: count, mean, M2 over the group's lanes of 0 reward
+ *   variance (M2 / count), 1 reward std (sqrt of it), 2 coefficient of variation (std /
+ *   mean), 3 final_reward, 4 mean reward; accumulated about the group's first member's
+ *   value and merged with Chan et al.'s update in a fixed tree (no floating-point
+ *   atomics: bit-identical from run to run).  A lane whose mean reward is exactly 0 has
+ *   an infinite CV: it is left out of metric 2, so lanes - count[2] such lanes exist.
+ * status i32 [1] (zeroed on the stream by the call): bit 0 = a group offset or a member
+ * lane was out of range (skipped, nothing is accessed out of bounds); bit 1 = more tie
+ * lanes than tie_cap (tie_count holds the true count); bit 2 = a lane had E <= 0 or
+ * E > record_cap (skipped); bit 3 = the lanes of a group do not share one E (its integer
+ * rate and length sums are then not the reference's statistics: use the lane table).
+ * window outside 1..64, record_cap <= 0, rows outside the lane table or a null required
+ * pointer: DXRL_E_INVALID before any launch.
+ * ------------------------------------------------------------------------ */
+#define DXRL_STUDY_LANE_INTS 8
+#define DXRL_STUDY_LANE_REALS 4
+#define DXRL_STUDY_METRICS 5
+typedef struct dxrl_study_summary_args {
+    int32_t num_lanes;               /* N: lanes of this record buffer (0 = no lane pass)    */
+    int32_t record_cap;              /* row pitch of the record buffers                      */
+    int32_t lane_offset;             /* first lane-table row this call writes                */
+    int32_t total_lanes;             /* rows of the lane table                               */
+    int32_t window;                  /* w, 1..64                                             */
+    int32_t min_count;               /* successes in a window that count as converged        */
+    int32_t num_groups;              /* G                                                    */
+    int32_t num_members;             /* entries of group_lanes (bounds check)                */
+    int32_t tie_cap;                 /* entries of tie_list                                  */
+    int32_t reserved;
+    double reward_threshold;
+    /* device inputs */
+    const double*  ep_return;        /* f64 [N][record_cap]                                  */
+    const int32_t* ep_length;        /* i32 [N][record_cap]                                  */
+    const uint8_t* ep_success;       /* u8  [N][record_cap]                                  */
+    const int32_t* ep_level;         /* i32 [N][record_cap] (nullable)                       */
+    const int32_t* lane_episodes;    /* i32 [N] E of every lane                              */
+    const int32_t* group_offsets;    /* i32 [G + 1] CSR offsets into group_lanes             */
+    const int32_t* group_lanes;      /* i32 [num_members] lane-table rows                    */
+    /* device outputs */
+    int64_t* lane_ints;              /* i64 [total_lanes][8]                                 */
+    double*  lane_reals;             /* f64 [total_lanes][4]                                 */
+    int64_t* group_stats;            /* i64 [G][16]; NULL = no group pass in this call       */
+    double*  group_metrics;          /* f64 [G][5][3]                                        */
+    int32_t* tie_count;              /* i32 [1]                                              */
+    int32_t* tie_list;               /* i32 [tie_cap]                                        */
+    int32_t* status;                 /* i32 [1]                                              */
+} dxrl_study_summary_args;
+
+int dxrl_study_summarize(int32_t device, const dxrl_study_summary_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
