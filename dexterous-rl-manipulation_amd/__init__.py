@@ -13,7 +13,8 @@ Drop-in surfaces (same names as the reference modules):
                       plot_failure_distribution,plot_failure_correlations,run_failure_study},
   robustness_analysis.{analyze_robustness_results,plot_robustness_results,print_robustness_report,
                        run_robustness_study}
-Batched device API: envs.VecEnv, policies.VecSimpleLearner, training.SimpleLearnerRollout.
+Batched device API: envs.VecEnv, policies.VecSimpleLearner, training.SimpleLearnerRollout,
+trainer.PGTrainer (iteration, fit, checkpoints; training_run.TrainingLog; `python -m ...train`).
 The compute runs in libdxrl.so (HIP, gfx950; C ABI in include/dxrl.h).  No CPU fallback.
 """
 from . import experiments, rewards  # noqa: F401  (no GPU needed to import)
@@ -26,6 +27,6 @@ def __getattr__(name):
     import importlib
     if name in ("envs", "policies", "training", "evaluation", "build", "_native", "trainer",
                 "evaluator", "metrics", "curriculum_ablation", "seed_variance", "failure_analysis", "failure_statistics",
-                "robustness_analysis"):
+                "robustness_analysis", "training_run", "workloads"):
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

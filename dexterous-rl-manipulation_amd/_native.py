@@ -208,6 +208,31 @@ class StudySummaryArgs(C.Structure):
                                           "group_metrics", "tie_count", "tie_list", "status")]
 
 
+# enum dxrl_pg_log_col: the named columns of the training log, in table order
+PG_LOG_COLUMNS = ("iteration", "env_steps", "episodes", "mean_return", "mean_length", "success_rate",
+                  "mean_step_reward", "done_fraction", "value_mean", "target_mean", "target_var", "residual_var",
+                  "explained_variance", "adv_mean", "adv_std", "policy_loss", "value_mse", "clip_frac", "approx_kl",
+                  "grad_norm", "is_best", "window_mean")
+PG_LOG_NAMED = len(PG_LOG_COLUMNS)  # DXRL_PG_LOG_NAMED
+PG_LOG_COLS = 24                    # DXRL_PG_LOG_COLS
+PG_LOG_IS_BEST = PG_LOG_COLUMNS.index("is_best")
+
+
+class PgLogHeader(C.Structure):
+    _fields_ = [("rows_written", C.c_int64), ("best_row", C.c_int64), ("converged_row", C.c_int64),
+                ("reserved", C.c_int64), ("best_score", C.c_double), ("reserved_f64", C.c_double * 3)]
+
+
+class PgLogArgs(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("num_envs", "horizon", "row", "cap", "iteration", "env_steps", "loss_blocks",
+                                         "loss_rows", "min_episodes", "num_params", "partial_doubles")] + \
+               [(k, C.c_int32) for k in ("score_col", "conv_col", "conv_window", "reserved")] + \
+               [("conv_threshold", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("ep_count", "ep_sum_return", "ep_sum_length", "ep_successes", "rew", "ret",
+                                          "done", "values", "stats", "loss_partial", "gnorm2", "params", "partial",
+                                          "best_params", "log", "header")]
+
+
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
 _SIGS = {
@@ -261,6 +286,8 @@ _SIGS = {
     "dxrl_failure_summarize": (C.c_int, [_I32, C.POINTER(FailureSummaryArgs), _P]),
     "dxrl_robustness_summarize": (C.c_int, [_I32, C.POINTER(RobustnessSummaryArgs), _P]),
     "dxrl_study_summarize": (C.c_int, [_I32, C.POINTER(StudySummaryArgs), _P]),
+    "dxrl_pg_log_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
+    "dxrl_pg_log_row": (C.c_int, [_I32, C.POINTER(PgLogArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

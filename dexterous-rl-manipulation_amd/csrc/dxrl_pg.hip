@@ -11,6 +11,7 @@
 // same env_step as dxrl_env_step), writes the training tape and auto-resets.
 // No inter-workgroup communication: envs and weights are independent/read-only.
 #include "dxrl_gemm.h"
+#include "dxrl_moments.h"
 #include "dxrl_pg.h"
 #include "dxrl_pg_mlp.h"
 #include "dxrl_pg_rollout.h"
@@ -921,26 +922,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
 // squared deviations; workgroups, the block partials and the ranks then merge these triples
 // with Chan et al.'s pairwise update in a fixed order (deterministic).  A plain
 // sum(A^2) - mean sum(A) loses ~(mean/std)^2 ulps (2.8e-6 relative at mean/std = 4.6e4).
-struct Moments {
-    double n, mean, m2;
-};
-__device__ __forceinline__ Moments merge(Moments a, Moments b) {
-    const double n = a.n + b.n;
-    if (b.n == 0.0) return a;
-    if (a.n == 0.0) return b;
-    const double d = b.mean - a.mean;
-    return Moments{n, a.mean + d * (b.n / n), a.m2 + b.m2 + d * d * (a.n * b.n / n)};
-}
-// workgroup tree merge in LDS (fixed pairing), result in red[0]
-template <int NT>
-__device__ void block_merge(Moments v, Moments* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = NT / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = merge(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-}
+// Moments, merge and block_merge: dxrl_moments.h.
 
 constexpr int kGaeChunk = 32, kGaeThreads = 64;
 __global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ rew, const uint8_t* __restrict__ done,

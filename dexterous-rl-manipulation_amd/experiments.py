@@ -115,6 +115,26 @@ class CurriculumConfig:
             raise KeyError(f"unknown curriculum '{name}' (have {sorted(presets)})")
         return presets[name]()
 
+    # -- checkpoint form: to_dict with plain Python numbers, plus which scalars were numpy floats
+    #    (a numpy.float64 friction changes the step's arithmetic, see to_native)
+    _SCALARS = ("object_size", "object_mass", "friction_coefficient", "spawn_distance")
+
+    def to_state(self) -> dict:
+        def plain(v):
+            if v is None:
+                return None
+            return [float(x) for x in v] if isinstance(v, (tuple, list)) else float(v)
+        out = {k: plain(getattr(self, k)) for k in self._KEYS}
+        out["numpy_scalars"] = [k for k in self._SCALARS if isinstance(getattr(self, k), np.floating)]
+        return out
+
+    @classmethod
+    def from_state(cls, state: dict) -> "CurriculumConfig":
+        d = {k: (tuple(v) if isinstance(v, list) else v) for k, v in state.items() if k != "numpy_scalars"}
+        for k in state.get("numpy_scalars", ()):
+            d[k] = np.float64(d[k])
+        return cls(**d)
+
     # -- device row
     def to_native(self):
         from ._native import Curriculum
@@ -361,6 +381,38 @@ class CurriculumScheduler:
         self._n_success = 0
         self.progression_history: List[Dict] = []
 
+    # -- checkpoints: everything a resumed run needs, as JSON-able data
+    def get_state(self) -> Dict[str, Any]:
+        return {
+            "class": type(self).__name__,
+            "init": {"initial_config": self.initial_config.to_state(), "target_config": self.target_config.to_state(),
+                     "success_rate_threshold": float(self.success_rate_threshold),
+                     "min_episodes_before_progression": int(self.min_episodes_before_progression),
+                     "window_size": int(self.window_size), "progression_steps": int(self.progression_steps),
+                     "history": self.history},
+            "current_difficulty_level": float(self.current_difficulty_level),
+            "episode_successes": [bool(x) for x in self.episode_successes],
+            "episode_steps": [int(x) for x in self.episode_steps],
+            "total_steps": int(self.total_steps), "total_episodes": int(self.total_episodes),
+            "n_success": int(self._n_success),
+            "progression_history": [dict(e) for e in self.progression_history],
+        }
+
+    def set_state(self, state: Dict[str, Any]):
+        """Restore ``get_state()``'s data into a scheduler built with the same constructor
+        arguments (``scheduler_from_state`` builds one).  The current config is re-derived from
+        the level exactly as ``_progress`` derived it (numpy scalars included)."""
+        if state.get("class") != type(self).__name__:
+            raise ValueError(f"state of a {state.get('class')}, not of a {type(self).__name__}")
+        self.current_difficulty_level = float(state["current_difficulty_level"])
+        self.current_config = (self._interpolate_config(self.current_difficulty_level)
+                               if self.current_difficulty_level > 0.0 else self._copy_config(self.initial_config))
+        self.episode_successes = [bool(x) for x in state["episode_successes"]]
+        self.episode_steps = [int(x) for x in state["episode_steps"]]
+        self.total_steps, self.total_episodes = int(state["total_steps"]), int(state["total_episodes"])
+        self._n_success = int(state["n_success"])
+        self.progression_history = [dict(e) for e in state["progression_history"]]
+
 
 class StepBasedScheduler(CurriculumScheduler):
     """Progress at total-step milestones (curriculum_scheduler.py:276-335)."""
@@ -414,6 +466,16 @@ class StepBasedScheduler(CurriculumScheduler):
         self._trim()
         return progressed
 
+    def get_state(self) -> Dict[str, Any]:
+        state = super().get_state()
+        state["init"]["step_milestones"] = [int(m) for m in self.step_milestones]
+        state["current_milestone_idx"] = int(self.current_milestone_idx)
+        return state
+
+    def set_state(self, state: Dict[str, Any]):
+        super().set_state(state)
+        self.current_milestone_idx = int(state["current_milestone_idx"])
+
     def _progress(self, rate: Optional[float] = None) -> bool:
         if self.current_milestone_idx >= len(self.step_milestones):
             return False
@@ -426,6 +488,18 @@ class StepBasedScheduler(CurriculumScheduler):
 
 
 # ============================================================ ExperimentConfig tree
+def scheduler_from_state(state: Dict[str, Any]) -> CurriculumScheduler:
+    """A scheduler rebuilt from ``get_state()``: constructor arguments, then ``set_state``."""
+    kinds = {"CurriculumScheduler": CurriculumScheduler, "StepBasedScheduler": StepBasedScheduler}
+    if state.get("class") not in kinds:
+        raise ValueError(f"unknown scheduler class {state.get('class')!r} (have {sorted(kinds)})")
+    init = dict(state["init"])
+    a, b = CurriculumConfig.from_state(init.pop("initial_config")), CurriculumConfig.from_state(init.pop("target_config"))
+    sc = kinds[state["class"]](a, b, **init)
+    sc.set_state(state)
+    return sc
+
+
 class CurriculumLogger:
     """experiments/curriculum_logger.py:13-130: per-episode curriculum state and the
     scheduler's progression events, saved as JSON."""

@@ -1,0 +1,116 @@
+"""``python -m dexterous_rl_manipulation_amd.train``: one training run of the MLP actor-critic.
+
+  --config-name NAME   a workload of workloads.py (easy, default, hard_heldout, variable_noise)
+  --config FILE        an ExperimentConfig JSON: its training section gives the episode limit and the
+                       seed, its curriculum_scheduler section the attached CurriculumScheduler
+  --iterations N --out DIR [--resume CKPT] [--keep-best COL] [--converge COL W THR]
+
+Writes DIR/training_log.json (TrainingLog), DIR/best_policy.npz (MLPActorPolicy, when some
+iteration qualified as best) and DIR/checkpoint.npz (PGTrainer.load_checkpoint / --resume).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from typing import List, Optional
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    from .training_run import _SCORE_COLUMNS
+    from .workloads import WORKLOADS
+    p = argparse.ArgumentParser(prog="python -m dexterous_rl_manipulation_amd.train", description=__doc__,
+                                formatter_class=argparse.RawDescriptionHelpFormatter)
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--config-name", choices=sorted(WORKLOADS), default=None, help="workload name (default: easy)")
+    g.add_argument("--config", metavar="FILE", default=None, help="ExperimentConfig JSON")
+    p.add_argument("--iterations", type=int, required=True)
+    p.add_argument("--out", metavar="DIR", required=True)
+    p.add_argument("--resume", metavar="CKPT", default=None, help="continue the run of a checkpoint.npz")
+    p.add_argument("--keep-best", metavar="COL", default="mean_return", choices=list(_SCORE_COLUMNS) + ["none"])
+    p.add_argument("--min-episodes", type=int, default=1)
+    p.add_argument("--converge", nargs=3, metavar=("COL", "W", "THR"), default=None)
+    p.add_argument("--stop-on-converge", action="store_true")
+    p.add_argument("--poll-every", type=int, default=0)
+    p.add_argument("--envs", type=int, default=None, help="envs (default: the workload's, 4096 with --config)")
+    p.add_argument("--horizon", type=int, default=200)
+    p.add_argument("--max-steps", type=int, default=None, help="episode step limit (default: the env's)")
+    p.add_argument("--epochs", type=int, default=1)
+    p.add_argument("--minibatches", type=int, default=1)
+    p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--device", default=None)
+    a = p.parse_args(argv)
+    if a.iterations < 0:
+        p.error("--iterations must be >= 0")
+    if a.converge is not None:
+        col, w, thr = a.converge
+        if col not in _SCORE_COLUMNS:
+            p.error(f"--converge COL must be one of {list(_SCORE_COLUMNS)}")
+        try:
+            a.converge = (col, int(w), float(thr))
+        except ValueError:
+            p.error("--converge takes COL W THR with an integer W and a number THR")
+        if a.converge[1] < 1:
+            p.error("--converge W must be >= 1")
+    if a.stop_on_converge and (a.converge is None or a.poll_every < 1):
+        p.error("--stop-on-converge needs --converge and --poll-every >= 1")
+    if a.keep_best == "none":
+        a.keep_best = None
+    if a.config_name is None and a.config is None:
+        a.config_name = "easy"
+    return a
+
+
+def _build(a, fresh: bool):
+    """(env, trainer or None): the run's env, and with `fresh` its new trainer."""
+    from . import experiments, workloads
+    from .envs import VecEnv
+    from .experiments import CurriculumConfig
+    from .trainer import PGTrainer, TrainerConfig
+    kw = dict(horizon=a.horizon, epochs=a.epochs, minibatches=a.minibatches, max_steps=a.max_steps)
+    if a.config is None:
+        w = workloads.WORKLOADS[a.config_name]
+        if a.seed is not None:
+            kw["seed"] = a.seed
+        if fresh:
+            return workloads.build_pg_workload(a.config_name, a.device, envs=a.envs, **kw)
+        env = VecEnv(a.envs or w["envs"], curriculum_config=CurriculumConfig.named(w["curriculum"]),
+                     reward_type="dense", seed=workloads.ENV_SEED, device=a.device)
+        return env, None
+    ex = experiments.load_config(a.config)
+    sc = ex.curriculum_scheduler
+    seed = ex.training.seed if a.seed is None else a.seed
+    env = VecEnv(a.envs or 4096, curriculum_config=CurriculumConfig.named(sc.initial_difficulty),
+                 reward_type=ex.training.reward_type, max_episode_steps=ex.training.max_episode_steps, seed=seed,
+                 device=a.device)
+    if not fresh:
+        return env, None
+    tr = PGTrainer(env, TrainerConfig(seed=seed, **kw))
+    tr.attach_curriculum(experiments.CurriculumScheduler(
+        CurriculumConfig.named(sc.initial_difficulty), CurriculumConfig.named(sc.target_difficulty),
+        sc.success_rate_threshold, sc.min_episodes_before_progression, sc.window_size, sc.progression_steps,
+        history="window"))
+    env.reset(write_obs=False)
+    return env, tr
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    a = parse_args(argv)
+    from .trainer import PGTrainer
+    os.makedirs(a.out, exist_ok=True)
+    env, tr = _build(a, fresh=a.resume is None)
+    if a.resume is not None:
+        tr = PGTrainer.load_checkpoint(a.resume, env)
+    log = tr.fit(a.iterations, keep_best=a.keep_best, min_episodes=a.min_episodes, converge=a.converge,
+                 stop_on_converge=a.stop_on_converge, poll_every=a.poll_every)
+    log.save(os.path.join(a.out, "training_log.json"))
+    if log.best_row is not None:
+        tr.best_policy().save(os.path.join(a.out, "best_policy.npz"))
+    tr.save_checkpoint(os.path.join(a.out, "checkpoint.npz"))
+    print(json.dumps(log.statistics()))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -777,6 +777,31 @@ class PGTrainer:
             self._join_comm()  # nothing of this iteration's exchanges stays in flight
         self.iteration_index += 1
 
+    # ------------------------------------------------------------------ training runs (training_run.py)
+    def fit(self, iterations: int, keep_best: Optional[str] = "mean_return", min_episodes: int = 1, converge=None,
+            stop_on_converge: bool = False, poll_every: int = 0):
+        """`iterations` x (iteration() + one device log row); returns the run's TrainingLog."""
+        from . import training_run
+        return training_run.fit(self, iterations, keep_best=keep_best, min_episodes=min_episodes, converge=converge,
+                                stop_on_converge=stop_on_converge, poll_every=poll_every)
+
+    def training_log(self):
+        from . import training_run
+        return training_run.training_log(self)
+
+    def best_policy(self, deterministic: bool = True, seed: Optional[int] = None):
+        from . import training_run
+        return training_run.best_policy(self, deterministic=deterministic, seed=seed)
+
+    def save_checkpoint(self, path):
+        from . import training_run
+        training_run.save_checkpoint(self, path)
+
+    @classmethod
+    def load_checkpoint(cls, path, env: VecEnv) -> "PGTrainer":
+        from . import training_run
+        return training_run.load_checkpoint(cls, path, env)
+
     # ------------------------------------------------------------------ stats
     def episode_stats(self) -> Dict[str, float]:
         cnt = int(self.ep_count.sum().item())

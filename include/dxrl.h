@@ -1020,6 +1020,129 @@ typedef struct dxrl_study_summary_args {
 
 int dxrl_study_summarize(int32_t device, const dxrl_study_summary_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Per-iteration training log (csrc/dxrl_pg_log.hip).  One call per policy-gradient
+ * iteration, enqueued behind the optimiser step: it reads what the iteration left on the
+ * device and writes row `row` of the f64 table log[cap][DXRL_PG_LOG_COLS]; nothing returns
+ * to the host.  Samples are time-major, m = t * num_envs + i, M = num_envs * horizon.
+ *
+ * Columns (enum dxrl_pg_log_col):
+ *   iteration, env_steps       the host scalars
+ *   episodes                   sum of ep_count
+ *   mean_return, mean_length,  sums of ep_sum_return / ep_sum_length / ep_successes over
+ *   success_rate               episodes (NaN when episodes == 0)
+ *   mean_step_reward           mean of rew
+ *   done_fraction              mean of done (count of non-zero bytes / M)
+ *   value_mean                 mean of values[m], m < M (the bootstrap slot values[M ..] is
+ *                              never read)
+ *   target_mean, target_var    population mean and variance of ret
+ *   residual_var               population variance of (double)ret[m] - (double)values[m]
+ *   explained_variance         1 - residual_var / target_var (NaN when target_var == 0)
+ *   adv_mean, adv_std          stats[2], stats[4] (dxrl_pg_gae / dxrl_pg_adv_combine)
+ *   policy_loss, value_mse,    the four columns of loss_partial summed over loss_blocks,
+ *   clip_frac, approx_kl       divided by loss_rows
+ *   grad_norm                  sqrt(gnorm2[0])
+ *   is_best, window_mean       below
+ * Columns from DXRL_PG_LOG_NAMED up to DXRL_PG_LOG_COLS are written as 0.
+ *
+ * Sums are f64; variances come from (count, mean, M2) triples merged with Chan's update in
+ * a fixed order (workgroup partials in `partial`, then one finishing workgroup): no
+ * floating-point atomics, and the same inputs give the same bytes on every call.
+ *
+ * Header (dxrl_pg_log_header, device memory, initialised by the caller to rows_written 0,
+ * best_row -1, converged_row -1, best_score -inf):
+ *   keep-best (score_col >= 0): is_best = 1 iff episodes >= min_episodes and
+ *     log[row][score_col] > best_score (strict: the first maximum wins, a NaN is never best);
+ *     best_score / best_row are then updated, and a second launch copies params to
+ *     best_params (num_params f32) iff is_best -- the flag is read on the device.
+ *   convergence (conv_col >= 0): window_mean = mean of log[row - W + 1 .. row][conv_col],
+ *     summed oldest first (NaN while row < W - 1); converged_row = the first row whose
+ *     window_mean > conv_threshold (strict; a NaN in the window does not converge).
+ *   rows_written = row + 1.
+ * score_col / conv_col must be < DXRL_PG_LOG_IS_BEST (or < 0: off; is_best 0 / window_mean
+ * NaN).  DXRL_E_INVALID before any launch: null args or required pointer, num_envs or
+ * horizon < 1, row outside [0, cap), a column index out of range, conv_col >= 0 with
+ * conv_window < 1, loss_blocks < 0, loss_rows < 1, partial_doubles smaller than
+ * dxrl_pg_log_partial_doubles(num_envs, horizon), score_col >= 0 with params but no
+ * best_params (both null: no copy).
+ * ------------------------------------------------------------------------ */
+#define DXRL_PG_LOG_COLS 24
+enum dxrl_pg_log_col {
+    DXRL_PG_LOG_ITERATION = 0,
+    DXRL_PG_LOG_ENV_STEPS,
+    DXRL_PG_LOG_EPISODES,
+    DXRL_PG_LOG_MEAN_RETURN,
+    DXRL_PG_LOG_MEAN_LENGTH,
+    DXRL_PG_LOG_SUCCESS_RATE,
+    DXRL_PG_LOG_MEAN_STEP_REWARD,
+    DXRL_PG_LOG_DONE_FRACTION,
+    DXRL_PG_LOG_VALUE_MEAN,
+    DXRL_PG_LOG_TARGET_MEAN,
+    DXRL_PG_LOG_TARGET_VAR,
+    DXRL_PG_LOG_RESIDUAL_VAR,
+    DXRL_PG_LOG_EXPLAINED_VARIANCE,
+    DXRL_PG_LOG_ADV_MEAN,
+    DXRL_PG_LOG_ADV_STD,
+    DXRL_PG_LOG_POLICY_LOSS,
+    DXRL_PG_LOG_VALUE_MSE,
+    DXRL_PG_LOG_CLIP_FRAC,
+    DXRL_PG_LOG_APPROX_KL,
+    DXRL_PG_LOG_GRAD_NORM,
+    DXRL_PG_LOG_IS_BEST,
+    DXRL_PG_LOG_WINDOW_MEAN,
+    DXRL_PG_LOG_NAMED /* 22 named columns, padded to DXRL_PG_LOG_COLS (a multiple of 4) */
+};
+
+typedef struct dxrl_pg_log_header {
+    int64_t rows_written;
+    int64_t best_row;      /* -1: none yet */
+    int64_t converged_row; /* -1: not converged */
+    int64_t reserved;
+    double best_score;     /* -inf: none yet */
+    double reserved_f64[3];
+} dxrl_pg_log_header;
+
+typedef struct dxrl_pg_log_args {
+    int64_t num_envs;                /* N                                                    */
+    int64_t horizon;                 /* T                                                    */
+    int64_t row;                     /* table row this call writes, 0 <= row < cap           */
+    int64_t cap;                     /* rows of the table                                    */
+    int64_t iteration;               /* column 0                                             */
+    int64_t env_steps;               /* column 1 (cumulative)                                */
+    int64_t loss_blocks;             /* rows of loss_partial                                 */
+    int64_t loss_rows;               /* samples of the last train pass                       */
+    int64_t min_episodes;            /* keep-best gate                                       */
+    int64_t num_params;              /* f32 elements of params / best_params                 */
+    int64_t partial_doubles;         /* f64 elements of partial                              */
+    int32_t score_col;               /* keep-best column, < 0: off                           */
+    int32_t conv_col;                /* convergence column, < 0: off                         */
+    int32_t conv_window;             /* W >= 1                                               */
+    int32_t reserved;
+    double conv_threshold;
+    /* device inputs */
+    const int32_t* ep_count;         /* i32 [N]                                              */
+    const double*  ep_sum_return;    /* f64 [N]                                              */
+    const int32_t* ep_sum_length;    /* i32 [N]                                              */
+    const int32_t* ep_successes;     /* i32 [N]                                              */
+    const float*   rew;              /* f32 [M]                                              */
+    const float*   ret;              /* f32 [M]                                              */
+    const uint8_t* done;             /* u8  [M]                                              */
+    const float*   values;           /* f32 [(T + 1) N]; only [0, M) is read                 */
+    const double*  stats;            /* f64 [8] (dxrl_pg_gae)                                */
+    const double*  loss_partial;     /* f64 [loss_blocks][4]                                 */
+    const double*  gnorm2;           /* f64 [1]                                              */
+    const float*   params;           /* f32 [num_params] (nullable with best_params)         */
+    /* device scratch and outputs */
+    double* partial;                 /* f64 [partial_doubles] scratch                        */
+    float*  best_params;             /* f32 [num_params] (nullable with params)              */
+    double* log;                     /* f64 [cap][DXRL_PG_LOG_COLS]                          */
+    dxrl_pg_log_header* header;
+} dxrl_pg_log_args;
+
+/* f64 elements of dxrl_pg_log_row's `partial` scratch for num_envs x horizon samples. */
+int dxrl_pg_log_partial_doubles(int64_t num_envs, int64_t horizon, int64_t* out);
+int dxrl_pg_log_row(int32_t device, const dxrl_pg_log_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

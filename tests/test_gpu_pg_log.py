@@ -1,0 +1,255 @@
+"""GPU: dxrl_pg_log_row (csrc/dxrl_pg_log.hip) on uploaded arrays, without a trainer, against the
+NumPy restatement (tests/pg_log_reference.py).
+
+Bounds.  Integer-derived columns are exact.  An f64 sum of k terms differs from the reference's
+sum by at most k 2^-52 sum|x| in any summation order (each of the k - 1 additions rounds a partial
+sum that is at most sum|x| by at most 2^-53 relative; both sides do so); means carry that bound
+divided by the count.  Variances and explained_variance: 1e-9 relative to the two-pass values
+(the figure for Chan-merged moments against two-pass), on inputs with
+|mean| / std <= 10 so the two-pass reference is itself well conditioned."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import pg_log_reference as L
+
+pytestmark = pytest.mark.gpu
+
+FILL = 7.25       # table fill value: rows the call must not touch keep it
+PAD = 40          # elements past every buffer's logical end
+SHAPES = [(16, 2), (48, 3), (1040, 33)]
+EPS = 2.0 ** -52
+
+
+@pytest.fixture(scope="module")
+def N():
+    from dexterous_rl_manipulation_amd import _native
+    _native.lib()
+    return _native
+
+
+def inputs(n, T, seed=0):
+    """Host arrays of one iteration (logical sizes).  ret: mean 5, std 1; values = ret + noise."""
+    rng = np.random.default_rng(seed)
+    M = n * T
+    ret = (5.0 + rng.standard_normal(M)).astype(np.float32)
+    values = np.concatenate([ret + 0.5 * rng.standard_normal(M).astype(np.float32),
+                             rng.standard_normal(n).astype(np.float32)]).astype(np.float32)
+    blocks = 5
+    return dict(n=n, T=T, ep_count=rng.integers(0, 4, n).astype(np.int32), ep_sum_return=rng.standard_normal(n) * 3,
+                ep_sum_length=rng.integers(0, 90, n).astype(np.int32), ep_successes=rng.integers(0, 3, n).astype(np.int32),
+                rew=rng.standard_normal(M).astype(np.float32), ret=ret, done=(rng.random(M) < 0.1).astype(np.uint8) * 3,
+                values=values, stats=rng.standard_normal(8), loss_partial=rng.standard_normal((blocks, 4)),
+                loss_rows=M // 2, gnorm2=2.75)
+
+
+class Harness:
+    """Device copies of `inputs` with PAD extra elements after each logical end, a table of `cap`
+    rows filled with FILL, a fresh header, and the call."""
+
+    def __init__(self, N, data, cap=4, pad="nan", offset=0, num_params=0):
+        self.N, self.data, self.cap = N, data, cap
+        dev = torch.device("cuda:0")
+        n, T = data["n"], data["T"]
+
+        def up(a, poison):
+            a = np.asarray(a)
+            tail = np.zeros(PAD, dtype=a.dtype)
+            if pad == "nan":
+                tail[:] = poison
+            # `offset` leading elements shift the data pointer off 16-byte alignment
+            full = np.concatenate([np.zeros(offset, dtype=a.dtype), a.ravel(), tail])
+            return torch.from_numpy(full).to(dev)[offset:]
+
+        self.t = {k: up(data[k], p) for k, p in (("ep_count", 10 ** 6), ("ep_sum_return", np.nan),
+                                                  ("ep_sum_length", 10 ** 6), ("ep_successes", 10 ** 6),
+                                                  ("rew", np.nan), ("ret", np.nan), ("done", 255),
+                                                  ("stats", np.nan), ("loss_partial", np.nan))}
+        v = np.array(data["values"], dtype=np.float32)
+        if pad == "nan":
+            v[n * T:] = 1e30  # the bootstrap slot: a huge sentinel that must never be read
+        self.t["values"] = up(v, np.nan)
+        self.t["gnorm2"] = torch.tensor([data["gnorm2"]], dtype=torch.float64, device=dev)
+        self.table = torch.full((cap, L.COLS), FILL, dtype=torch.float64, device=dev)
+        self.header = torch.zeros(64, dtype=torch.uint8, device=dev)
+        self.header[8:24].view(torch.int64).fill_(-1)
+        self.header[32:40].view(torch.float64).fill_(-math.inf)
+        nb = C.c_int64()
+        N.call("dxrl_pg_log_partial_doubles", n, T, C.byref(nb))
+        self.partial = torch.full((nb.value,), float("nan"), dtype=torch.float64, device=dev)
+        self.params = self.best = None
+        if num_params:
+            self.params = torch.zeros(num_params + 1, device=dev)[1:]      # 4-byte aligned only
+            self.best = torch.full((num_params + 1,), -1.0, device=dev)[1:]
+
+    def args(self, row, iteration=3, env_steps=1234567, score_col=-1, min_episodes=1, conv_col=-1, window=1,
+             threshold=0.0):
+        N, d, p = self.N, self.data, self.N.ptr
+        a = N.PgLogArgs()
+        a.num_envs, a.horizon, a.row, a.cap, a.iteration, a.env_steps = d["n"], d["T"], row, self.cap, iteration, env_steps
+        a.loss_blocks, a.loss_rows, a.min_episodes = np.asarray(d["loss_partial"]).shape[0], d["loss_rows"], min_episodes
+        a.partial_doubles = self.partial.numel()
+        a.score_col, a.conv_col, a.conv_window, a.conv_threshold = score_col, conv_col, window, threshold
+        for k in ("ep_count", "ep_sum_return", "ep_sum_length", "ep_successes", "rew", "ret", "done", "values", "stats",
+                  "loss_partial", "gnorm2"):
+            setattr(a, k, p(self.t[k]))
+        a.partial, a.log, a.header = p(self.partial), p(self.table), p(self.header)
+        if self.params is not None:
+            a.num_params, a.params, a.best_params = self.params.numel(), p(self.params), p(self.best)
+        return a
+
+    def call(self, row, **kw):
+        a = self.args(row, **kw)
+        self.N.call("dxrl_pg_log_row", 0, C.byref(a), self.N.stream_of(torch.device("cuda:0")))
+        torch.cuda.synchronize()
+        return self.table.cpu().numpy()
+
+    def head(self):
+        from dexterous_rl_manipulation_amd.training_run import header_dict
+        return header_dict(self.header.cpu().numpy())
+
+
+def sum_bound(x):
+    x = np.asarray(x, dtype=np.float64)
+    return x.size * EPS * float(np.abs(x).sum())
+
+
+@pytest.mark.parametrize("n,T", SHAPES)
+def test_row_against_the_restatement(N, n, T):
+    d = inputs(n, T, seed=n)
+    M = n * T
+    h = Harness(N, d)
+    table = h.call(2, iteration=3, env_steps=1234567)
+    got = {name: table[2, k] for k, name in enumerate(L.COLUMNS)}
+    ref = L.row_values(n, T, 3, 1234567, d["ep_count"], d["ep_sum_return"], d["ep_sum_length"], d["ep_successes"],
+                       d["rew"], d["ret"], d["done"], d["values"], d["stats"], d["loss_partial"], d["loss_rows"],
+                       d["gnorm2"])
+    for name in ("iteration", "env_steps", "episodes", "mean_length", "success_rate", "done_fraction", "adv_mean",
+                 "adv_std"):
+        assert got[name] == ref[name], name
+    eps_n = ref["episodes"]
+    val = np.asarray(d["values"], dtype=np.float64)[:M]
+    for name, terms, count in (("mean_return", d["ep_sum_return"], eps_n), ("mean_step_reward", d["rew"], M),
+                               ("value_mean", val, M), ("target_mean", d["ret"], M)):
+        print(name, got[name], ref[name], abs(got[name] - ref[name]), sum_bound(terms) / count)
+        assert abs(got[name] - ref[name]) <= sum_bound(terms) / count, name
+    loss = np.asarray(d["loss_partial"])
+    for k, name in enumerate(("policy_loss", "value_mse", "clip_frac", "approx_kl")):
+        assert abs(got[name] - ref[name]) <= sum_bound(loss[:, k]) / d["loss_rows"], name
+    assert abs(got["grad_norm"] - ref["grad_norm"]) <= EPS * ref["grad_norm"]  # one rounding of sqrt
+    for name in ("target_var", "residual_var", "explained_variance"):
+        print(name, got[name], ref[name], abs(got[name] / ref[name] - 1.0))
+        assert abs(got[name] - ref[name]) <= 1e-9 * abs(ref[name]), name
+    assert got["is_best"] == 0.0 and math.isnan(got["window_mean"])  # both rules off
+    assert np.all(table[2, len(L.COLUMNS):] == 0.0)                   # padding columns
+    assert np.all(table[[0, 1, 3]] == FILL)                           # other rows untouched
+    assert h.head() == {"rows_written": 3, "best_row": -1, "converged_row": -1, "best_score": -math.inf}
+    # a second call: identical bytes
+    assert h.call(2).tobytes() == table.tobytes()
+    # nothing past a logical end is read: zero padding and a clean bootstrap slot give the same bytes
+    clean = Harness(N, d, pad="zero").call(2)
+    assert clean.tobytes() == table.tobytes()
+    # pointers off 16-byte alignment take the scalar loads: same samples, same order, same bytes
+    assert Harness(N, d, offset=1).call(2).tobytes() == table.tobytes()
+
+
+def test_zero_episodes_and_constant_targets_give_nan(N):
+    d = inputs(48, 3, seed=1)
+    d["ep_count"] = np.zeros(48, dtype=np.int32)
+    d["ret"] = np.full(144, 2.5, dtype=np.float32)
+    row = Harness(N, d).call(0, score_col=L.IDX["mean_return"], conv_col=L.IDX["mean_return"], window=1)[0]
+    g = {name: row[k] for k, name in enumerate(L.COLUMNS)}
+    assert g["episodes"] == 0.0
+    assert all(math.isnan(g[k]) for k in ("mean_return", "mean_length", "success_rate"))
+    assert g["target_var"] == 0.0 and g["target_mean"] == 2.5 and math.isnan(g["explained_variance"])
+    assert g["residual_var"] > 0.0
+    assert g["is_best"] == 0.0 and math.isnan(g["window_mean"])  # a NaN score is never best, never converges
+
+
+def scripted(N, scores, episodes, rewards, num_params=0):
+    """A harness whose row r scores scores[r] (mean_return) over episodes[r] episodes, with
+    mean_step_reward rewards[r]; `play(r, **rules)` uploads row r's inputs and makes the call."""
+    n, T = 16, 2
+    d = inputs(n, T, seed=9)
+    h = Harness(N, d, cap=len(scores), num_params=num_params)
+
+    def play(r, **rules):
+        cnt = np.zeros(n, dtype=np.int32)
+        cnt[3] = episodes[r]
+        ret = np.zeros(n)
+        ret[3] = scores[r] * episodes[r] if episodes[r] else 0.0  # small integers: the quotient is exact
+        h.t["ep_count"][:n].copy_(torch.from_numpy(cnt))
+        h.t["ep_sum_return"][:n].copy_(torch.from_numpy(ret))
+        h.t["rew"][:n * T].fill_(float(rewards[r]))
+        if h.params is not None:
+            h.params.fill_(float(r + 1))  # the tag of row r
+        return h.call(r, **rules)
+    return h, play
+
+
+def test_keep_best_copies_exactly_the_expected_rows(N):
+    nan = float("nan")
+    scores = [1.0, 3.0, 3.0, nan, 9.0, 4.0, 2.0]   # a tie (row 2), a NaN (row 3)
+    episodes = [4, 4, 4, 4, 1, 4, 4]               # row 4 is below min_episodes = 2
+    want_rows, want_header, want_table = L.series_rules(scores, episodes, 2, [0.0] * 7, 1, 1e9)
+    assert want_rows == [0, 1, 5]
+    h, play = scripted(N, scores, episodes, [0.0] * 7, num_params=1031)
+    tag = -1.0
+    for r in range(len(scores)):
+        table = play(r, score_col=L.IDX["mean_return"], min_episodes=2)
+        if r in want_rows:
+            tag = float(r + 1)
+        assert table[r, L.IS_BEST] == want_table[r, L.IS_BEST], r
+        assert torch.all(h.best == tag), r  # the tagged params of exactly the expected row, else untouched
+        head = h.head()
+        assert head["best_row"] == (max(x for x in want_rows if x <= r))
+    assert h.head() == want_header
+    # score_col < 0: no flag, no copy, header's best untouched
+    h.params.fill_(99.0)
+    table = h.call(6)
+    assert table[6, L.IS_BEST] == 0.0 and torch.all(h.best == tag) and h.head()["best_row"] == 5
+
+
+def test_convergence_is_strict_and_sticks(N):
+    vals = [1.0, 1.0, 3.0, 2.0, -1.0, 7.0]  # window-2 means: -, 1, 2 (== threshold), 2.5, 0.5, 3
+    _, want_header, want_table = L.series_rules([0.0] * 6, [1] * 6, 1, vals, 2, 2.0)
+    assert want_header["converged_row"] == 3
+    h, play = scripted(N, [0.0] * 6, [1] * 6, vals)
+    col = L.IDX["mean_step_reward"]
+    for r in range(6):
+        table = play(r, conv_col=col, window=2, threshold=2.0)
+        assert table[r, col] == vals[r]
+        want = want_table[r, L.IDX["window_mean"]]
+        got = table[r, L.IDX["window_mean"]]
+        assert (math.isnan(got) and math.isnan(want)) or got == want, r
+        assert h.head()["converged_row"] == (3 if r >= 3 else -1), r  # not at the tie, and the first one sticks
+
+
+def test_argument_errors_leave_the_table_unwritten(N):
+    d = inputs(16, 2)
+    h = Harness(N, d, num_params=8)
+    stream = N.stream_of(torch.device("cuda:0"))
+    with pytest.raises(ValueError, match="null args"):
+        N.call("dxrl_pg_log_row", 0, None, stream)
+    cases = [("row", 4, "outside the table"), ("row", -1, "outside the table"), ("cap", 0, "outside the table"),
+             ("num_envs", 0, "num_envs"), ("horizon", 0, "horizon"),
+             ("score_col", L.IS_BEST, "score_col"), ("score_col", L.COLS, "score_col"),
+             ("conv_col", L.IS_BEST, "conv_col"), ("conv_col", 99, "conv_col"), ("conv_window", 0, "conv_window"),
+             ("loss_rows", 0, "loss_rows"), ("loss_blocks", -1, "loss_blocks"), ("partial_doubles", 1, "partial holds"),
+             ("best_params", None, "keep-best"), ("num_params", 0, "keep-best")]
+    cases += [(k, None, "null") for k in ("ep_count", "ep_sum_return", "ep_sum_length", "ep_successes", "rew", "ret",
+                                          "done", "values", "stats", "loss_partial", "gnorm2", "partial", "log",
+                                          "header")]
+    for field, value, msg in cases:
+        a = h.args(1, score_col=L.IDX["mean_return"], conv_col=L.IDX["mean_return"], window=2)
+        setattr(a, field, value)
+        with pytest.raises(ValueError, match=msg):
+            N.call("dxrl_pg_log_row", 0, C.byref(a), stream)
+    torch.cuda.synchronize()
+    assert torch.all(h.table == FILL) and torch.all(h.best == -1.0)
+    assert h.head() == L.new_header()
+    with pytest.raises(ValueError):
+        N.call("dxrl_pg_log_partial_doubles", 0, 2, C.byref(C.c_int64()))
