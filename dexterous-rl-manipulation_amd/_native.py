@@ -233,6 +233,34 @@ class PgLogArgs(C.Structure):
                                           "best_params", "log", "header")]
 
 
+# enum dxrl_pg_val_col: the named columns of the validation table, in table order
+PG_VAL_COLUMNS = ("iteration", "env_steps", "train_row", "episodes", "successes", "success_rate", "mean_return",
+                  "return_std", "mean_length", "mean_success_length", "mean_contacts", "min_object_success_rate",
+                  "objects_solved", "eval_status", "is_best", "since_best")
+PG_VAL_NAMED = len(PG_VAL_COLUMNS)  # DXRL_PG_VAL_NAMED
+PG_VAL_COLS = 16                    # DXRL_PG_VAL_COLS
+PG_VAL_IS_BEST = PG_VAL_COLUMNS.index("is_best")
+
+
+class PgValHeader(C.Structure):
+    _fields_ = [("rows_written", C.c_int64), ("best_row", C.c_int64), ("stopped_row", C.c_int64),
+                ("since_best", C.c_int64), ("best_score", C.c_double), ("reserved_f64", C.c_double * 3)]
+
+
+class PgValArgs(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("num_objects", "episodes_per_object", "row", "cap", "iteration", "env_steps",
+                                         "train_row", "num_params", "partial_doubles")] + \
+               [("score_col", C.c_int32), ("patience", C.c_int32), ("min_delta", C.c_double),
+                ("solve_threshold", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("ep_return", "ep_length", "ep_success", "ep_contacts", "status", "params",
+                                          "partial", "best_params", "val", "object_successes", "header")]
+
+
+# the structs added after tests/test_native_abi.py fixed its list: (C name, mirror), sized against
+# include/dxrl.h by the tests of the layers that use them
+LATER_STRUCTS = (("dxrl_pg_log_args", PgLogArgs), ("dxrl_pg_log_header", PgLogHeader),
+                 ("dxrl_pg_val_args", PgValArgs), ("dxrl_pg_val_header", PgValHeader))
+
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
 _SIGS = {
@@ -288,6 +316,8 @@ _SIGS = {
     "dxrl_study_summarize": (C.c_int, [_I32, C.POINTER(StudySummaryArgs), _P]),
     "dxrl_pg_log_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_log_row": (C.c_int, [_I32, C.POINTER(PgLogArgs), _P]),
+    "dxrl_pg_val_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
+    "dxrl_pg_val_row": (C.c_int, [_I32, C.POINTER(PgValArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

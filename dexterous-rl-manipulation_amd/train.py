@@ -4,9 +4,13 @@
   --config FILE        an ExperimentConfig JSON: its training section gives the episode limit and the
                        seed, its curriculum_scheduler section the attached CurriculumScheduler
   --iterations N --out DIR [--resume CKPT] [--keep-best COL] [--converge COL W THR]
+  --validate-every K   validate on HeldOutObjectSet(<the run's curriculum config>) after every K-th
+                       iteration: [--val-episodes E] per object, [--val-seed S], [--val-keep-best COL],
+                       [--patience P] (with --poll-every: stop after P validations without a new best)
 
-Writes DIR/training_log.json (TrainingLog), DIR/best_policy.npz (MLPActorPolicy, when some
-iteration qualified as best) and DIR/checkpoint.npz (PGTrainer.load_checkpoint / --resume).
+Writes DIR/training_log.json (TrainingLog, with the validation curve), DIR/best_policy.npz
+(MLPActorPolicy, when some iteration qualified as best), DIR/best_val_policy.npz (the actor of the
+best validation) and DIR/checkpoint.npz (PGTrainer.load_checkpoint / --resume).
 """
 from __future__ import annotations
 
@@ -18,7 +22,7 @@ from typing import List, Optional
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
-    from .training_run import _SCORE_COLUMNS
+    from .training_run import _SCORE_COLUMNS, _VAL_SCORE_COLUMNS
     from .workloads import WORKLOADS
     p = argparse.ArgumentParser(prog="python -m dexterous_rl_manipulation_amd.train", description=__doc__,
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -33,6 +37,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--converge", nargs=3, metavar=("COL", "W", "THR"), default=None)
     p.add_argument("--stop-on-converge", action="store_true")
     p.add_argument("--poll-every", type=int, default=0)
+    p.add_argument("--validate-every", type=int, default=0, metavar="K", help="0: no validation")
+    p.add_argument("--val-episodes", type=int, default=5, metavar="E", help="episodes per held-out object")
+    p.add_argument("--val-seed", type=int, default=0, metavar="S")
+    p.add_argument("--val-keep-best", metavar="COL", default="success_rate",
+                   choices=list(_VAL_SCORE_COLUMNS) + ["none"])
+    p.add_argument("--patience", type=int, default=0, metavar="P")
     p.add_argument("--envs", type=int, default=None, help="envs (default: the workload's, 4096 with --config)")
     p.add_argument("--horizon", type=int, default=200)
     p.add_argument("--max-steps", type=int, default=None, help="episode step limit (default: the env's)")
@@ -57,6 +67,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--stop-on-converge needs --converge and --poll-every >= 1")
     if a.keep_best == "none":
         a.keep_best = None
+    if a.validate_every < 0 or a.val_episodes < 1 or a.patience < 0:
+        p.error("--validate-every and --patience must be >= 0 and --val-episodes >= 1")
+    if a.patience and not a.validate_every:
+        p.error("--patience needs --validate-every")
+    if a.val_keep_best == "none":
+        a.val_keep_best = None
     if a.config_name is None and a.config is None:
         a.config_name = "easy"
     return a
@@ -100,13 +116,23 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .trainer import PGTrainer
     os.makedirs(a.out, exist_ok=True)
     env, tr = _build(a, fresh=a.resume is None)
+    base_config = env.curriculum_configs[0]  # the run's curriculum config, the same on a resume
     if a.resume is not None:
         tr = PGTrainer.load_checkpoint(a.resume, env)
+    kw = {}
+    if a.validate_every:
+        from .evaluation import HeldOutObjectSet
+        plan = tr.validation_plan(HeldOutObjectSet(base_config), episodes_per_object=a.val_episodes,
+                                  seed=a.val_seed, max_steps=a.max_steps)
+        kw = dict(validation=plan, validate_every=a.validate_every, val_keep_best=a.val_keep_best,
+                  patience=a.patience, stop_on_patience=bool(a.patience and a.poll_every))
     log = tr.fit(a.iterations, keep_best=a.keep_best, min_episodes=a.min_episodes, converge=a.converge,
-                 stop_on_converge=a.stop_on_converge, poll_every=a.poll_every)
+                 stop_on_converge=a.stop_on_converge, poll_every=a.poll_every, **kw)
     log.save(os.path.join(a.out, "training_log.json"))
     if log.best_row is not None:
         tr.best_policy().save(os.path.join(a.out, "best_policy.npz"))
+    if log.validation is not None and log.validation.best_row is not None:
+        tr.best_policy(which="validation").save(os.path.join(a.out, "best_val_policy.npz"))
     tr.save_checkpoint(os.path.join(a.out, "checkpoint.npz"))
     print(json.dumps(log.statistics()))
     return 0

@@ -779,19 +779,31 @@ class PGTrainer:
 
     # ------------------------------------------------------------------ training runs (training_run.py)
     def fit(self, iterations: int, keep_best: Optional[str] = "mean_return", min_episodes: int = 1, converge=None,
-            stop_on_converge: bool = False, poll_every: int = 0):
-        """`iterations` x (iteration() + one device log row); returns the run's TrainingLog."""
+            stop_on_converge: bool = False, poll_every: int = 0, validation=None, validate_every: int = 1,
+            val_keep_best: Optional[str] = "success_rate", min_delta: float = 0.0, patience: int = 0,
+            stop_on_patience: bool = False):
+        """`iterations` x (iteration() + one device log row), with `validation` (a validation_plan)
+        a held-out validation row every validate_every iterations; returns the run's TrainingLog."""
         from . import training_run
         return training_run.fit(self, iterations, keep_best=keep_best, min_episodes=min_episodes, converge=converge,
-                                stop_on_converge=stop_on_converge, poll_every=poll_every)
+                                stop_on_converge=stop_on_converge, poll_every=poll_every, validation=validation,
+                                validate_every=validate_every, val_keep_best=val_keep_best, min_delta=min_delta,
+                                patience=patience, stop_on_patience=stop_on_patience)
+
+    def validation_plan(self, heldout_set, episodes_per_object: int = 5, seed: int = 0, device_seed: int = 0,
+                        max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0):
+        """A held-out evaluation of this trainer's live actor, built once for fit(validation=...)."""
+        from . import training_run
+        return training_run.ValidationPlan(self, heldout_set, episodes_per_object, seed, device_seed, max_steps,
+                                           deterministic, solve_threshold)
 
     def training_log(self):
         from . import training_run
         return training_run.training_log(self)
 
-    def best_policy(self, deterministic: bool = True, seed: Optional[int] = None):
+    def best_policy(self, deterministic: bool = True, seed: Optional[int] = None, which: str = "training"):
         from . import training_run
-        return training_run.best_policy(self, deterministic=deterministic, seed=seed)
+        return training_run.best_policy(self, deterministic=deterministic, seed=seed, which=which)
 
     def save_checkpoint(self, path):
         from . import training_run

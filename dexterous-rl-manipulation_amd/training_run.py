@@ -12,6 +12,13 @@ A checkpoint is one ``.npz`` without pickle -- arrays plus one JSON string, in t
 master parameters, Adam moments, bf16 pack and counters, the running episode returns, the env
 slab (offsets only, nothing address-dependent), the curriculum table's configs, the trainer
 config, the log table / header / best parameters, and the attached scheduler.
+
+``fit(validation=plan)`` adds held-out validation: a ``ValidationPlan`` built once (the launch of
+``Evaluator.evaluate_heldout_set(parallel=True)`` with device Philox resets) runs the episode
+kernel on the trainer's live weights every ``validate_every`` iterations, and ``dxrl_pg_val_row``
+(csrc/dxrl_pg_val.hip) reduces its episode records to one row of a second device table with its
+own keep-best, best parameters and patience.  ``log.validation`` is the ``ValidationLog``; the
+checkpoint carries the validation tables and the plan's fingerprint as optional entries.
 """
 from __future__ import annotations
 
@@ -34,6 +41,11 @@ LOG_FORMAT = "dxrl-training-log-v1"
 _SCORE_COLUMNS = COLUMNS[:N.PG_LOG_IS_BEST]  # columns a score / convergence rule may read
 _HEADER_BYTES = C.sizeof(N.PgLogHeader)
 _MIN_CAP = 256
+VAL_COLUMNS = N.PG_VAL_COLUMNS
+VAL_COLS = N.PG_VAL_COLS
+_VAL_SCORE_COLUMNS = VAL_COLUMNS[:N.PG_VAL_IS_BEST]  # columns the validation keep-best may read
+_VAL_HEADER_BYTES = C.sizeof(N.PgValHeader)
+_MIN_VAL_CAP = 64
 
 
 def column_index(name: Optional[str], what: str) -> int:
@@ -55,12 +67,13 @@ class TrainingLog:
     threshold (reward_comparison.py:121-124), or None."""
 
     def __init__(self, table=None, header: Optional[Dict[str, Any]] = None, window: Optional[int] = None,
-                 settings: Optional[Dict[str, Any]] = None, _pending=None):
+                 settings: Optional[Dict[str, Any]] = None, _pending=None, validation: "Optional[ValidationLog]" = None):
         self._pending = _pending
         self._table = None if table is None else np.array(table, dtype=np.float64).reshape(-1, COLS)
         self._header = dict(header) if header is not None else None
         self.window = window
         self.settings = dict(settings or {})
+        self.validation = validation  # the held-out curve of fit(validation=plan), or None
 
     # -- lazy fill (fit enqueued the copy; the first read waits for it)
     def _resolve(self):
@@ -134,9 +147,12 @@ class TrainingLog:
 
     # -- JSON (NaN and the infinities as strings, so the file is standard JSON)
     def to_dict(self) -> Dict[str, Any]:
-        return {"format": LOG_FORMAT, "columns": list(COLUMNS), "window": self.window, "settings": self.settings,
-                "header": {k: _enc(v) for k, v in self.header.items()},
-                "rows": [[_enc(x) for x in row[:len(COLUMNS)]] for row in self.table.tolist()]}
+        out = {"format": LOG_FORMAT, "columns": list(COLUMNS), "window": self.window, "settings": self.settings,
+               "header": {k: _enc(v) for k, v in self.header.items()},
+               "rows": [[_enc(x) for x in row[:len(COLUMNS)]] for row in self.table.tolist()]}
+        if self.validation is not None:  # a log without validation serialises as it always did
+            out["validation"] = self.validation.to_dict()
+        return out
 
     @classmethod
     def from_dict(cls, d: Dict[str, Any]) -> "TrainingLog":
@@ -145,7 +161,9 @@ class TrainingLog:
         table = np.zeros((len(d["rows"]), COLS), dtype=np.float64)
         for r, row in enumerate(d["rows"]):
             table[r, :len(COLUMNS)] = [_dec(x) for x in row]
-        return cls(table, {k: _dec(v) for k, v in d["header"].items()}, d.get("window"), d.get("settings"))
+        val = ValidationLog.from_dict(d["validation"]) if d.get("validation") is not None else None
+        return cls(table, {k: _dec(v) for k, v in d["header"].items()}, d.get("window"), d.get("settings"),
+                   validation=val)
 
     def save(self, path):
         with open(path, "w") as f:
@@ -174,6 +192,293 @@ def header_dict(raw: np.ndarray) -> Dict[str, Any]:
     return {"rows_written": int(i[0]), "best_row": int(i[1]), "converged_row": int(i[2]), "best_score": float(f[0])}
 
 
+# ====================================================================== ValidationLog
+class ValidationLog:
+    """The held-out curve of a run: one row per validation (``log.validation["success_rate"]``,
+    ``.columns``), the per-object success counts of every row with the objects' names, and the
+    iteration keep-best chose / patience ran out at (None: none)."""
+
+    def __init__(self, table=None, header: Optional[Dict[str, Any]] = None, object_successes=None,
+                 object_names=(), settings: Optional[Dict[str, Any]] = None, _pending=None):
+        self._pending = _pending
+        self.object_names = list(object_names)
+        self._table = None if table is None else np.array(table, dtype=np.float64).reshape(-1, VAL_COLS)
+        self._header = dict(header) if header is not None else None
+        self._objects = None if object_successes is None else \
+            np.array(object_successes, dtype=np.int32).reshape(-1, len(self.object_names))
+        self.settings = dict(settings or {})
+
+    def _resolve(self):
+        if self._pending is not None:
+            event, host_table, host_header, host_objects, rows = self._pending
+            event.synchronize()
+            self._table = host_table[:rows].numpy().copy()
+            self._header = val_header_dict(host_header.numpy())
+            self._objects = host_objects[:rows].numpy().copy()
+            self._pending = None
+
+    @property
+    def table(self) -> np.ndarray:
+        self._resolve()
+        return self._table
+
+    @property
+    def header(self) -> Dict[str, Any]:
+        self._resolve()
+        return self._header
+
+    @property
+    def object_successes(self) -> np.ndarray:
+        """i32 [rows][objects]: successes of each object (out of episodes / objects per row)."""
+        self._resolve()
+        return self._objects
+
+    @property
+    def columns(self) -> Dict[str, np.ndarray]:
+        t = self.table
+        return {name: t[:, k] for k, name in enumerate(VAL_COLUMNS)}
+
+    def __getitem__(self, name: str) -> np.ndarray:
+        return self.table[:, VAL_COLUMNS.index(name)]
+
+    def __len__(self) -> int:
+        return self.table.shape[0]
+
+    def _row(self, key: str) -> Optional[int]:
+        r = int(self.header[key])
+        return r if r >= 0 else None
+
+    @property
+    def best_row(self) -> Optional[int]:
+        return self._row("best_row")
+
+    @property
+    def best_iteration(self) -> Optional[int]:
+        r = self.best_row
+        return None if r is None else int(self["iteration"][r])
+
+    @property
+    def stopped_row(self) -> Optional[int]:
+        return self._row("stopped_row")
+
+    @property
+    def stopped_iteration(self) -> Optional[int]:
+        r = self.stopped_row
+        return None if r is None else int(self["iteration"][r])
+
+    def statistics(self) -> Dict[str, Any]:
+        n = len(self)
+        out: Dict[str, Any] = {"validations": n, "best_iteration": self.best_iteration,
+                               "stopped_iteration": self.stopped_iteration,
+                               "best_score": float(self.header["best_score"]) if self.best_row is not None else None}
+        if n == 0:
+            return out
+        out["episodes_per_validation"] = int(self["episodes"][-1])
+        for name in ("success_rate", "mean_return", "mean_length", "min_object_success_rate", "objects_solved"):
+            col = self[name]
+            out[f"final_{name}"] = float(col[-1])
+            out[f"max_{name}"] = float(np.nanmax(col)) if not np.isnan(col).all() else float("nan")
+        return out
+
+    def to_dict(self) -> Dict[str, Any]:
+        return {"columns": list(VAL_COLUMNS), "settings": self.settings, "object_names": self.object_names,
+                "header": {k: _enc(v) for k, v in self.header.items()},
+                "rows": [[_enc(x) for x in row[:len(VAL_COLUMNS)]] for row in self.table.tolist()],
+                "object_successes": self.object_successes.tolist()}
+
+    @classmethod
+    def from_dict(cls, d: Dict[str, Any]) -> "ValidationLog":
+        if list(d.get("columns", [])) != list(VAL_COLUMNS):
+            raise ValueError("not a validation log with this build's columns")
+        table = np.zeros((len(d["rows"]), VAL_COLS), dtype=np.float64)
+        for r, row in enumerate(d["rows"]):
+            table[r, :len(VAL_COLUMNS)] = [_dec(x) for x in row]
+        return cls(table, {k: _dec(v) for k, v in d["header"].items()}, d["object_successes"], d["object_names"],
+                   d.get("settings"))
+
+
+def val_header_dict(raw: np.ndarray) -> Dict[str, Any]:
+    """dxrl_pg_val_header bytes -> {rows_written, best_row, stopped_row, since_best, best_score}."""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    i, f = raw[:32].view(np.int64), raw[32:64].view(np.float64)
+    return {"rows_written": int(i[0]), "best_row": int(i[1]), "stopped_row": int(i[2]), "since_best": int(i[3]),
+            "best_score": float(f[0])}
+
+
+def val_column_index(name: Optional[str], what: str = "val_keep_best") -> int:
+    if name is None:
+        return -1
+    if name not in _VAL_SCORE_COLUMNS:
+        raise ValueError(f"{what} must be one of {list(_VAL_SCORE_COLUMNS)} or None, got {name!r}")
+    return VAL_COLUMNS.index(name)
+
+
+# ====================================================================== validation plan
+class ValidationPlan:
+    """A held-out evaluation of the trainer's live actor, built once: what
+    ``Evaluator.evaluate_heldout_set(K, seed, parallel=True, device_seed=device_seed)`` would
+    launch (object-major records, one lane per episode, device Philox resets), with its env, lane
+    and segment tables, record buffers, work-queue counter and status word kept for the plan's
+    life.  ``run`` enqueues ``dxrl_evaluate_mlp`` on the trainer's packed weights and
+    ``dxrl_pg_val_row`` behind it and reads nothing back.  Every run uses the same seeds (common
+    random numbers), so rows are comparable across iterations.  The plan touches neither the
+    training env nor the trainer's streams or buffers."""
+
+    def __init__(self, tr, heldout_set, episodes_per_object: int = 5, seed: int = 0, device_seed: int = 0,
+                 max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0):
+        from .envs import VecEnv
+        from .evaluator import Evaluator
+        objs = list(heldout_set.heldout_objects)
+        G, K = len(objs), int(episodes_per_object)
+        if G < 1 or K < 1:
+            raise ValueError("a validation needs at least one held-out object and one episode per object")
+        if G > N.MAX_CURRICULA:
+            raise ValueError(f"{G} held-out objects: the env's curriculum table holds {N.MAX_CURRICULA} rows, one "
+                             f"per object -- validate on at most {N.MAX_CURRICULA} objects")
+        if seed is None:
+            raise ValueError("a validation repeats the same episodes every time: seed must be an integer")
+        ms = int(max_steps or tr.env.max_episode_steps)
+        dev = self.dev = tr.dev
+        self.G, self.K, self.E, self.max_steps = G, K, G * K, ms
+        self.seed, self.device_seed = int(seed), int(device_seed)
+        self.deterministic, self.solve_threshold = bool(deterministic), float(solve_threshold)
+        self.object_names = [f"object_{o}" for o in range(G)]
+        ev = Evaluator(None, heldout_set, reward_type=tr.env.reward_type, max_episode_steps=ms, device=dev)
+        program = ev.heldout_program(K, self.seed, parallel=True)
+        plan =program.plan(host_resets=False, host_noise=False)
+        self.fingerprint = {"objects": [_config_state(c) for c in program.configs], "episodes_per_object": K,
+                            "seed": self.seed, "device_seed": self.device_seed, "max_steps": ms,
+                            "deterministic": self.deterministic, "solve_threshold": self.solve_threshold,
+                            "reward_type": tr.env.reward_type}
+        self.fingerprint = json.loads(json.dumps(self.fingerprint))  # as a checkpoint returns it
+        E = self.E
+        self.env = VecEnv(E, reward_type=tr.env.reward_type, reward_shaping=tr.env.reward_shaping,
+                          max_episode_steps=ms, seed=self.device_seed, device=dev)
+        self.env.set_curricula(program.configs)
+        self.lane_off = torch.from_numpy(np.ascontiguousarray(plan.lane_off)).to(dev, torch.int32)
+        self.segments = torch.from_numpy(plan.segments.view(np.uint8).copy()).to(dev)
+        self.ep_return = torch.zeros(E, dtype=torch.float64, device=dev)
+        self.ep_length = torch.zeros(E, dtype=torch.int32, device=dev)
+        self.ep_success = torch.zeros(E, dtype=torch.uint8, device=dev)
+        self.ep_contacts = torch.zeros(E, dtype=torch.uint8, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.queue = torch.zeros(1, dtype=torch.int32, device=dev)
+        nb = C.c_int64()
+        N.call("dxrl_pg_val_partial_doubles", G, K, C.byref(nb))
+        self.partial = torch.zeros(nb.value, dtype=torch.float64, device=dev)
+        self.action_std = None  # exp(log_std) of the last stochastic run (kept alive for its launch)
+        a = self.args = N.EvalArgs()
+        a.num_lanes, a.policy, a.max_steps, a.total_episodes = E, N.EVAL_POLICY_MLP, ms, E
+        a.lane_segments, a.segments = N.ptr(self.lane_off), N.ptr(self.segments)
+        a.policy_seed = a.noise_seed = a.reset_seed = self.device_seed & (2**64 - 1)
+        a.ep_return, a.ep_length, a.ep_success = N.ptr(self.ep_return), N.ptr(self.ep_length), N.ptr(self.ep_success)
+        a.ep_contacts, a.status, a.work_queue = N.ptr(self.ep_contacts), N.ptr(self.status), N.ptr(self.queue)
+
+    def run(self, tr, val: "_ValState", iteration: int, env_steps: int, train_row: int, score_col: int = -1,
+            min_delta: float = 0.0, patience: int = 0):
+        """Enqueue one validation of the trainer's current weights as row ``val.rows`` (no sync).
+        ``tr.params`` is swapped with a spare buffer by every optimiser step, so the pointers are
+        taken here."""
+        from .trainer import ACT, OFF
+        if val.fingerprint != self.fingerprint:
+            raise ValueError("this run's validation table was written by another plan (differs in "
+                             f"{', '.join(fingerprint_diff(val.fingerprint, self.fingerprint))})")
+        val.reserve(val.rows + 1)
+        p = N.ptr
+        with torch.cuda.device(self.dev):
+            self.status.zero_()  # the episode kernel only ever sets bits of it
+            m = N.EvalMlp()
+            m.packed, m.params, m.action_std = p(tr.packed), p(tr.params), None
+            if not self.deterministic:
+                # f64 exp rounded to f32 (the kernel evaluates no exp)
+                ls = tr.params[OFF["logstd"]:OFF["logstd"] + ACT]
+                self.action_std = torch.exp(ls.double()).float()
+                m.action_std = p(self.action_std)
+            N.call("dxrl_evaluate_mlp", self.env.handle, C.byref(self.args), C.byref(m), tr._s())
+            v = N.PgValArgs()
+            v.num_objects, v.episodes_per_object, v.row, v.cap = self.G, self.K, val.rows, val.cap
+            v.iteration, v.env_steps, v.train_row = int(iteration), int(env_steps), int(train_row)
+            v.num_params, v.partial_doubles = tr.params.numel(), self.partial.numel()
+            v.score_col, v.patience = int(score_col), int(patience)
+            v.min_delta, v.solve_threshold = float(min_delta), self.solve_threshold
+            v.ep_return, v.ep_length, v.ep_success = p(self.ep_return), p(self.ep_length), p(self.ep_success)
+            v.ep_contacts, v.status = p(self.ep_contacts), p(self.status)
+            v.params, v.best_params, v.partial = p(tr.params), p(val.best_params), p(self.partial)
+            v.val, v.object_successes, v.header = p(val.table), p(val.objects), p(val.header)
+            N.call("dxrl_pg_val_row", self.dev.index, C.byref(v), tr._s())
+        val.rows += 1
+
+
+def fingerprint_diff(a: Dict[str, Any], b: Dict[str, Any]):
+    return sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+
+
+class _ValState:
+    """The device validation table, per-object table, header and validation-best parameters of a
+    trainer's run (a second, independent set beside the training log's)."""
+
+    def __init__(self, tr, fingerprint: Dict[str, Any], object_names, cap: int = 0):
+        d = self.dev = tr.dev
+        self.fingerprint, self.object_names, self.G = fingerprint, list(object_names), len(object_names)
+        self.cap = 0
+        self.table = self.objects = self.host_table = self.host_objects = None
+        self.header = torch.zeros(_VAL_HEADER_BYTES, dtype=torch.uint8, device=d)
+        self.header[8:24].view(torch.int64).fill_(-1)                  # best_row, stopped_row
+        self.header[32:40].view(torch.float64).fill_(-math.inf)        # best_score
+        self.host_header = torch.zeros(_VAL_HEADER_BYTES, dtype=torch.uint8).pin_memory()
+        self.best_params = torch.zeros_like(tr.params)
+        self.rows = 0
+        self.settings: Dict[str, Any] = {}
+        self.event = torch.cuda.Event()
+        self.last_log = None
+        self.reserve(cap)
+
+    def reserve(self, cap: int):
+        if self.table is not None and cap <= self.cap:
+            return
+        cap = max(cap, _MIN_VAL_CAP, 2 * self.cap)
+        table = torch.zeros(cap, VAL_COLS, dtype=torch.float64, device=self.dev)
+        objects = torch.zeros(cap, self.G, dtype=torch.int32, device=self.dev)
+        if self.table is not None and self.rows:
+            table[:self.rows].copy_(self.table[:self.rows])
+            objects[:self.rows].copy_(self.objects[:self.rows])
+        self.table, self.objects, self.cap = table, objects, cap
+        self.host_table = torch.zeros(cap, VAL_COLS, dtype=torch.float64).pin_memory()
+        self.host_objects = torch.zeros(cap, self.G, dtype=torch.int32).pin_memory()
+
+
+def val_state(tr, st: "_RunState", plan: ValidationPlan) -> _ValState:
+    """The run's validation state for `plan`: created on first use; a run validated by another
+    plan (an earlier fit, or a checkpoint) raises."""
+    if st.val is None:
+        st.val = _ValState(tr, plan.fingerprint, plan.object_names)
+    elif st.val.fingerprint != plan.fingerprint:
+        raise ValueError("this run is validated by another plan (differs in "
+                         f"{', '.join(fingerprint_diff(st.val.fingerprint, plan.fingerprint))}): a validation "
+                         "table holds rows of one held-out set, episode count, seeds, step limit and mode")
+    return st.val
+
+
+def validation_log(tr) -> Optional[ValidationLog]:
+    """The run's validation curve so far (None: never validated), filled like ``training_log``."""
+    st = getattr(tr, "_run", None)
+    v = st.val if st is not None else None
+    if v is None:
+        return None
+    last = v.last_log() if v.last_log is not None else None
+    if last is not None:
+        last._resolve()
+    if v.rows:
+        v.host_table[:v.rows].copy_(v.table[:v.rows], non_blocking=True)
+        v.host_objects[:v.rows].copy_(v.objects[:v.rows], non_blocking=True)
+    v.host_header.copy_(v.header, non_blocking=True)
+    v.event.record(torch.cuda.current_stream(tr.dev))
+    log = ValidationLog(object_names=v.object_names, settings=v.settings,
+                        _pending=(v.event, v.host_table, v.host_header, v.host_objects, v.rows))
+    v.last_log = weakref.ref(log)
+    return log
+
+
 # ====================================================================== device state of a run
 class _RunState:
     """The device table, header, best parameters and scratch of a trainer's run."""
@@ -198,6 +503,7 @@ class _RunState:
         self.host_reads = 0   # host reads of device memory made inside fit (polls)
         self.event = torch.cuda.Event()
         self.last_log = None  # weak reference to the last TrainingLog handed out
+        self.val: Optional[_ValState] = None  # the validation tables (fit(validation=plan))
         self.reserve(tr, cap)
 
     def reserve(self, tr, cap: int):
@@ -244,7 +550,9 @@ def log_iteration(tr, st: _RunState, score_col: int, min_episodes: int, conv_col
 
 
 def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episodes: int = 1, converge=None,
-        stop_on_converge: bool = False, poll_every: int = 0) -> TrainingLog:
+        stop_on_converge: bool = False, poll_every: int = 0, validation: Optional[ValidationPlan] = None,
+        validate_every: int = 1, val_keep_best: Optional[str] = "success_rate", min_delta: float = 0.0,
+        patience: int = 0, stop_on_patience: bool = False) -> TrainingLog:
     """Run `iterations` training iterations, logging each on the device.
 
     keep_best: the score column ("mean_return", "success_rate", any column before is_best, or
@@ -253,7 +561,17 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
     whose window mean is strictly above the threshold.  With poll_every = k and
     stop_on_converge the header is read every k iterations and the run stops at the first poll
     after convergence; with poll_every = 0 the host reads nothing until the log is first used.
-    A second fit on the same trainer continues the same log."""
+    A second fit on the same trainer continues the same log.
+
+    validation: a ``ValidationPlan`` (``tr.validation_plan(heldout_set, ...)``).  After every
+    validate_every-th logged iteration of the run, and after the last one of this call, the plan
+    runs against the weights the next rollout would use and ``dxrl_pg_val_row`` appends a row to
+    the run's validation table (``log.validation``): a second keep-best (val_keep_best, a column
+    of the validation table; strictly above the best so far + min_delta) with its own best
+    parameters (``tr.best_policy(which="validation")``), and patience: the validation header's
+    stopped_row is the first row that is the patience-th in a row without a new best.  With
+    stop_on_patience the validation header is read at the same polls, and the run stops at the
+    first poll after stopped_row is set.  keep_best / converge on the training log are untouched."""
     if tr.collective:
         raise ValueError("fit() runs on one rank: a collective trainer (world > 1 or a process group) would need "
                          "the ranks' log sums merged between the reduce and the finish stage, which is not built")
@@ -269,18 +587,42 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
             raise ValueError("converge must be (column, window >= 1, threshold)")
     if stop_on_converge and converge is None:
         raise ValueError("stop_on_converge needs converge=(column, window, threshold)")
+    val_col, every, patience = val_column_index(val_keep_best), int(validate_every), int(patience)
+    if validation is not None and not isinstance(validation, ValidationPlan):
+        raise ValueError("validation must be a ValidationPlan (tr.validation_plan(heldout_set, ...))")
+    if every < 1 or patience < 0:
+        raise ValueError("validate_every must be >= 1 and patience >= 0")
+    if stop_on_patience and (validation is None or patience < 1):
+        raise ValueError("stop_on_patience needs validation=plan and patience >= 1")
     st = run_state(tr)
+    val = val_state(tr, st, validation) if validation is not None else None
     st.reserve(tr, st.rows + iterations)
     if converge is not None:
         st.window = window
     st.settings = {"keep_best": keep_best, "min_episodes": int(min_episodes),
                    "converge": None if converge is None else [converge[0], window, threshold]}
+    if val is not None:
+        val.reserve(val.rows + iterations // every + 1)
+        val.settings = {"validate_every": every, "val_keep_best": val_keep_best, "min_delta": float(min_delta),
+                        "patience": patience}
+
+    def validate():
+        validation.run(tr, val, tr.iteration_index - 1, st.env_steps, st.rows - 1, val_col, min_delta, patience)
+
     for k in range(iterations):
         tr.iteration()
         log_iteration(tr, st, score_col, min_episodes, conv_col, window, threshold)
-        if poll_every and stop_on_converge and (k + 1) % int(poll_every) == 0:
+        validated = val is not None and (st.rows % every == 0 or k == iterations - 1)
+        if validated:
+            validate()
+        if poll_every and (stop_on_converge or stop_on_patience) and (k + 1) % int(poll_every) == 0:
             st.host_reads += 1
-            if header_dict(st.header.cpu().numpy())["converged_row"] >= 0:
+            stop = stop_on_converge and header_dict(st.header.cpu().numpy())["converged_row"] >= 0
+            if stop_on_patience and val_header_dict(val.header.cpu().numpy())["stopped_row"] >= 0:
+                stop = True
+            if stop:
+                if val is not None and not validated:
+                    validate()  # the last iteration of the run is always validated
                 break
     return training_log(tr)
 
@@ -296,15 +638,22 @@ def training_log(tr) -> TrainingLog:
     st.host_header.copy_(st.header, non_blocking=True)
     st.event.record(torch.cuda.current_stream(tr.dev))
     log = TrainingLog(window=st.window, settings=st.settings,
-                      _pending=(st.event, st.host_table, st.host_header, st.rows))
+                      _pending=(st.event, st.host_table, st.host_header, st.rows), validation=validation_log(tr))
     st.last_log = weakref.ref(log)
     return log
 
 
-def best_policy(tr, deterministic: bool = True, seed: Optional[int] = None):
-    """The actor of the best logged iteration as a frozen ``MLPActorPolicy``."""
+def best_policy(tr, deterministic: bool = True, seed: Optional[int] = None, which: str = "training"):
+    """The actor of the best logged iteration (which="training") or of the best validation
+    (which="validation") as a frozen ``MLPActorPolicy``."""
     from .policies import MLPActorPolicy
+    if which not in ("training", "validation"):
+        raise ValueError(f'which must be "training" or "validation", got {which!r}')
     st = getattr(tr, "_run", None)
+    if which == "validation":
+        if st is None or st.val is None or val_header_dict(st.val.header.cpu().numpy())["best_row"] < 0:
+            raise ValueError("no validation-best parameters yet: run fit(validation=plan) with val_keep_best")
+        return MLPActorPolicy.from_params(st.val.best_params, deterministic=deterministic, seed=seed)
     if st is None or header_dict(st.header.cpu().numpy())["best_row"] < 0:
         raise ValueError("no best parameters yet: run fit() with keep_best, and min_episodes that some iteration "
                          "reaches")
@@ -366,7 +715,32 @@ def save_checkpoint(tr, path):
         arrays.update(log_table=host(st.table[:st.rows]), log_header=host(st.header),
                       best_params=host(st.best_params))
         meta["log"] = {"rows": st.rows, "env_steps": st.env_steps, "window": st.window, "settings": st.settings}
+        if st.val is not None:  # optional entries: a run never validated writes the file it always did
+            arrays.update(validation_arrays(host(st.val.table[:st.val.rows]), host(st.val.header),
+                                            host(st.val.best_params), host(st.val.objects[:st.val.rows])))
+            meta["validation"] = validation_meta(st.val.rows, st.val.fingerprint, st.val.object_names, st.val.settings)
     write_checkpoint(path, arrays, meta)
+
+
+def validation_arrays(table, header, best_params, objects) -> Dict[str, np.ndarray]:
+    """The checkpoint's optional validation arrays."""
+    return {"val_table": table, "val_header": header, "val_best_params": best_params, "val_objects": objects}
+
+
+def validation_meta(rows: int, fingerprint, object_names, settings) -> Dict[str, Any]:
+    """The checkpoint's optional `validation` entry of the JSON part."""
+    return {"rows": int(rows), "fingerprint": fingerprint, "object_names": list(object_names),
+            "settings": dict(settings or {})}
+
+
+def validation_log_of_checkpoint(arrays: Dict[str, np.ndarray], meta: Dict[str, Any]) -> Optional[ValidationLog]:
+    """The validation curve a checkpoint carries (None: the run was never validated, or the file
+    predates validation)."""
+    v = meta.get("validation")
+    if v is None:
+        return None
+    return ValidationLog(arrays["val_table"], val_header_dict(arrays["val_header"]), arrays["val_objects"],
+                         v["object_names"], v.get("settings"))
 
 
 def load_checkpoint(cls, path, env):
@@ -408,5 +782,14 @@ def load_checkpoint(cls, path, env):
             put(st.table[:st.rows], "log_table")
         put(st.header, "log_header")
         put(st.best_params, "best_params")
+        v = meta.get("validation")  # absent in checkpoints written before validation existed
+        if v is not None:
+            val = st.val = _ValState(tr, v["fingerprint"], v["object_names"], int(v["rows"]))
+            val.rows, val.settings = int(v["rows"]), dict(v["settings"] or {})
+            if val.rows:
+                put(val.table[:val.rows], "val_table")
+                put(val.objects[:val.rows], "val_objects")
+            put(val.header, "val_header")
+            put(val.best_params, "val_best_params")
     torch.cuda.synchronize(dev)
     return tr

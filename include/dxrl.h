@@ -1143,6 +1143,115 @@ typedef struct dxrl_pg_log_args {
 int dxrl_pg_log_partial_doubles(int64_t num_envs, int64_t horizon, int64_t* out);
 int dxrl_pg_log_row(int32_t device, const dxrl_pg_log_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Held-out validation row of a training run (csrc/dxrl_pg_val.hip).  One call per validation,
+ * enqueued behind dxrl_evaluate_mlp on the same stream: it reduces the episode records of an
+ * object-major evaluation (G objects x K episodes, E = G K, the record of object o, episode k
+ * at o K + k -- Evaluator.heldout_program's layout) into row `row` of the f64 table
+ * val[cap][DXRL_PG_VAL_COLS]; nothing returns to the host.
+ *
+ * Columns (enum dxrl_pg_val_col):
+ *   iteration, env_steps,      the host scalars; train_row is the row of the training log this
+ *   train_row                  validation follows
+ *   episodes                   E
+ *   successes, success_rate    count of non-zero ep_success bytes, and that count / E
+ *   mean_return, return_std    population mean and standard deviation of ep_return
+ *                              (np.mean / np.std, EvalSummary.std_reward's definition)
+ *   mean_length                mean of ep_length
+ *   mean_success_length        mean of ep_length over the successes (NaN with none)
+ *   mean_contacts              mean of ep_contacts
+ *   min_object_success_rate    min over objects of successes(o) / K
+ *   objects_solved             objects with (double)successes(o) / K >= solve_threshold
+ *   eval_status                the episode kernel's status word
+ *   is_best, since_best        below
+ *
+ * Integer sums are exact; the return moments are (count, mean, M2) triples of ep_return - ep_return[0]
+ * (the shift is exact for returns of one magnitude, so a large common offset does not cancel)
+ * merged with Chan's update in a fixed order: records in index order inside a thread, lanes by
+ * shuffles, waves and workgroup partials in index order.  No floating-point atomics; the same
+ * inputs give the same bytes on every call.
+ *
+ * Header (dxrl_pg_val_header, device memory, initialised by the caller to rows_written 0,
+ * best_row -1, stopped_row -1, since_best 0, best_score -inf):
+ *   keep-best (score_col >= 0): is_best = 1 iff eval_status == 0 and
+ *     val[row][score_col] > best_score + min_delta (strict: the first maximum wins, a NaN is
+ *     never best, and with best_score == -inf any finite score is); best_score / best_row are
+ *     then updated, and a following launch copies params to best_params (num_params f32) iff
+ *     is_best -- the flag is read on the device.
+ *   patience: since_best = 0 if is_best, else the header's since_best (the previous row's) + 1;
+ *     with patience > 0, stopped_row = the first row with since_best >= patience, never
+ *     overwritten once set.
+ *   rows_written = row + 1.
+ * object_successes (nullable): row `row` of i32 [cap][G], the per-object success counts.
+ * Launches: reduce, finish, and the copy when params / best_params are given and score_col >= 0.
+ * DXRL_E_INVALID before any launch: null args or required pointer, G or K < 1, G K above
+ * INT32_MAX, row outside [0, cap), score_col >= DXRL_PG_VAL_IS_BEST, patience < 0, params
+ * without best_params or the reverse (or with num_params < 1), partial_doubles smaller than
+ * dxrl_pg_val_partial_doubles(G, K).
+ * ------------------------------------------------------------------------ */
+#define DXRL_PG_VAL_COLS 16
+enum dxrl_pg_val_col {
+    DXRL_PG_VAL_ITERATION = 0,
+    DXRL_PG_VAL_ENV_STEPS,
+    DXRL_PG_VAL_TRAIN_ROW,
+    DXRL_PG_VAL_EPISODES,
+    DXRL_PG_VAL_SUCCESSES,
+    DXRL_PG_VAL_SUCCESS_RATE,
+    DXRL_PG_VAL_MEAN_RETURN,
+    DXRL_PG_VAL_RETURN_STD,
+    DXRL_PG_VAL_MEAN_LENGTH,
+    DXRL_PG_VAL_MEAN_SUCCESS_LENGTH,
+    DXRL_PG_VAL_MEAN_CONTACTS,
+    DXRL_PG_VAL_MIN_OBJECT_SUCCESS_RATE,
+    DXRL_PG_VAL_OBJECTS_SOLVED,
+    DXRL_PG_VAL_EVAL_STATUS,
+    DXRL_PG_VAL_IS_BEST,
+    DXRL_PG_VAL_SINCE_BEST,
+    DXRL_PG_VAL_NAMED /* 16 named columns == DXRL_PG_VAL_COLS (a multiple of 4) */
+};
+
+typedef struct dxrl_pg_val_header {
+    int64_t rows_written;
+    int64_t best_row;      /* -1: none yet */
+    int64_t stopped_row;   /* -1: patience not exhausted */
+    int64_t since_best;    /* the last written row's since_best */
+    double best_score;     /* -inf: none yet */
+    double reserved_f64[3];
+} dxrl_pg_val_header;
+
+typedef struct dxrl_pg_val_args {
+    int64_t num_objects;             /* G                                                    */
+    int64_t episodes_per_object;     /* K                                                    */
+    int64_t row;                     /* table row this call writes, 0 <= row < cap           */
+    int64_t cap;                     /* rows of the tables                                   */
+    int64_t iteration;               /* column 0                                             */
+    int64_t env_steps;               /* column 1                                             */
+    int64_t train_row;               /* column 2                                             */
+    int64_t num_params;              /* f32 elements of params / best_params                 */
+    int64_t partial_doubles;         /* f64 elements of partial                              */
+    int32_t score_col;               /* keep-best column, < 0: off                           */
+    int32_t patience;                /* >= 0; 0: never stops                                 */
+    double min_delta;                /* keep-best margin                                     */
+    double solve_threshold;          /* objects_solved: success rate >= this                 */
+    /* device inputs */
+    const double*  ep_return;        /* f64 [E]                                              */
+    const int32_t* ep_length;        /* i32 [E]                                              */
+    const uint8_t* ep_success;       /* u8  [E]                                              */
+    const uint8_t* ep_contacts;      /* u8  [E]                                              */
+    const int32_t* status;           /* i32 [1] the episode kernel's status word             */
+    const float*   params;           /* f32 [num_params] (nullable with best_params)         */
+    /* device scratch and outputs */
+    double*  partial;                /* f64 [partial_doubles] scratch                        */
+    float*   best_params;            /* f32 [num_params] (nullable with params)              */
+    double*  val;                    /* f64 [cap][DXRL_PG_VAL_COLS]                          */
+    int32_t* object_successes;       /* i32 [cap][G] (nullable)                              */
+    dxrl_pg_val_header* header;
+} dxrl_pg_val_args;
+
+/* f64 elements of dxrl_pg_val_row's `partial` scratch for G objects x K episodes. */
+int dxrl_pg_val_partial_doubles(int64_t num_objects, int64_t episodes_per_object, int64_t* out);
+int dxrl_pg_val_row(int32_t device, const dxrl_pg_val_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
