@@ -256,10 +256,34 @@ class PgValArgs(C.Structure):
                                           "partial", "best_params", "val", "object_successes", "header")]
 
 
+# enum dxrl_pg_val_level_col / dxrl_pg_val_robust_col: the per-level and over-levels tables of
+# dxrl_pg_val_levels_row, in table order
+PG_VAL_MAX_LEVELS = 16              # DXRL_PG_VAL_MAX_LEVELS
+PG_VAL_LEVEL_COLUMNS = ("obs_noise_std", "dyn_noise_std", "episodes", "successes", "success_rate", "mean_return",
+                        "return_std", "mean_length", "mean_contacts", "min_object_success_rate", "degradation",
+                        "degradation_percentage")
+PG_VAL_LEVEL_COLS = len(PG_VAL_LEVEL_COLUMNS)    # DXRL_PG_VAL_LEVEL_COLS
+PG_VAL_ROBUST_COLUMNS = ("levels", "worst_level", "worst_success_rate", "mean_success_rate",
+                         "mean_noisy_success_rate", "max_degradation", "max_degradation_percentage",
+                         "worst_mean_return")
+PG_VAL_ROBUST_COLS = len(PG_VAL_ROBUST_COLUMNS)  # DXRL_PG_VAL_ROBUST_COLS
+
+
+class PgValLevelsArgs(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("num_objects", "episodes_per_object", "row", "cap", "iteration", "env_steps",
+                                         "train_row", "num_params", "partial_doubles")] + \
+               [("score_col", C.c_int32), ("patience", C.c_int32), ("min_delta", C.c_double),
+                ("solve_threshold", C.c_double), ("num_levels", C.c_int32), ("score_table", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("ep_return", "ep_length", "ep_success", "ep_contacts", "status", "params",
+                                          "level_noise", "partial", "best_params", "val", "levels", "robust",
+                                          "object_successes", "header")]
+
+
 # the structs added after tests/test_native_abi.py fixed its list: (C name, mirror), sized against
 # include/dxrl.h by the tests of the layers that use them
 LATER_STRUCTS = (("dxrl_pg_log_args", PgLogArgs), ("dxrl_pg_log_header", PgLogHeader),
-                 ("dxrl_pg_val_args", PgValArgs), ("dxrl_pg_val_header", PgValHeader))
+                 ("dxrl_pg_val_args", PgValArgs), ("dxrl_pg_val_header", PgValHeader),
+                 ("dxrl_pg_val_levels_args", PgValLevelsArgs))
 
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
@@ -318,6 +342,8 @@ _SIGS = {
     "dxrl_pg_log_row": (C.c_int, [_I32, C.POINTER(PgLogArgs), _P]),
     "dxrl_pg_val_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_val_row": (C.c_int, [_I32, C.POINTER(PgValArgs), _P]),
+    "dxrl_pg_val_levels_partial_doubles": (C.c_int, [_I32, _I64, _I64, C.POINTER(_I64)]),
+    "dxrl_pg_val_levels_row": (C.c_int, [_I32, C.POINTER(PgValLevelsArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

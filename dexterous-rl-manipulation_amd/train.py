@@ -7,6 +7,12 @@
   --validate-every K   validate on HeldOutObjectSet(<the run's curriculum config>) after every K-th
                        iteration: [--val-episodes E] per object, [--val-seed S], [--val-keep-best COL],
                        [--patience P] (with --poll-every: stop after P validations without a new best)
+  --val-obs-noise S.. --val-dyn-noise S..
+                       validate under noise as well: the levels of the robustness sweep over these
+                       observation / dynamics noise standard deviations (baseline, each alone, and the
+                       first-three x first-three combinations; at most 16 levels).  --val-keep-best may
+                       then name a score over the levels: worst_success_rate, mean_success_rate,
+                       mean_noisy_success_rate, worst_mean_return
 
 Writes DIR/training_log.json (TrainingLog, with the validation curve), DIR/best_policy.npz
 (MLPActorPolicy, when some iteration qualified as best), DIR/best_val_policy.npz (the actor of the
@@ -22,7 +28,7 @@ from typing import List, Optional
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
-    from .training_run import _SCORE_COLUMNS, _VAL_SCORE_COLUMNS
+    from .training_run import _SCORE_COLUMNS, _VAL_ROBUST_SCORE_COLUMNS, _VAL_SCORE_COLUMNS
     from .workloads import WORKLOADS
     p = argparse.ArgumentParser(prog="python -m dexterous_rl_manipulation_amd.train", description=__doc__,
                                 formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -41,7 +47,11 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--val-episodes", type=int, default=5, metavar="E", help="episodes per held-out object")
     p.add_argument("--val-seed", type=int, default=0, metavar="S")
     p.add_argument("--val-keep-best", metavar="COL", default="success_rate",
-                   choices=list(_VAL_SCORE_COLUMNS) + ["none"])
+                   choices=list(_VAL_SCORE_COLUMNS) + list(_VAL_ROBUST_SCORE_COLUMNS) + ["none"])
+    p.add_argument("--val-obs-noise", type=float, nargs="+", default=None, metavar="S",
+                   help="observation-noise levels of the validation sweep")
+    p.add_argument("--val-dyn-noise", type=float, nargs="+", default=None, metavar="S",
+                   help="dynamics-noise levels of the validation sweep")
     p.add_argument("--patience", type=int, default=0, metavar="P")
     p.add_argument("--envs", type=int, default=None, help="envs (default: the workload's, 4096 with --config)")
     p.add_argument("--horizon", type=int, default=200)
@@ -73,6 +83,18 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--patience needs --validate-every")
     if a.val_keep_best == "none":
         a.val_keep_best = None
+    a.val_noise_levels = None
+    if a.val_obs_noise is not None or a.val_dyn_noise is not None:
+        from .training_run import ValidationPlan, parse_noise_levels
+        if not a.validate_every:
+            p.error("--val-obs-noise / --val-dyn-noise need --validate-every")
+        try:
+            a.val_noise_levels = parse_noise_levels(
+                ValidationPlan.sweep_levels(a.val_obs_noise or [], a.val_dyn_noise or []))
+        except ValueError as e:
+            p.error(str(e))
+    if a.val_keep_best in _VAL_ROBUST_SCORE_COLUMNS and a.val_noise_levels is None:
+        p.error(f"--val-keep-best {a.val_keep_best} needs --val-obs-noise / --val-dyn-noise")
     if a.config_name is None and a.config is None:
         a.config_name = "easy"
     return a
@@ -123,7 +145,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     if a.validate_every:
         from .evaluation import HeldOutObjectSet
         plan = tr.validation_plan(HeldOutObjectSet(base_config), episodes_per_object=a.val_episodes,
-                                  seed=a.val_seed, max_steps=a.max_steps)
+                                  seed=a.val_seed, max_steps=a.max_steps, noise_levels=a.val_noise_levels)
         kw = dict(validation=plan, validate_every=a.validate_every, val_keep_best=a.val_keep_best,
                   patience=a.patience, stop_on_patience=bool(a.patience and a.poll_every))
     log = tr.fit(a.iterations, keep_best=a.keep_best, min_episodes=a.min_episodes, converge=a.converge,

@@ -791,11 +791,14 @@ class PGTrainer:
                                 patience=patience, stop_on_patience=stop_on_patience)
 
     def validation_plan(self, heldout_set, episodes_per_object: int = 5, seed: int = 0, device_seed: int = 0,
-                        max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0):
-        """A held-out evaluation of this trainer's live actor, built once for fit(validation=...)."""
+                        max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0,
+                        noise_levels=None):
+        """A held-out evaluation of this trainer's live actor, built once for fit(validation=...).
+        noise_levels: (obs_std, dyn_std) pairs (ValidationPlan.sweep_levels builds the reference's
+        sweep) -- every validation then runs all levels and logs per-level and robust rows."""
         from . import training_run
         return training_run.ValidationPlan(self, heldout_set, episodes_per_object, seed, device_seed, max_steps,
-                                           deterministic, solve_threshold)
+                                           deterministic, solve_threshold, noise_levels)
 
     def training_log(self):
         from . import training_run

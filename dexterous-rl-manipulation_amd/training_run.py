@@ -19,6 +19,11 @@ kernel on the trainer's live weights every ``validate_every`` iterations, and ``
 (csrc/dxrl_pg_val.hip) reduces its episode records to one row of a second device table with its
 own keep-best, best parameters and patience.  ``log.validation`` is the ``ValidationLog``; the
 checkpoint carries the validation tables and the plan's fingerprint as optional entries.
+
+A plan built with ``noise_levels`` validates under every (obs_std, dyn_std) level in the one
+episode launch, and ``dxrl_pg_val_levels_row`` (csrc/dxrl_pg_val_levels.hip) writes the clean
+row, a row per level with the degradation columns, and a row of scores over the levels
+(worst / mean success rate, worst mean return) that keep-best and patience may follow.
 """
 from __future__ import annotations
 
@@ -46,6 +51,13 @@ VAL_COLS = N.PG_VAL_COLS
 _VAL_SCORE_COLUMNS = VAL_COLUMNS[:N.PG_VAL_IS_BEST]  # columns the validation keep-best may read
 _VAL_HEADER_BYTES = C.sizeof(N.PgValHeader)
 _MIN_VAL_CAP = 64
+VAL_LEVEL_COLUMNS = N.PG_VAL_LEVEL_COLUMNS
+VAL_LEVEL_COLS = N.PG_VAL_LEVEL_COLS
+VAL_ROBUST_COLUMNS = N.PG_VAL_ROBUST_COLUMNS
+VAL_ROBUST_COLS = N.PG_VAL_ROBUST_COLS
+# columns of the robust row the validation keep-best may read (a plan with noise levels)
+_VAL_ROBUST_SCORE_COLUMNS = ("worst_success_rate", "mean_success_rate", "mean_noisy_success_rate",
+                             "worst_mean_return")
 
 
 def column_index(name: Optional[str], what: str) -> int:
@@ -196,25 +208,44 @@ def header_dict(raw: np.ndarray) -> Dict[str, Any]:
 class ValidationLog:
     """The held-out curve of a run: one row per validation (``log.validation["success_rate"]``,
     ``.columns``), the per-object success counts of every row with the objects' names, and the
-    iteration keep-best chose / patience ran out at (None: none)."""
+    iteration keep-best chose / patience ran out at (None: none).
+
+    A plan with noise levels adds ``noise_levels`` (the (obs_std, dyn_std) pairs, baseline first),
+    ``levels`` (f64 [rows][L][12], ``level_column(name)`` -> [rows][L]), ``robust`` (f64 [rows][8],
+    ``robust_column(name)``), ``level_results(row)``, and ``object_successes`` becomes
+    [rows][L][objects]; the main table is then level 0, the clean curve.  Without levels these
+    are None."""
 
     def __init__(self, table=None, header: Optional[Dict[str, Any]] = None, object_successes=None,
-                 object_names=(), settings: Optional[Dict[str, Any]] = None, _pending=None):
+                 object_names=(), settings: Optional[Dict[str, Any]] = None, _pending=None, noise_levels=None,
+                 levels=None, robust=None):
         self._pending = _pending
         self.object_names = list(object_names)
+        self.noise_levels = None if noise_levels is None else [(float(o), float(d)) for o, d in noise_levels]
+        L = self.num_levels
         self._table = None if table is None else np.array(table, dtype=np.float64).reshape(-1, VAL_COLS)
         self._header = dict(header) if header is not None else None
-        self._objects = None if object_successes is None else \
-            np.array(object_successes, dtype=np.int32).reshape(-1, len(self.object_names))
+        shape = (-1, L, len(self.object_names)) if L else (-1, len(self.object_names))
+        self._objects = None if object_successes is None else np.array(object_successes, dtype=np.int32).reshape(shape)
+        self._levels = None if levels is None or not L else \
+            np.array(levels, dtype=np.float64).reshape(-1, L, VAL_LEVEL_COLS)
+        self._robust = None if robust is None or not L else \
+            np.array(robust, dtype=np.float64).reshape(-1, VAL_ROBUST_COLS)
         self.settings = dict(settings or {})
+
+    @property
+    def num_levels(self) -> int:
+        return 0 if self.noise_levels is None else len(self.noise_levels)
 
     def _resolve(self):
         if self._pending is not None:
-            event, host_table, host_header, host_objects, rows = self._pending
+            event, host_table, host_header, host_objects, rows, *more = self._pending
             event.synchronize()
             self._table = host_table[:rows].numpy().copy()
             self._header = val_header_dict(host_header.numpy())
             self._objects = host_objects[:rows].numpy().copy()
+            if more:
+                self._levels, self._robust = (t[:rows].numpy().copy() for t in more)
             self._pending = None
 
     @property
@@ -229,9 +260,50 @@ class ValidationLog:
 
     @property
     def object_successes(self) -> np.ndarray:
-        """i32 [rows][objects]: successes of each object (out of episodes / objects per row)."""
+        """i32 [rows][objects] ([rows][levels][objects] with noise levels): successes of each
+        object (out of episodes / objects per row and level)."""
         self._resolve()
         return self._objects
+
+    @property
+    def levels(self) -> Optional[np.ndarray]:
+        """f64 [rows][L][12] (VAL_LEVEL_COLUMNS), or None without noise levels."""
+        self._resolve()
+        return self._levels
+
+    @property
+    def robust(self) -> Optional[np.ndarray]:
+        """f64 [rows][8] (VAL_ROBUST_COLUMNS), or None without noise levels."""
+        self._resolve()
+        return self._robust
+
+    def _need_levels(self):
+        if not self.num_levels:
+            raise ValueError("this validation has no noise levels (validation_plan(..., noise_levels=...))")
+
+    def level_column(self, name: str) -> np.ndarray:
+        """[rows][L]: one column of the level rows."""
+        self._need_levels()
+        return self.levels[:, :, VAL_LEVEL_COLUMNS.index(name)]
+
+    def robust_column(self, name: str) -> np.ndarray:
+        self._need_levels()
+        return self.robust[:, VAL_ROBUST_COLUMNS.index(name)]
+
+    @property
+    def robust_columns(self) -> Dict[str, np.ndarray]:
+        self._need_levels()
+        return {name: self.robust[:, k] for k, name in enumerate(VAL_ROBUST_COLUMNS)}
+
+    def level_results(self, row: int):
+        """The levels of one validation as ``RobustnessTester`` result dictionaries, in its order:
+        ``{"noise_levels": {observation_noise_std, dynamics_noise_std}, "metrics": {...}}``."""
+        self._need_levels()
+        out = []
+        for (o, d), r in zip(self.noise_levels, self.levels[row]):
+            out.append({"noise_levels": {"observation_noise_std": o, "dynamics_noise_std": d},
+                        "metrics": {name: float(r[k]) for k, name in enumerate(VAL_LEVEL_COLUMNS) if k >= 2}})
+        return out
 
     @property
     def columns(self) -> Dict[str, np.ndarray]:
@@ -278,13 +350,23 @@ class ValidationLog:
             col = self[name]
             out[f"final_{name}"] = float(col[-1])
             out[f"max_{name}"] = float(np.nanmax(col)) if not np.isnan(col).all() else float("nan")
+        if self.num_levels:
+            out["noise_levels"] = self.num_levels
+            for name in ("worst_success_rate", "mean_success_rate", "max_degradation_percentage"):
+                out[f"final_{name}"] = float(self.robust_column(name)[-1])
         return out
 
     def to_dict(self) -> Dict[str, Any]:
-        return {"columns": list(VAL_COLUMNS), "settings": self.settings, "object_names": self.object_names,
-                "header": {k: _enc(v) for k, v in self.header.items()},
-                "rows": [[_enc(x) for x in row[:len(VAL_COLUMNS)]] for row in self.table.tolist()],
-                "object_successes": self.object_successes.tolist()}
+        out = {"columns": list(VAL_COLUMNS), "settings": self.settings, "object_names": self.object_names,
+               "header": {k: _enc(v) for k, v in self.header.items()},
+               "rows": [[_enc(x) for x in row[:len(VAL_COLUMNS)]] for row in self.table.tolist()],
+               "object_successes": self.object_successes.tolist()}
+        if self.num_levels:  # a validation without levels serialises as it always did
+            out["noise_levels"] = [list(p) for p in self.noise_levels]
+            out["level_columns"], out["robust_columns"] = list(VAL_LEVEL_COLUMNS), list(VAL_ROBUST_COLUMNS)
+            out["levels"] = [[[_enc(x) for x in lv] for lv in row] for row in self.levels.tolist()]
+            out["robust"] = [[_enc(x) for x in row] for row in self.robust.tolist()]
+        return out
 
     @classmethod
     def from_dict(cls, d: Dict[str, Any]) -> "ValidationLog":
@@ -293,8 +375,16 @@ class ValidationLog:
         table = np.zeros((len(d["rows"]), VAL_COLS), dtype=np.float64)
         for r, row in enumerate(d["rows"]):
             table[r, :len(VAL_COLUMNS)] = [_dec(x) for x in row]
+        noise = d.get("noise_levels")  # absent in logs without levels and in older files
+        levels = robust = None
+        if noise is not None:
+            if list(d.get("level_columns", [])) != list(VAL_LEVEL_COLUMNS) or \
+                    list(d.get("robust_columns", [])) != list(VAL_ROBUST_COLUMNS):
+                raise ValueError("not a validation log with this build's level / robust columns")
+            levels = np.array([[[_dec(x) for x in lv] for lv in row] for row in d["levels"]], dtype=np.float64)
+            robust = np.array([[_dec(x) for x in row] for row in d["robust"]], dtype=np.float64)
         return cls(table, {k: _dec(v) for k, v in d["header"].items()}, d["object_successes"], d["object_names"],
-                   d.get("settings"))
+                   d.get("settings"), noise_levels=noise, levels=levels, robust=robust)
 
 
 def val_header_dict(raw: np.ndarray) -> Dict[str, Any]:
@@ -313,6 +403,45 @@ def val_column_index(name: Optional[str], what: str = "val_keep_best") -> int:
     return VAL_COLUMNS.index(name)
 
 
+def val_score(name: Optional[str], has_levels: bool, what: str = "val_keep_best"):
+    """(score_table, score_col) of a validation keep-best column: a column of the main row
+    (table 0), or -- for a plan with noise levels -- one of the robust row's score columns
+    (table 1)."""
+    if name in _VAL_ROBUST_SCORE_COLUMNS:
+        if not has_levels:
+            raise ValueError(f"{what}={name!r} is a score over noise levels: it needs a validation plan built "
+                             "with noise_levels")
+        return 1, VAL_ROBUST_COLUMNS.index(name)
+    if name is not None and name not in _VAL_SCORE_COLUMNS:
+        raise ValueError(f"{what} must be one of {list(_VAL_SCORE_COLUMNS)}, (with noise levels) "
+                         f"{list(_VAL_ROBUST_SCORE_COLUMNS)} or None, got {name!r}")
+    return 0, val_column_index(name, what)
+
+
+def parse_noise_levels(noise_levels):
+    """The (obs_std, dyn_std) pairs of a levels plan as a list of float pairs with the baseline
+    (0.0, 0.0) first (inserted when absent; moved to the front when given later).  ValueError for a
+    level that is not a pair of finite values >= 0, a duplicate, or more than
+    N.PG_VAL_MAX_LEVELS levels."""
+    levels = []
+    for lv in noise_levels:
+        try:
+            o, d = (float(x) for x in lv)
+        except (TypeError, ValueError):
+            raise ValueError(f"a noise level is an (obs_std, dyn_std) pair, got {lv!r}") from None
+        if not (math.isfinite(o) and math.isfinite(d)) or o < 0.0 or d < 0.0:
+            raise ValueError(f"noise standard deviations must be finite and >= 0, got {lv!r}")
+        if (o, d) in levels:
+            raise ValueError(f"duplicate noise level {(o, d)!r}")
+        levels.append((o, d))
+    if (0.0, 0.0) in levels:
+        levels.remove((0.0, 0.0))
+    levels.insert(0, (0.0, 0.0))
+    if len(levels) > N.PG_VAL_MAX_LEVELS:
+        raise ValueError(f"{len(levels)} noise levels (with the baseline): at most {N.PG_VAL_MAX_LEVELS}")
+    return levels
+
+
 # ====================================================================== validation plan
 class ValidationPlan:
     """A held-out evaluation of the trainer's live actor, built once: what
@@ -322,12 +451,22 @@ class ValidationPlan:
     life.  ``run`` enqueues ``dxrl_evaluate_mlp`` on the trainer's packed weights and
     ``dxrl_pg_val_row`` behind it and reads nothing back.  Every run uses the same seeds (common
     random numbers), so rows are comparable across iterations.  The plan touches neither the
-    training env nor the trainer's streams or buffers."""
+    training env nor the trainer's streams or buffers.
+
+    ``noise_levels`` (a sequence of (obs_std, dyn_std) pairs; ``parse_noise_levels``) makes it a
+    robustness sweep of the live actor: one lane per episode of every level, level-major (level
+    l, object o, episode k is lane, segment and record (l G + o) K + k), each lane the segment
+    ``Segment(o, [seed + k], obs_std, dyn_std)`` with device Philox noise, and
+    ``dxrl_pg_val_levels_row`` behind the one episode launch.  Level 0 is the baseline and holds
+    records 0 .. G K - 1, which are the plan without levels' records; the device streams are keyed
+    by record index, so the levels do not share spawns or noise draws (no common random numbers
+    across levels)."""
 
     def __init__(self, tr, heldout_set, episodes_per_object: int = 5, seed: int = 0, device_seed: int = 0,
-                 max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0):
+                 max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0,
+                 noise_levels=None):
         from .envs import VecEnv
-        from .evaluator import Evaluator
+        from .evaluator import Evaluator, Segment
         objs = list(heldout_set.heldout_objects)
         G, K = len(objs), int(episodes_per_object)
         if G < 1 or K < 1:
@@ -337,19 +476,31 @@ class ValidationPlan:
                              f"per object -- validate on at most {N.MAX_CURRICULA} objects")
         if seed is None:
             raise ValueError("a validation repeats the same episodes every time: seed must be an integer")
+        self.noise_levels = None if noise_levels is None else parse_noise_levels(noise_levels)
+        L = self.L = 0 if self.noise_levels is None else len(self.noise_levels)
         ms = int(max_steps or tr.env.max_episode_steps)
         dev = self.dev = tr.dev
-        self.G, self.K, self.E, self.max_steps = G, K, G * K, ms
+        self.G, self.K, self.E, self.max_steps = G, K, max(L, 1) * G * K, ms
+        if self.E > 2**31 - 1:
+            raise ValueError(f"{self.E} validation episodes: levels x objects x episodes must fit 32 bits")
         self.seed, self.device_seed = int(seed), int(device_seed)
         self.deterministic, self.solve_threshold = bool(deterministic), float(solve_threshold)
         self.object_names = [f"object_{o}" for o in range(G)]
         ev = Evaluator(None, heldout_set, reward_type=tr.env.reward_type, max_episode_steps=ms, device=dev)
         program = ev.heldout_program(K, self.seed, parallel=True)
+        if L:  # heldout_program's lanes (Segment(o, [seed + k])) once per level, with the level's noise
+            program = ev._program(program.configs)
+            for obs, dyn in self.noise_levels:
+                for o in range(G):
+                    for k in range(K):
+                        program.add_lane([Segment(o, [self.seed + k], obs, dyn, noise_seed=(self.seed, k))])
         plan =program.plan(host_resets=False, host_noise=False)
         self.fingerprint = {"objects": [_config_state(c) for c in program.configs], "episodes_per_object": K,
                             "seed": self.seed, "device_seed": self.device_seed, "max_steps": ms,
                             "deterministic": self.deterministic, "solve_threshold": self.solve_threshold,
                             "reward_type": tr.env.reward_type}
+        if L:  # a plan without levels keeps the fingerprint it always had
+            self.fingerprint["noise_levels"] = [list(p) for p in self.noise_levels]
         self.fingerprint = json.loads(json.dumps(self.fingerprint))  # as a checkpoint returns it
         E = self.E
         self.env = VecEnv(E, reward_type=tr.env.reward_type, reward_shaping=tr.env.reward_shaping,
@@ -364,7 +515,11 @@ class ValidationPlan:
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.queue = torch.zeros(1, dtype=torch.int32, device=dev)
         nb = C.c_int64()
-        N.call("dxrl_pg_val_partial_doubles", G, K, C.byref(nb))
+        if L:
+            N.call("dxrl_pg_val_levels_partial_doubles", L, G, K, C.byref(nb))
+            self.level_noise = torch.tensor(self.noise_levels, dtype=torch.float64, device=dev)
+        else:
+            N.call("dxrl_pg_val_partial_doubles", G, K, C.byref(nb))
         self.partial = torch.zeros(nb.value, dtype=torch.float64, device=dev)
         self.action_std = None  # exp(log_std) of the last stochastic run (kept alive for its launch)
         a = self.args = N.EvalArgs()
@@ -374,15 +529,29 @@ class ValidationPlan:
         a.ep_return, a.ep_length, a.ep_success = N.ptr(self.ep_return), N.ptr(self.ep_length), N.ptr(self.ep_success)
         a.ep_contacts, a.status, a.work_queue = N.ptr(self.ep_contacts), N.ptr(self.status), N.ptr(self.queue)
 
+    @staticmethod
+    def sweep_levels(observation_noise_levels, dynamics_noise_levels):
+        """The distinct (obs_std, dyn_std) levels of ``RobustnessTester.sweep_levels``, in its
+        order.  With a 0.0 among the first three values of a list the reference's combined block
+        repeats single-noise levels; a plan runs each level once, so a repeat is dropped."""
+        from .evaluator import RobustnessTester
+        obs, dyn = [float(x) for x in observation_noise_levels], [float(x) for x in dynamics_noise_levels]
+        if not all(math.isfinite(x) and x >= 0.0 for x in obs + dyn):  # the sweep would skip them silently
+            raise ValueError(f"noise standard deviations must be finite and >= 0, got {obs} and {dyn}")
+        levels = RobustnessTester.sweep_levels(obs, dyn)[0]
+        return list(dict.fromkeys((float(o), float(d)) for o, d in levels))
+
     def run(self, tr, val: "_ValState", iteration: int, env_steps: int, train_row: int, score_col: int = -1,
-            min_delta: float = 0.0, patience: int = 0):
+            min_delta: float = 0.0, patience: int = 0, score_table: int = 0):
         """Enqueue one validation of the trainer's current weights as row ``val.rows`` (no sync).
         ``tr.params`` is swapped with a spare buffer by every optimiser step, so the pointers are
-        taken here."""
+        taken here.  ``score_table`` 1 (a plan with levels) reads the score from the robust row."""
         from .trainer import ACT, OFF
         if val.fingerprint != self.fingerprint:
             raise ValueError("this run's validation table was written by another plan (differs in "
                              f"{', '.join(fingerprint_diff(val.fingerprint, self.fingerprint))})")
+        if score_table and not self.L:
+            raise ValueError("a robust score needs a plan with noise levels")
         val.reserve(val.rows + 1)
         p = N.ptr
         with torch.cuda.device(self.dev):
@@ -395,7 +564,7 @@ class ValidationPlan:
                 self.action_std = torch.exp(ls.double()).float()
                 m.action_std = p(self.action_std)
             N.call("dxrl_evaluate_mlp", self.env.handle, C.byref(self.args), C.byref(m), tr._s())
-            v = N.PgValArgs()
+            v = N.PgValLevelsArgs() if self.L else N.PgValArgs()
             v.num_objects, v.episodes_per_object, v.row, v.cap = self.G, self.K, val.rows, val.cap
             v.iteration, v.env_steps, v.train_row = int(iteration), int(env_steps), int(train_row)
             v.num_params, v.partial_doubles = tr.params.numel(), self.partial.numel()
@@ -405,7 +574,12 @@ class ValidationPlan:
             v.ep_contacts, v.status = p(self.ep_contacts), p(self.status)
             v.params, v.best_params, v.partial = p(tr.params), p(val.best_params), p(self.partial)
             v.val, v.object_successes, v.header = p(val.table), p(val.objects), p(val.header)
-            N.call("dxrl_pg_val_row", self.dev.index, C.byref(v), tr._s())
+            if self.L:
+                v.num_levels, v.score_table, v.level_noise = self.L, int(score_table), p(self.level_noise)
+                v.levels, v.robust = p(val.levels), p(val.robust)
+                N.call("dxrl_pg_val_levels_row", self.dev.index, C.byref(v), tr._s())
+            else:
+                N.call("dxrl_pg_val_row", self.dev.index, C.byref(v), tr._s())
         val.rows += 1
 
 
@@ -415,13 +589,19 @@ def fingerprint_diff(a: Dict[str, Any], b: Dict[str, Any]):
 
 class _ValState:
     """The device validation table, per-object table, header and validation-best parameters of a
-    trainer's run (a second, independent set beside the training log's)."""
+    trainer's run (a second, independent set beside the training log's).  For a plan with noise
+    levels (the fingerprint's noise_levels) also the level and robust tables, and the per-object
+    table holds a row per level."""
 
     def __init__(self, tr, fingerprint: Dict[str, Any], object_names, cap: int = 0):
         d = self.dev = tr.dev
         self.fingerprint, self.object_names, self.G = fingerprint, list(object_names), len(object_names)
+        noise = fingerprint.get("noise_levels")
+        self.noise_levels = None if noise is None else [(float(o), float(dd)) for o, dd in noise]
+        self.L = 0 if noise is None else len(noise)
         self.cap = 0
         self.table = self.objects = self.host_table = self.host_objects = None
+        self.levels = self.robust = self.host_levels = self.host_robust = None
         self.header = torch.zeros(_VAL_HEADER_BYTES, dtype=torch.uint8, device=d)
         self.header[8:24].view(torch.int64).fill_(-1)                  # best_row, stopped_row
         self.header[32:40].view(torch.float64).fill_(-math.inf)        # best_score
@@ -433,18 +613,26 @@ class _ValState:
         self.last_log = None
         self.reserve(cap)
 
+    def _shapes(self, cap: int):
+        """name -> (shape, dtype) of the run's validation tables."""
+        shapes = {"table": ((cap, VAL_COLS), torch.float64),
+                  "objects": ((cap, self.L, self.G) if self.L else (cap, self.G), torch.int32)}
+        if self.L:
+            shapes["levels"] = ((cap, self.L, VAL_LEVEL_COLS), torch.float64)
+            shapes["robust"] = ((cap, VAL_ROBUST_COLS), torch.float64)
+        return shapes
+
     def reserve(self, cap: int):
         if self.table is not None and cap <= self.cap:
             return
         cap = max(cap, _MIN_VAL_CAP, 2 * self.cap)
-        table = torch.zeros(cap, VAL_COLS, dtype=torch.float64, device=self.dev)
-        objects = torch.zeros(cap, self.G, dtype=torch.int32, device=self.dev)
-        if self.table is not None and self.rows:
-            table[:self.rows].copy_(self.table[:self.rows])
-            objects[:self.rows].copy_(self.objects[:self.rows])
-        self.table, self.objects, self.cap = table, objects, cap
-        self.host_table = torch.zeros(cap, VAL_COLS, dtype=torch.float64).pin_memory()
-        self.host_objects = torch.zeros(cap, self.G, dtype=torch.int32).pin_memory()
+        for name, (shape, dtype) in self._shapes(cap).items():
+            new, old = torch.zeros(shape, dtype=dtype, device=self.dev), getattr(self, name)
+            if old is not None and self.rows:
+                new[:self.rows].copy_(old[:self.rows])
+            setattr(self, name, new)
+            setattr(self, "host_" + name, torch.zeros(shape, dtype=dtype).pin_memory())
+        self.cap = cap
 
 
 def val_state(tr, st: "_RunState", plan: ValidationPlan) -> _ValState:
@@ -455,7 +643,8 @@ def val_state(tr, st: "_RunState", plan: ValidationPlan) -> _ValState:
     elif st.val.fingerprint != plan.fingerprint:
         raise ValueError("this run is validated by another plan (differs in "
                          f"{', '.join(fingerprint_diff(st.val.fingerprint, plan.fingerprint))}): a validation "
-                         "table holds rows of one held-out set, episode count, seeds, step limit and mode")
+                         "table holds rows of one held-out set, episode count, seeds, step limit, mode and "
+                         "noise levels")
     return st.val
 
 
@@ -468,13 +657,15 @@ def validation_log(tr) -> Optional[ValidationLog]:
     last = v.last_log() if v.last_log is not None else None
     if last is not None:
         last._resolve()
+    names = ("table", "objects") + (("levels", "robust") if v.L else ())
     if v.rows:
-        v.host_table[:v.rows].copy_(v.table[:v.rows], non_blocking=True)
-        v.host_objects[:v.rows].copy_(v.objects[:v.rows], non_blocking=True)
+        for name in names:
+            getattr(v, "host_" + name)[:v.rows].copy_(getattr(v, name)[:v.rows], non_blocking=True)
     v.host_header.copy_(v.header, non_blocking=True)
     v.event.record(torch.cuda.current_stream(tr.dev))
-    log = ValidationLog(object_names=v.object_names, settings=v.settings,
-                        _pending=(v.event, v.host_table, v.host_header, v.host_objects, v.rows))
+    more = (v.host_levels, v.host_robust) if v.L else ()
+    log = ValidationLog(object_names=v.object_names, settings=v.settings, noise_levels=v.noise_levels,
+                        _pending=(v.event, v.host_table, v.host_header, v.host_objects, v.rows) + more)
     v.last_log = weakref.ref(log)
     return log
 
@@ -571,7 +762,13 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
     parameters (``tr.best_policy(which="validation")``), and patience: the validation header's
     stopped_row is the first row that is the patience-th in a row without a new best.  With
     stop_on_patience the validation header is read at the same polls, and the run stops at the
-    first poll after stopped_row is set.  keep_best / converge on the training log are untouched."""
+    first poll after stopped_row is set.  keep_best / converge on the training log are untouched.
+
+    With a plan built with noise_levels every validation is a robustness sweep of the live actor
+    (``dxrl_pg_val_levels_row``): ``log.validation`` keeps its columns as the clean (level 0)
+    curve and gains ``levels`` / ``robust``, and val_keep_best may also name a score over the
+    levels -- "worst_success_rate", "mean_success_rate", "mean_noisy_success_rate" or
+    "worst_mean_return" -- which min_delta, patience and stop_on_patience then follow."""
     if tr.collective:
         raise ValueError("fit() runs on one rank: a collective trainer (world > 1 or a process group) would need "
                          "the ranks' log sums merged between the reduce and the finish stage, which is not built")
@@ -587,9 +784,10 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
             raise ValueError("converge must be (column, window >= 1, threshold)")
     if stop_on_converge and converge is None:
         raise ValueError("stop_on_converge needs converge=(column, window, threshold)")
-    val_col, every, patience = val_column_index(val_keep_best), int(validate_every), int(patience)
+    every, patience = int(validate_every), int(patience)
     if validation is not None and not isinstance(validation, ValidationPlan):
         raise ValueError("validation must be a ValidationPlan (tr.validation_plan(heldout_set, ...))")
+    val_table, val_col = val_score(val_keep_best, validation is not None and validation.L > 0)
     if every < 1 or patience < 0:
         raise ValueError("validate_every must be >= 1 and patience >= 0")
     if stop_on_patience and (validation is None or patience < 1):
@@ -607,7 +805,8 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
                         "patience": patience}
 
     def validate():
-        validation.run(tr, val, tr.iteration_index - 1, st.env_steps, st.rows - 1, val_col, min_delta, patience)
+        validation.run(tr, val, tr.iteration_index - 1, st.env_steps, st.rows - 1, val_col, min_delta, patience,
+                       score_table=val_table)
 
     for k in range(iterations):
         tr.iteration()
@@ -716,15 +915,21 @@ def save_checkpoint(tr, path):
                       best_params=host(st.best_params))
         meta["log"] = {"rows": st.rows, "env_steps": st.env_steps, "window": st.window, "settings": st.settings}
         if st.val is not None:  # optional entries: a run never validated writes the file it always did
-            arrays.update(validation_arrays(host(st.val.table[:st.val.rows]), host(st.val.header),
-                                            host(st.val.best_params), host(st.val.objects[:st.val.rows])))
+            v = st.val
+            arrays.update(validation_arrays(host(v.table[:v.rows]), host(v.header), host(v.best_params),
+                                            host(v.objects[:v.rows]),
+                                            host(v.levels[:v.rows]) if v.L else None,
+                                            host(v.robust[:v.rows]) if v.L else None))
             meta["validation"] = validation_meta(st.val.rows, st.val.fingerprint, st.val.object_names, st.val.settings)
     write_checkpoint(path, arrays, meta)
 
 
-def validation_arrays(table, header, best_params, objects) -> Dict[str, np.ndarray]:
-    """The checkpoint's optional validation arrays."""
-    return {"val_table": table, "val_header": header, "val_best_params": best_params, "val_objects": objects}
+def validation_arrays(table, header, best_params, objects, levels=None, robust=None) -> Dict[str, np.ndarray]:
+    """The checkpoint's optional validation arrays (levels / robust: a plan with noise levels)."""
+    out = {"val_table": table, "val_header": header, "val_best_params": best_params, "val_objects": objects}
+    if levels is not None:
+        out.update(val_levels=levels, val_robust=robust)
+    return out
 
 
 def validation_meta(rows: int, fingerprint, object_names, settings) -> Dict[str, Any]:
@@ -739,8 +944,11 @@ def validation_log_of_checkpoint(arrays: Dict[str, np.ndarray], meta: Dict[str, 
     v = meta.get("validation")
     if v is None:
         return None
+    noise = v["fingerprint"].get("noise_levels")  # absent: a plan without levels, or an older file
     return ValidationLog(arrays["val_table"], val_header_dict(arrays["val_header"]), arrays["val_objects"],
-                         v["object_names"], v.get("settings"))
+                         v["object_names"], v.get("settings"), noise_levels=noise,
+                         levels=arrays["val_levels"] if noise is not None else None,
+                         robust=arrays["val_robust"] if noise is not None else None)
 
 
 def load_checkpoint(cls, path, env):
@@ -789,6 +997,9 @@ def load_checkpoint(cls, path, env):
             if val.rows:
                 put(val.table[:val.rows], "val_table")
                 put(val.objects[:val.rows], "val_objects")
+                if val.L:
+                    put(val.levels[:val.rows], "val_levels")
+                    put(val.robust[:val.rows], "val_robust")
             put(val.header, "val_header")
             put(val.best_params, "val_best_params")
     torch.cuda.synchronize(dev)

@@ -1252,6 +1252,114 @@ typedef struct dxrl_pg_val_args {
 int dxrl_pg_val_partial_doubles(int64_t num_objects, int64_t episodes_per_object, int64_t* out);
 int dxrl_pg_val_row(int32_t device, const dxrl_pg_val_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Noise-level validation row of a training run (csrc/dxrl_pg_val_levels.hip): dxrl_pg_val_row
+ * over L noise levels of the same G objects x K episodes in one call.  The records are
+ * level-major: level l, object o, episode k at (l G + o) K + k, E = L G K; level 0 is the
+ * baseline.  One call writes row `row` of three tables and applies keep-best and patience to the
+ * same dxrl_pg_val_header, by dxrl_pg_val_row's rules, on the selected score.
+ *
+ * val[row] (DXRL_PG_VAL_COLS columns): level 0's row, exactly what dxrl_pg_val_row writes for
+ *   level 0's G K records; is_best / since_best follow the selected score.
+ * levels[row][l] (DXRL_PG_VAL_LEVEL_COLS columns, enum dxrl_pg_val_level_col):
+ *   obs_noise_std, dyn_noise_std     level_noise[l], copied
+ *   episodes .. min_object_success_rate
+ *                                    bit for bit the columns of those names dxrl_pg_val_row
+ *                                    writes with its record pointers offset by l G K (the same
+ *                                    1,024-record chunks, workgroups per level, merge order, and
+ *                                    the moments' shift taken from the level's own first record)
+ *   degradation                      success_rate[0] - success_rate[l]
+ *   degradation_percentage           success_rate[0] > 0 ? degradation / success_rate[0] * 100
+ *                                    : 0.0 (f64, in this order; both 0.0 for level 0)
+ * robust[row] (DXRL_PG_VAL_ROBUST_COLS columns, enum dxrl_pg_val_robust_col; sums in level
+ * order, then one division):
+ *   levels                           L
+ *   worst_level, worst_success_rate  the first minimum of success_rate over the levels
+ *   mean_success_rate                over all levels
+ *   mean_noisy_success_rate          over levels 1 .. L-1 (NaN when L == 1)
+ *   max_degradation,                 maxima over the levels of the two degradation columns
+ *   max_degradation_percentage
+ *   worst_mean_return                minimum of mean_return over the levels
+ * object_successes (nullable): i32 [cap][L][G].
+ * Score: score_table 0 -> val[row][score_col], score_col < DXRL_PG_VAL_IS_BEST; score_table 1 ->
+ * robust[row][score_col], score_col < DXRL_PG_VAL_ROBUST_COLS; score_col < 0: keep-best off.
+ * Launches, whatever L: reduce (val_grid(G, K) workgroups x L), finish (one workgroup, one wave
+ * per level), and the copy when params / best_params are given and score_col >= 0.  The same
+ * inputs give the same bytes.
+ * DXRL_E_INVALID before any launch: whatever dxrl_pg_val_row rejects, num_levels outside
+ * [1, DXRL_PG_VAL_MAX_LEVELS], L G K above INT32_MAX, score_table outside {0, 1}, score_col
+ * outside the selected table's score columns, null levels / robust / level_noise, partial_doubles
+ * smaller than dxrl_pg_val_levels_partial_doubles(L, G, K).
+ * ------------------------------------------------------------------------ */
+#define DXRL_PG_VAL_MAX_LEVELS 16
+#define DXRL_PG_VAL_LEVEL_COLS 12
+enum dxrl_pg_val_level_col {
+    DXRL_PG_VAL_LEVEL_OBS_NOISE_STD = 0,
+    DXRL_PG_VAL_LEVEL_DYN_NOISE_STD,
+    DXRL_PG_VAL_LEVEL_EPISODES,
+    DXRL_PG_VAL_LEVEL_SUCCESSES,
+    DXRL_PG_VAL_LEVEL_SUCCESS_RATE,
+    DXRL_PG_VAL_LEVEL_MEAN_RETURN,
+    DXRL_PG_VAL_LEVEL_RETURN_STD,
+    DXRL_PG_VAL_LEVEL_MEAN_LENGTH,
+    DXRL_PG_VAL_LEVEL_MEAN_CONTACTS,
+    DXRL_PG_VAL_LEVEL_MIN_OBJECT_SUCCESS_RATE,
+    DXRL_PG_VAL_LEVEL_DEGRADATION,
+    DXRL_PG_VAL_LEVEL_DEGRADATION_PERCENTAGE,
+    DXRL_PG_VAL_LEVEL_NAMED /* == DXRL_PG_VAL_LEVEL_COLS */
+};
+#define DXRL_PG_VAL_ROBUST_COLS 8
+enum dxrl_pg_val_robust_col {
+    DXRL_PG_VAL_ROBUST_LEVELS = 0,
+    DXRL_PG_VAL_ROBUST_WORST_LEVEL,
+    DXRL_PG_VAL_ROBUST_WORST_SUCCESS_RATE,
+    DXRL_PG_VAL_ROBUST_MEAN_SUCCESS_RATE,
+    DXRL_PG_VAL_ROBUST_MEAN_NOISY_SUCCESS_RATE,
+    DXRL_PG_VAL_ROBUST_MAX_DEGRADATION,
+    DXRL_PG_VAL_ROBUST_MAX_DEGRADATION_PERCENTAGE,
+    DXRL_PG_VAL_ROBUST_WORST_MEAN_RETURN,
+    DXRL_PG_VAL_ROBUST_NAMED /* == DXRL_PG_VAL_ROBUST_COLS */
+};
+
+typedef struct dxrl_pg_val_levels_args {
+    int64_t num_objects;             /* G                                                    */
+    int64_t episodes_per_object;     /* K                                                    */
+    int64_t row;                     /* table row this call writes, 0 <= row < cap           */
+    int64_t cap;                     /* rows of the tables                                   */
+    int64_t iteration;               /* val column 0                                         */
+    int64_t env_steps;               /* val column 1                                         */
+    int64_t train_row;               /* val column 2                                         */
+    int64_t num_params;              /* f32 elements of params / best_params                 */
+    int64_t partial_doubles;         /* f64 elements of partial                              */
+    int32_t score_col;               /* keep-best column of the selected table, < 0: off     */
+    int32_t patience;                /* >= 0; 0: never stops                                 */
+    double min_delta;                /* keep-best margin                                     */
+    double solve_threshold;          /* objects_solved of the main row                       */
+    int32_t num_levels;              /* L, 1 .. DXRL_PG_VAL_MAX_LEVELS                       */
+    int32_t score_table;             /* 0: score_col indexes val[row], 1: robust[row]        */
+    /* device inputs */
+    const double*  ep_return;        /* f64 [L G K]                                          */
+    const int32_t* ep_length;        /* i32 [L G K]                                          */
+    const uint8_t* ep_success;       /* u8  [L G K]                                          */
+    const uint8_t* ep_contacts;      /* u8  [L G K]                                          */
+    const int32_t* status;           /* i32 [1] the episode kernel's status word             */
+    const float*   params;           /* f32 [num_params] (nullable with best_params)         */
+    const double*  level_noise;      /* f64 [L][2] obs std, dyn std                          */
+    /* device scratch and outputs */
+    double*  partial;                /* f64 [partial_doubles] scratch                        */
+    float*   best_params;            /* f32 [num_params] (nullable with params)              */
+    double*  val;                    /* f64 [cap][DXRL_PG_VAL_COLS]                          */
+    double*  levels;                 /* f64 [cap][L][DXRL_PG_VAL_LEVEL_COLS]                 */
+    double*  robust;                 /* f64 [cap][DXRL_PG_VAL_ROBUST_COLS]                   */
+    int32_t* object_successes;       /* i32 [cap][L][G] (nullable)                           */
+    dxrl_pg_val_header* header;
+} dxrl_pg_val_levels_args;
+
+/* f64 elements of dxrl_pg_val_levels_row's `partial` scratch for L levels of G objects x K episodes. */
+int dxrl_pg_val_levels_partial_doubles(int32_t num_levels, int64_t num_objects, int64_t episodes_per_object,
+                                       int64_t* out);
+int dxrl_pg_val_levels_row(int32_t device, const dxrl_pg_val_levels_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
