@@ -5,26 +5,18 @@
 // Two launches on the caller's stream, no host synchronisation between:
 //   k_summary_episodes  a wave per episode row: all the contact_hist traffic (dword loads of the
 //                       row body, byte loads of an unaligned head / tail), a cross-lane reduction
-//                       to (S1, S2, first-five, last-five), then the rules on lane 0.
-//   k_summary_groups    a workgroup per group: strided accumulation over the CSR member list
-//                       (about 32 B per member), then a fixed tree in LDS -- the return moments,
-//                       taken about the group's first return, merge with Chan et al.'s update in
-//                       that fixed order, so group_return is bit-identical from run to run (no
-//                       floating-point atomics).  One extra
-//                       workgroup compacts the tie rows into tie_list in ascending order.
+//                       to (S1, S2, first-five, last-five), then the rules on lane 0
+//                       (failure_word, dxrl_metrics_groups.h).
+//   k_summary_groups    a workgroup per group: the group pass of dxrl_metrics_groups.h on the code
+//                       byte the episode pass left in ep_work.  One extra workgroup compacts the
+//                       tie rows into tie_list in ascending order (compact_rows, dxrl_reduce.h).
 #include "dxrl_hist_row.h"
-#include "dxrl_internal.h"
+#include "dxrl_metrics_groups.h"
 
 namespace dxrl {
 namespace {
 
-constexpr int kSumThreads = 256, kSumWaves = kSumThreads / 64;
-constexpr int kBatch = 4;      // group members gathered per trip of the group pass
-constexpr int kIntStats = 14;  // group_stats slots 0..13 (14, 15 stay zero)
-constexpr int kTieBit = 0x80;  // ep_work: low bits code + 1, bit 7 the tie flag
-
-// metrics.FailureType order (code k <-> list(FailureType)[k])
-enum : int { F_SLIPPAGE = 0, F_UNSTABLE = 1, F_MISALIGNED = 2, F_TIMEOUT = 3, F_DROPPED = 4, F_INSUFFICIENT = 5 };
+constexpr int kSumThreads = kGroupThreads, kSumWaves = kSumThreads / 64;
 
 __global__ __launch_bounds__(kSumThreads) void k_summary_episodes(
     int E, int max_steps, int success_threshold, const int32_t* __restrict__ ep_length,
@@ -38,46 +30,16 @@ __global__ __launch_bounds__(kSumThreads) void k_summary_episodes(
     const int n = len < 0 ? 0 : (len > max_steps ? max_steps : len);  // bytes of the row that are read
     const uint8_t* row = hist + (size_t)e * (size_t)max_steps;
     const HistRow h = hist_row_reduce<false>(row, n, lane);
-    const int s1 = h.s1, s2 = h.s2, f5 = h.f5, l5 = h.l5;
     if (lane != 0) return;
-    int code = -1, tie = 0;
-    if (!ep_success[e]) {
-        const int nc = ep_contacts[e];  // num_contacts == final_contacts of the last step's info
-        if (len >= max_steps) {
-            code = F_TIMEOUT;  // :63-65
-        } else if (nc == 0) {
-            code = F_DROPPED;  // :67-69
-        } else {
-            // :72-83, only when the history has more than 5 entries.  np.var(counts) > 2.0 decided
-            // exactly: n S2 - S1^2 > 2 n^2 (n <= 4096, counts u8: below 2^41)
-            const long long nn = len;
-            const long long num = nn * (long long)s2 - (long long)s1 * (long long)s1;
-            const long long lim = 2 * nn * nn;
-            tie = len > 5 && num == lim;  // np.var's own rounding decides: left to the host
-            const double trend = ((double)l5 / 5.0) - ((double)f5 / 5.0);  // the reference's f64 expression
-            if (len > 5 && num > lim) code = F_UNSTABLE;
-            else if (len > 10 && trend < -1.0) code = F_SLIPPAGE;
-            else if (nc > 0 && nc < success_threshold) code = F_MISALIGNED;  // :86-87
-            else code = F_INSUFFICIENT;                                       // :90-95
-        }
-    }
-    ep_work[e] = (uint8_t)((code + 1) | (tie ? kTieBit : 0));
-    if (ep_code) ep_code[e] = (int8_t)code;
+    const int ok = ep_success[e] != 0;
+    const int nc = ok ? 0 : ep_contacts[e];  // num_contacts == final_contacts of the last step's info
+    const int w = failure_word(len, ok, nc, h.s1, h.s2, h.f5, h.l5, max_steps, success_threshold);
+    ep_work[e] = (uint8_t)w;
+    if (ep_code) ep_code[e] = (int8_t)((w & 0x7f) - 1);
     if (ep_moments) {
         int32_t* m = ep_moments + 4 * (size_t)e;
-        m[0] = s1, m[1] = s2, m[2] = f5, m[3] = l5;
+        m[0] = h.s1, m[1] = h.s2, m[2] = h.f5, m[3] = h.l5;
     }
-}
-
-struct Moments {
-    double n, mean, m2;
-};
-// Chan et al.'s pairwise update (as dxrl_pg_gae merges its advantage moments)
-__device__ __forceinline__ Moments merge(const Moments& a, const Moments& b) {
-    if (b.n == 0.0) return a;
-    if (a.n == 0.0) return b;
-    const double n = a.n + b.n, d = b.mean - a.mean;
-    return Moments{n, a.mean + d * (b.n / n), a.m2 + b.m2 + d * d * (a.n * b.n / n)};
 }
 
 __global__ __launch_bounds__(kSumThreads) void k_summary_groups(
@@ -90,111 +52,13 @@ __global__ __launch_bounds__(kSumThreads) void k_summary_groups(
     __shared__ long long si[kIntStats][kSumThreads];
     __shared__ double sd[3][kSumThreads];
     __shared__ int scan[kSumThreads];
-    const int tid = threadIdx.x;
     if ((int)blockIdx.x == G) {
-        // tie rows in ascending episode order: thread t owns episodes [t c, (t + 1) c)
-        const int c = (E + kSumThreads - 1) / kSumThreads;
-        const int lo = min(tid * c, E), hi = min(lo + c, E);
-        int cnt = 0;
-        for (int e = lo; e < hi; ++e) cnt += (ep_work[e] & kTieBit) != 0;
-        scan[tid] = cnt;
-        __syncthreads();
-        for (int s = 1; s < kSumThreads; s <<= 1) {  // inclusive Hillis-Steele scan
-            const int v = tid >= s ? scan[tid - s] : 0;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
-        int at = scan[tid] - cnt;
-        for (int e = lo; e < hi; ++e)
-            if (ep_work[e] & kTieBit) {
-                if (at < tie_cap) tie_list[at] = e;
-                ++at;
-            }
-        if (tid == kSumThreads - 1) {
-            *tie_count = scan[tid];  // the true count, also when the list overflowed
-            if (scan[tid] > tie_cap) atomicOr(status, 2);
-        }
+        compact_rows<kSumThreads>(E, [=](int e) { return (ep_work[e] & kTieBit) != 0; }, scan, tie_count, tie_list,
+                                  tie_cap, status);
         return;
     }
-    const int g = blockIdx.x;
-    const int lo = group_offsets[g], hi = group_offsets[g + 1];
-    long long acc[kIntStats];
-#pragma unroll
-    for (int k = 0; k < kIntStats; ++k) acc[k] = 0;
-    Moments mo{0.0, 0.0, 0.0};
-    bool bad = lo < 0 || hi < lo || hi > num_members;
-    // The return moments are taken about K, the group's first member's return (as dxrl_pg_gae takes
-    // an env's about its first advantage): with returns of the form -1e6 + small, a running mean
-    // held as an absolute f64 rounds at 1e-10 and costs M2 ~1e-8 relative; about K it does not.
-    double K = 0.0;
-    if (!bad && lo < hi) {
-        const int e0 = group_episodes[lo];
-        if (e0 >= 0 && e0 < E) K = ep_return[e0];
-    }
-    if (!bad) {
-        // kBatch members per trip: their gathers go out together (one memory latency per trip, a big
-        // group is a chain of trips on one workgroup), then they are accumulated in member order
-        for (long long m0 = lo + tid; m0 < hi; m0 += kSumThreads * kBatch) {
-            int ee[kBatch], len_[kBatch], nc_[kBatch], ok_[kBatch], w_[kBatch];
-            double x_[kBatch];
-            bool use[kBatch];
-#pragma unroll
-            for (int b = 0; b < kBatch; ++b) {
-                const long long m = m0 + b * kSumThreads;
-                ee[b] = m < hi ? group_episodes[m] : 0;
-                use[b] = m < hi && ee[b] >= 0 && ee[b] < E;
-                bad |= m < hi && !use[b];
-            }
-#pragma unroll
-            for (int b = 0; b < kBatch; ++b) {
-                const int e = use[b] ? ee[b] : 0;  // E > 0 whenever a member is in range
-                len_[b] = use[b] ? ep_length[e] : 0;
-                nc_[b] = use[b] ? ep_contacts[e] : 0;
-                ok_[b] = use[b] ? ep_success[e] != 0 : 0;
-                w_[b] = use[b] ? ep_work[e] : 0;
-                x_[b] = use[b] ? ep_return[e] : 0.0;
-            }
-#pragma unroll
-            for (int b = 0; b < kBatch; ++b) {
-                if (!use[b]) continue;
-                const long long len = len_[b], nc = nc_[b];
-                const int ok = ok_[b], w = w_[b], code = (w & 0x7f) - 1;
-                acc[0] += 1;
-                acc[1] += ok;
-                acc[2] += len;
-                acc[3] += len * len;
-                acc[4] += nc;
-                acc[5] += ok ? len : 0;
-                acc[6] += ok ? nc : 0;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) acc[7 + k] += code == k;
-                acc[13] += (w & kTieBit) != 0;
-                // Welford step = Chan merge with a single value
-                const double x = x_[b] - K, n1 = mo.n + 1.0, d = x - mo.mean;
-                mo.mean += d / n1;
-                mo.m2 += d * (x - mo.mean);
-                mo.n = n1;
-            }
-        }
-    }
-    if (bad) atomicOr(status, 1);
-#pragma unroll
-    for (int k = 0; k < kIntStats; ++k) si[k][tid] = acc[k];
-    sd[0][tid] = mo.n, sd[1][tid] = mo.mean, sd[2][tid] = mo.m2;
-    __syncthreads();
-    for (int s = kSumThreads / 2; s >= 1; s >>= 1) {  // fixed tree
-        if (tid < s) {
-#pragma unroll
-            for (int k = 0; k < kIntStats; ++k) si[k][tid] += si[k][tid + s];
-            const Moments r = merge(Moments{sd[0][tid], sd[1][tid], sd[2][tid]},
-                                    Moments{sd[0][tid + s], sd[1][tid + s], sd[2][tid + s]});
-            sd[0][tid] = r.n, sd[1][tid] = r.mean, sd[2][tid] = r.m2;
-        }
-        __syncthreads();
-    }
-    if (tid < 16) group_stats[16 * (size_t)g + tid] = tid < kIntStats ? si[tid][0] : 0;
-    if (tid < 3) group_return[3 * (size_t)g + tid] = tid == 1 && sd[0][0] > 0.0 ? K + sd[1][0] : sd[tid][0];
+    metrics_group_pass(blockIdx.x, E, num_members, group_offsets, group_episodes, ep_length, ep_success, ep_contacts,
+                       ep_return, CodeByte{ep_work}, group_stats, group_return, status, si, sd);
 }
 
 }  // namespace

@@ -11,13 +11,15 @@
 //                       thread per episode reads the five words the episode kernel accumulated.
 //   k_failure_groups    a workgroup per (group, mode): strided accumulation over the CSR member
 //                       list, then a fixed tree in LDS.  The property moments are taken about the
-//                       (group, mode)'s first member -- found by a block-wide minimum first -- and
-//                       merged with Chan et al.'s update in that fixed order, so mode_props is
-//                       bit-identical from run to run (no floating-point atomics); min / max are
-//                       exact.  Mode 0's workgroup also writes group_totals; one extra workgroup
-//                       compacts the tie rows into tie_list in ascending order.
+//                       (group, mode)'s first member -- found by a block-wide minimum first -- by
+//                       push and merged with merge (dxrl_moments.h) in that fixed order, so
+//                       mode_props is bit-identical from run to run (no floating-point atomics);
+//                       min / max are exact.  Mode 0's workgroup also writes group_totals; one
+//                       extra workgroup compacts the tie rows into tie_list in ascending order
+//                       (compact_rows, dxrl_reduce.h).
 #include "dxrl_hist_row.h"
-#include "dxrl_internal.h"
+#include "dxrl_moments.h"
+#include "dxrl_reduce.h"
 
 namespace dxrl {
 namespace {
@@ -95,17 +97,6 @@ __global__ __launch_bounds__(kFsThreads) void k_failure_episodes(
     if (ep_confidence) ep_confidence[e] = v.conf;
 }
 
-struct Moments {
-    double n, mean, m2;
-};
-// Chan et al.'s pairwise update (as k_summary_groups merges its return moments)
-__device__ __forceinline__ Moments merge(const Moments& a, const Moments& b) {
-    if (b.n == 0.0) return a;
-    if (a.n == 0.0) return b;
-    const double n = a.n + b.n, d = b.mean - a.mean;
-    return Moments{n, a.mean + d * (b.n / n), a.m2 + b.m2 + d * d * (a.n * b.n / n)};
-}
-
 __global__ __launch_bounds__(kFsThreads) void k_failure_groups(
     int E, int G, int num_members, const int32_t* __restrict__ group_offsets,
     const int32_t* __restrict__ group_episodes, const int32_t* __restrict__ ep_length,
@@ -120,29 +111,8 @@ __global__ __launch_bounds__(kFsThreads) void k_failure_groups(
     const int tid = threadIdx.x;
     if ((int)blockIdx.x == G) {
         if (blockIdx.y != 0) return;
-        // tie rows in ascending episode order: thread t owns episodes [t c, (t + 1) c)
-        const int c = (E + kFsThreads - 1) / kFsThreads;
-        const int lo = min(tid * c, E), hi = min(lo + c, E);
-        int cnt = 0;
-        for (int e = lo; e < hi; ++e) cnt += (ep_work[e] & kFsTie) != 0;
-        scan[tid] = cnt;
-        __syncthreads();
-        for (int s = 1; s < kFsThreads; s <<= 1) {  // inclusive Hillis-Steele scan
-            const int v = tid >= s ? scan[tid - s] : 0;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
-        int at = scan[tid] - cnt;
-        for (int e = lo; e < hi; ++e)
-            if (ep_work[e] & kFsTie) {
-                if (at < tie_cap) tie_list[at] = e;
-                ++at;
-            }
-        if (tid == kFsThreads - 1) {
-            *tie_count = scan[tid];  // the true count, also when the list overflowed
-            if (scan[tid] > tie_cap) atomicOr(status, 2);
-        }
+        compact_rows<kFsThreads>(E, [=](int e) { return (ep_work[e] & kFsTie) != 0; }, scan, tie_count, tie_list,
+                                 tie_cap, status);
         return;
     }
     const int g = blockIdx.x, mode = blockIdx.y;
@@ -206,15 +176,16 @@ __global__ __launch_bounds__(kFsThreads) void k_failure_groups(
             acc[3] += nc;
             acc[4] += nc * nc;
             const double* p = ep_props + 3 * (size_t)e;
-            cnt += 1.0;
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {  // Welford step = Chan merge with a single value
-                const double v = p[q], x = v - K[q], d = x - mean[q];
-                mean[q] += d / cnt;
-                m2[q] += d * (x - mean[q]);
+            for (int q = 0; q < 3; ++q) {
+                const double v = p[q];
+                Moments t{cnt, mean[q], m2[q]};  // the three properties share one count (sn below)
+                push(t, v - K[q]);
+                mean[q] = t.mean, m2[q] = t.m2;
                 mn[q] = fmin(mn[q], v);
                 mx[q] = fmax(mx[q], v);
             }
+            cnt += 1.0;
         }
     }
 #pragma unroll

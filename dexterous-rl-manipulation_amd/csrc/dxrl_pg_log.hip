@@ -19,10 +19,11 @@
 //   k_pg_log_finish   one wave: sums the partials and merges their triples in index order (Chan),
 //                     sums the learner's loss partials, writes the row, and applies the keep-best
 //                     and convergence rules to the header.
-//   k_pg_keep_best    copies params to best_params iff the row's is_best flag is set (read on the
-//                     device).
+//   k_pg_val_keep_best  the conditional copy the validation rows use too (dxrl_keep_best.h):
+//                     params to best_params iff the row's is_best flag is set (read on the device).
 // No floating-point atomics, no tickets, no spin-waits: the launch order is the only ordering.
-#include "dxrl_internal.h"
+// merge and wave_moments are dxrl_moments.h's, wave_sum, quiet_nan and aligned16 dxrl_reduce.h's.
+#include "dxrl_keep_best.h"
 #include "dxrl_moments.h"
 
 namespace dxrl {
@@ -33,7 +34,6 @@ constexpr int kWave = 64;
 constexpr int kLogGroup = 16;          // samples per vector group
 constexpr int kLogMaxBlocks = 1024;    // 4 workgroups per CU on 256 CUs
 constexpr int kLogPartial = 12;        // doubles per workgroup partial
-constexpr int kCopyThreads = 256;
 // partial layout: plain sums, then the two triples' (mean, M2) with the shared count
 enum { P_REW, P_VAL, P_DONE, P_N, P_TMEAN, P_TM2, P_RMEAN, P_RM2, P_ECNT, P_ELEN, P_ESUC, P_ERET };
 static_assert(P_ERET + 1 == kLogPartial, "partial layout");
@@ -44,24 +44,8 @@ inline int64_t log_grid(int64_t M) {
     return blocks < 1 ? 1 : blocks > kLogMaxBlocks ? kLogMaxBlocks : blocks;
 }
 
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// fixed-order wave reductions by lane shuffles (offsets 32, 16, .., 1); lane 0 holds the result
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-    return v;
-}
-__device__ __forceinline__ Moments wave_moments(Moments v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const Moments b{__shfl_down(v.n, o, kWave), __shfl_down(v.mean, o, kWave), __shfl_down(v.m2, o, kWave)};
-        v = merge(v, b);
-    }
-    return v;
-}
-
-// (count, mean, M2) from sums of (x - K) and (x - K)^2
+// (count, mean, M2) from sums of (x - K) and (x - K)^2: this pass accumulates shifted sums, not
+// Welford steps, and converts them once per workgroup
 __device__ __forceinline__ Moments shifted_moments(double c, double K, double s, double s2) {
     return c > 0.0 ? Moments{c, K + s / c, fmax(s2 - s * (s / c), 0.0)} : Moments{0.0, 0.0, 0.0};
 }
@@ -247,25 +231,6 @@ __global__ __launch_bounds__(kWave) void k_pg_log_finish(const FinishArgs f) {
     if (lane < DXRL_PG_LOG_COLS) a.log[a.row * DXRL_PG_LOG_COLS + lane] = out[lane];
 }
 
-// params -> best_params iff the row's is_best flag is set; 16-byte copies where both pointers
-// allow, scalar otherwise and for the tail
-__global__ __launch_bounds__(kCopyThreads) void k_pg_keep_best(const double* __restrict__ flag,
-                                                               const float* __restrict__ params,
-                                                               float* __restrict__ best, int64_t n, int vec) {
-    if (*flag == 0.0) return;
-    const int64_t i = (int64_t)blockIdx.x * kCopyThreads + threadIdx.x;
-    const int64_t n4 = vec ? n / 4 : 0;
-    if (i < n4) reinterpret_cast<float4*>(best)[i] = reinterpret_cast<const float4*>(params)[i];
-    const int64_t j = 4 * n4 + i;  // at most 3 tail elements when vec; every element otherwise
-    if (!vec) {
-        for (int64_t k = 4 * i; k < 4 * i + 4 && k < n; ++k) best[k] = params[k];
-    } else if (j < n) {
-        best[j] = params[j];
-    }
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 }  // namespace dxrl
 
@@ -316,11 +281,9 @@ extern "C" int dxrl_pg_log_row(int32_t device, const dxrl_pg_log_args* args, voi
     hipLaunchKernelGGL(k_pg_log_finish, dim3(1), dim3(kWave), 0, st, f);
     if (int rc = launch_check("k_pg_log_finish")) return rc;
     if (copy) {
-        const int64_t quads = (a.num_params + 3) / 4;
-        hipLaunchKernelGGL(k_pg_keep_best, dim3((unsigned)((quads + kCopyThreads - 1) / kCopyThreads)), dim3(kCopyThreads),
-                           0, st, a.log + a.row * DXRL_PG_LOG_COLS + DXRL_PG_LOG_IS_BEST, a.params, a.best_params,
-                           a.num_params, (int)(aligned16(a.params) && aligned16(a.best_params)));
-        if (int rc = launch_check("k_pg_keep_best")) return rc;
+        if (int rc = launch_keep_best(st, a.log + a.row * DXRL_PG_LOG_COLS + DXRL_PG_LOG_IS_BEST, a.params,
+                                      a.best_params, a.num_params))
+            return rc;
     }
     return DXRL_OK;
 }

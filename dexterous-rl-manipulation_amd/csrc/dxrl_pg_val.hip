@@ -22,7 +22,7 @@
 //                       solved count over the objects, writes the row and the optional
 //                       object_successes row, applies keep-best and patience to the header.
 //   k_pg_val_keep_best  copies params to best_params iff the row's is_best flag is set (read on
-//                       the device).
+//                       the device); dxrl_keep_best.h, the training log's copy too.
 // A single-workgroup path that folds reduce and finish into one launch for small E was not built:
 // it would save one dependent launch (about 5 us) behind an episode kernel of a millisecond.
 // No floating-point atomics, no tickets, no spin-waits: the launch order is the only ordering.

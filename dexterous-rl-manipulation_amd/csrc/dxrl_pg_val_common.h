@@ -1,11 +1,14 @@
 // dxrl_pg_val_common.h -- the record reduction of a validation row, shared by dxrl_pg_val.hip (one
 // set of G x K records) and dxrl_pg_val_levels.hip (L such sets, one per noise level): the body
 // of the reduce workgroup, the per-set part of the finishing wave, the columns both rows share,
-// the keep-best / patience rules of the header, and the conditional parameter copy.  Both
-// translation units run the same code on a set of records, so a level's statistics are the
-// single-set kernel's bit for bit.
+// and the keep-best / patience rules of the header.  Both translation units run the same code on
+// a set of records, so a level's statistics are the single-set kernel's bit for bit.  merge and
+// wave_moments are dxrl_moments.h's; wave_sum, wave_min, quiet_nan and aligned16 dxrl_reduce.h's;
+// the conditional parameter copy (launch_keep_best) dxrl_keep_best.h's.  A record enters the
+// moments by merge(m, {1, x, 0}), not by push: the two round differently, and this form is the
+// contract here.
 #pragma once
-#include "dxrl_internal.h"
+#include "dxrl_keep_best.h"
 #include "dxrl_moments.h"
 
 #include <climits>
@@ -20,7 +23,6 @@ constexpr int kValPerThread = 4;   // consecutive records per thread and pass
 constexpr int kValChunk = kValThreads * kValPerThread;
 constexpr int kValMaxBlocks = 64;  // one partial per lane of the finishing wave
 constexpr int kValPartial = 8;     // doubles per workgroup partial
-constexpr int kCopyThreads = 256;
 enum { V_N, V_MEAN, V_M2, V_LEN, V_SUC, V_SLEN, V_CON, V_PAD };
 static_assert(V_PAD + 1 == kValPartial, "partial layout");
 static_assert(kValMaxBlocks <= kWave, "the finish reads one partial per lane");
@@ -33,36 +35,6 @@ inline int64_t val_grid(int64_t G, int64_t K) {
 }
 // scratch of one set of records: the workgroup partials, then G i32 object counts
 inline int64_t val_partial_doubles(int64_t G) { return (int64_t)kValMaxBlocks * kValPartial + (G + 1) / 2; }
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// fixed-order wave reductions by lane shuffles (offsets 32, 16, .., 1); lane 0 holds the result
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-    return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const int b = __shfl_down(v, o, kWave);
-        v = b < v ? b : v;
-    }
-    return v;
-}
-__device__ __forceinline__ Moments wave_moments(Moments v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const Moments b{__shfl_down(v.n, o, kWave), __shfl_down(v.mean, o, kWave), __shfl_down(v.m2, o, kWave)};
-        v = merge(v, b);
-    }
-    return v;
-}
 
 // One reduce workgroup (block `block` of `blocks`, kValThreads threads) over the E = G K records
 // behind the four pointers: its partial into partial[block], the success counts of its objects
@@ -221,29 +193,6 @@ __device__ __forceinline__ void val_header_rules(dxrl_pg_val_header* h, double* 
     h->since_best = since;
     if (patience > 0 && h->stopped_row < 0 && since >= (int64_t)patience) h->stopped_row = row;
     h->rows_written = row + 1;
-}
-
-// params -> best_params iff the row's is_best flag is set; 16-byte copies where both pointers
-// allow, scalar otherwise and for the tail
-__global__ __launch_bounds__(kCopyThreads) void k_pg_val_keep_best(const double* __restrict__ flag,
-                                                                   const float* __restrict__ params,
-                                                                   float* __restrict__ best, int64_t n, int vec) {
-    if (*flag == 0.0) return;
-    const int64_t i = (int64_t)blockIdx.x * kCopyThreads + threadIdx.x;
-    if (vec && 4 * i + 4 <= n) {
-        reinterpret_cast<float4*>(best)[i] = reinterpret_cast<const float4*>(params)[i];
-    } else {
-        for (int64_t k = 4 * i; k < 4 * i + 4 && k < n; ++k) best[k] = params[k];
-    }
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-inline int launch_keep_best(hipStream_t st, const double* flag, const float* params, float* best, int64_t n) {
-    const int64_t quads = (n + 3) / 4;
-    hipLaunchKernelGGL(k_pg_val_keep_best, dim3((unsigned)((quads + kCopyThreads - 1) / kCopyThreads)),
-                       dim3(kCopyThreads), 0, st, flag, params, best, n, (int)(aligned16(params) && aligned16(best)));
-    return launch_check("k_pg_val_keep_best");
 }
 
 }  // namespace

@@ -17,7 +17,7 @@
 //                           finishing wave on its level; after one barrier thread 0 forms the
 //                           degradation and robust columns in level order in LDS and applies the
 //                           header rules; after a second the workgroup writes the three rows.
-//   k_pg_val_keep_best      the conditional copy of params to best_params.
+//   k_pg_val_keep_best      the conditional copy of params to best_params (dxrl_keep_best.h).
 // L dxrl_pg_val_row calls would be 2 L + 1 dependent launches sharing one header.  No
 // floating-point atomics, no tickets, no spin-waits: the launch order is the only ordering.
 #include "dxrl_pg_val_common.h"
@@ -29,8 +29,6 @@ constexpr int kMaxLevels = DXRL_PG_VAL_MAX_LEVELS;
 static_assert(kMaxLevels * kWave <= 1024, "one wave per level in one workgroup");
 static_assert(DXRL_PG_VAL_LEVEL_NAMED == DXRL_PG_VAL_LEVEL_COLS && DXRL_PG_VAL_ROBUST_NAMED == DXRL_PG_VAL_ROBUST_COLS,
               "column enums");
-
-__device__ __forceinline__ bool dev_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 __global__ __launch_bounds__(kValThreads) void k_pg_val_levels_reduce(
     const double* __restrict__ ep_return, const int32_t* __restrict__ ep_length,
@@ -45,7 +43,7 @@ __global__ __launch_bounds__(kValThreads) void k_pg_val_levels_reduce(
     double* part = partial + (int64_t)blockIdx.y * level_stride;
     int32_t* counts = reinterpret_cast<int32_t*>(part + (int64_t)kValMaxBlocks * kValPartial);
     // uniform over the workgroup, so the barrier inside is reached by all of its threads
-    if (dev_aligned16(ret) && dev_aligned16(len) && dev_aligned16(suc) && dev_aligned16(con)) {
+    if (aligned16(ret) && aligned16(len) && aligned16(suc) && aligned16(con)) {
         val_reduce_block<true>(ret, len, suc, con, GK, G, K, (int64_t)blockIdx.x, (int64_t)gridDim.x, part, counts,
                                wred);
     } else {

@@ -12,12 +12,14 @@
 //                   moving average (E * 8 bytes, at most E * w multiply-adds).  Every reduction is a
 //                   fixed shuffle tree: bit-identical from run to run.
 //   k_study_groups  a workgroup per group over the lane table and a CSR member list: integer sums,
-//                   five Welford accumulators taken about the group's first member, merged with
-//                   Chan et al.'s update in a fixed LDS tree.  One extra workgroup compacts the tie
-//                   lanes into tie_list in ascending order.
+//                   five Welford accumulators taken about the group's first member (push), merged
+//                   with Chan et al.'s update (merge, both dxrl_moments.h) in a fixed LDS tree.
+//                   One extra workgroup compacts the tie lanes into tie_list in ascending order
+//                   (compact_rows, dxrl_reduce.h).
 #include <climits>
 
-#include "dxrl_internal.h"
+#include "dxrl_moments.h"
+#include "dxrl_reduce.h"
 
 namespace dxrl {
 namespace {
@@ -31,24 +33,8 @@ constexpr int kGrpRed = kGrpInts + 2;  // + min / max of E (status bit 3)
 enum : int { L_EPISODES, L_STEPS, L_SUCCESSES, L_FINAL_WINDOW, L_CONV, L_REWARD_CONV, L_LEVEL, L_FLAGS };
 constexpr int kFlagTie = 1, kFlagSkipped = 2;
 
-struct Moments {
-    double n, mean, m2;
-};
-// Chan et al.'s pairwise update (as dxrl_eval_summarize merges its return moments)
-__device__ __forceinline__ Moments merge(const Moments& a, const Moments& b) {
-    if (b.n == 0.0) return a;
-    if (a.n == 0.0) return b;
-    const double n = a.n + b.n, d = b.mean - a.mean;
-    return Moments{n, a.mean + d * (b.n / n), a.m2 + b.m2 + d * d * (a.n * b.n / n)};
-}
-// Welford step = Chan merge with a single value
-__device__ __forceinline__ void push(Moments& m, double x) {
-    const double n1 = m.n + 1.0, d = x - m.mean;
-    m.mean += d / n1;
-    m.m2 += d * (x - m.mean);
-    m.n = n1;
-}
-
+// butterfly reductions of integers (order-free, every lane ends with the result); in this file
+// they stand in front of dxrl_reduce.h's lane-0 forms
 __device__ __forceinline__ int wave_min(int v) {
     for (int s = kWave / 2; s >= 1; s >>= 1) v = min(v, __shfl_xor(v, s));
     return v;
@@ -176,29 +162,9 @@ __global__ __launch_bounds__(kGrpThreads) void k_study_groups(
     __shared__ int scan[kGrpThreads];
     const int tid = threadIdx.x;
     if ((int)blockIdx.x == G) {
-        // tie lanes in ascending row order: thread t owns rows [t c, (t + 1) c)
-        const int c = (L + kGrpThreads - 1) / kGrpThreads;
-        const int lo = min(tid * c, L), hi = min(lo + c, L);
-        int cnt = 0;
-        for (int l = lo; l < hi; ++l) cnt += (lane_ints[(size_t)kLI * l + L_FLAGS] & kFlagTie) != 0;
-        scan[tid] = cnt;
-        __syncthreads();
-        for (int s = 1; s < kGrpThreads; s <<= 1) {  // inclusive Hillis-Steele scan
-            const int v = tid >= s ? scan[tid - s] : 0;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
-        int at = scan[tid] - cnt;
-        for (int l = lo; l < hi; ++l)
-            if (lane_ints[(size_t)kLI * l + L_FLAGS] & kFlagTie) {
-                if (at < tie_cap) tie_list[at] = l;
-                ++at;
-            }
-        if (tid == kGrpThreads - 1) {
-            *tie_count = scan[tid];  // the true count, also when the list overflowed
-            if (scan[tid] > tie_cap) atomicOr(status, 2);
-        }
+        // tie lanes in ascending row order
+        compact_rows<kGrpThreads>(L, [=](int l) { return (lane_ints[(size_t)kLI * l + L_FLAGS] & kFlagTie) != 0; },
+                                  scan, tie_count, tie_list, tie_cap, status);
         return;
     }
     const int g = blockIdx.x;

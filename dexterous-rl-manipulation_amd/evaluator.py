@@ -582,31 +582,42 @@ class _Summary:
         return [v for v in self.__dict__.values() if isinstance(v, torch.Tensor)]
 
 
-def _prepare_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out_hist, success_threshold=3,
-                     tie_cap=None):
-    """Group table upload and output buffers of a summary, made before the episode launch so
-    that nothing but the call itself sits between the episode kernel and the summary launches."""
+def _new_summary(dev, groups, E, ms, entry, args, out_len, out_suc, out_con, success_threshold, tie_cap):
+    """What the three summaries share, made before the episode launch so that nothing but the call
+    itself sits between the episode kernel and the summary launches: the group table and its
+    upload, the flags (status, tie count) and tie-list buffers, the timing event, and the fields
+    every argument struct has.  The caller adds its entry's own buffers and fields."""
     off, mem = group_table(groups)
     G = len(off) - 1
-    t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-    z = lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
     cap = max(1, E) if tie_cap is None else int(tie_cap)
-    s = _Summary(off=off, mem=mem, E=E, ms=ms, d_off=t(off), d_mem=t(mem) if len(mem) else None,
-                 work=z(max(1, E), dt=torch.uint8), code=z(max(1, E), dt=torch.int8),
-                 stats=z(max(1, G), 16, dt=torch.int64), ret=z(max(1, G), 3, dt=torch.float64),
-                 flags=z(2, dt=torch.int32), ties=z(cap, dt=torch.int32), hist=out_hist, length=out_len,
-                 entry="dxrl_eval_summarize")
-    a = N.EvalSummaryArgs()
-    a.total_episodes, a.max_steps, a.success_threshold, a.num_groups = E, ms, success_threshold, G
-    a.num_members, a.tie_cap = len(mem), cap
+    s = _Summary(off=off, mem=mem, E=E, ms=ms, G=G, d_off=torch.from_numpy(off).to(dev),
+                 d_mem=torch.from_numpy(mem).to(dev) if len(mem) else None, flags=_zeros(dev, 2, dt=torch.int32),
+                 ties=_zeros(dev, cap, dt=torch.int32), entry=entry, args=args,
+                 e2=torch.cuda.Event(enable_timing=True))
+    a = args
+    a.total_episodes, a.max_steps, a.success_threshold = E, ms, int(success_threshold)
+    a.num_groups, a.num_members, a.tie_cap = G, len(mem), cap
     a.ep_length, a.ep_success, a.ep_contacts = N.ptr(out_len), N.ptr(out_suc), N.ptr(out_con)
-    a.ep_return, a.contact_hist = N.ptr(out_ret), N.ptr(out_hist)
     a.group_offsets, a.group_episodes = N.ptr(s.d_off), N.ptr(s.d_mem)
+    a.status, a.tie_count, a.tie_list = s.flags.data_ptr(), s.flags.data_ptr() + 4, N.ptr(s.ties)
+    return s, a, max(1, E), max(1, G)
+
+
+def _zeros(dev, *shape, dt):
+    return torch.zeros(*shape, dtype=dt, device=dev)
+
+
+def _prepare_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_ret, out_hist, success_threshold=3,
+                     tie_cap=None):
+    """Group table upload and output buffers of a summary (see ``_new_summary``)."""
+    s, a, e, g = _new_summary(dev, groups, E, ms, "dxrl_eval_summarize", N.EvalSummaryArgs(), out_len, out_suc,
+                              out_con, success_threshold, tie_cap)
+    s.work, s.code = _zeros(dev, e, dt=torch.uint8), _zeros(dev, e, dt=torch.int8)
+    s.stats, s.ret = _zeros(dev, g, 16, dt=torch.int64), _zeros(dev, g, 3, dt=torch.float64)
+    s.hist, s.length = out_hist, out_len
+    a.ep_return, a.contact_hist = N.ptr(out_ret), N.ptr(out_hist)
     a.ep_work, a.ep_code, a.ep_moments = N.ptr(s.work), N.ptr(s.code), None
     a.group_stats, a.group_return = N.ptr(s.stats), N.ptr(s.ret)
-    a.status, a.tie_count, a.tie_list = s.flags.data_ptr(), s.flags.data_ptr() + 4, N.ptr(s.ties)
-    s.e2 = torch.cuda.Event(enable_timing=True)
-    s.args = a
     return s
 
 
@@ -622,7 +633,9 @@ class _PendingSummary:
         self.stream, self.e0, self.e1, self.repeat = stream, e0, e1, repeat
         self.status, self.used, self.outs, self.keep, self.summary = status, used, outs, keep, summary
 
-    def result(self, timing: Optional[Dict] = None) -> EvalSummary:
+    def _finish(self, timing: Optional[Dict], what: str = "group table out of range"):
+        """The head of every result(): waits for the stream, fills ``timing``, checks the episode
+        kernel's and the summary's status, and returns the summary with its flags on the host."""
         self.stream.synchronize()
         s = self.summary
         if timing is not None:
@@ -633,7 +646,11 @@ class _PendingSummary:
         self.keep[0].close()
         flags = s.flags.cpu().numpy()
         if int(flags[0]):
-            raise N.NativeError(f"dxrl_eval_summarize: status {int(flags[0])} (group table out of range)")
+            raise N.NativeError(f"{s.entry}: status {int(flags[0])} ({what})")
+        return s, flags
+
+    def result(self, timing: Optional[Dict] = None) -> EvalSummary:
+        s, flags = self._finish(timing)
         stats, ret, used = s.stats.cpu().numpy(), s.ret.cpu().numpy(), self.used.cpu().numpy()
         nbytes = 4 + flags.nbytes + stats.nbytes + ret.nbytes + used.nbytes
         nt = int(flags[1])
@@ -645,8 +662,7 @@ class _PendingSummary:
             codes, hist, length = s.code[li].cpu().numpy(), s.hist[li].cpu().numpy(), s.length[li].cpu().numpy()
             nbytes += ties.nbytes + codes.nbytes + hist.nbytes + length.nbytes
             unstable = settle_ties(stats, s.off, s.mem, ties, codes, hist, length)
-        G = len(s.off) - 1
-        return EvalSummary(stats[:G], ret[:G], ties, unstable, used, nbytes)
+        return EvalSummary(stats[:s.G], ret[:s.G], ties, unstable, used, nbytes)
 
 
 # ------------------------------------------------------------------ device failure studies
@@ -705,34 +721,19 @@ def _prepare_failure_summary(dev, groups, E, ms, out_len, out_suc, out_con, out_
                              classify_max_steps: int = 200, success_threshold: int = 3, tie_cap=None):
     """Group table, property upload and output buffers of a failure summary, made before the
     episode launch (as ``_prepare_summary``)."""
-    off, mem = group_table(groups)
-    G = len(off) - 1
-    t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-    z = lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
-    cap = max(1, E) if tie_cap is None else int(tie_cap)
+    s, a, e, g = _new_summary(dev, groups, E, ms, "dxrl_failure_summarize", N.FailureSummaryArgs(), out_len, out_suc,
+                              out_con, success_threshold, tie_cap)
     M = N.FAILURE_MODES
-    s = _Summary(off=off, mem=mem, E=E, ms=ms, d_off=t(off), d_mem=t(mem) if len(mem) else None,
-                 d_props=t(np.ascontiguousarray(props, dtype=np.float64).reshape(-1, 3)),
-                 work=z(max(1, E), dt=torch.uint8), stats=z(max(1, G), M, 8, dt=torch.int64),
-                 totals=z(max(1, G), 4, dt=torch.int64), mprops=z(max(1, G), M, 3, 5, dt=torch.float64),
-                 flags=z(2, dt=torch.int32), ties=z(cap, dt=torch.int32), hist=out_hist, length=out_len,
-                 contacts=out_con, classify_max_steps=int(classify_max_steps),
-                 success_threshold=int(success_threshold), entry="dxrl_failure_summarize")
-    a = N.FailureSummaryArgs()
-    a.total_episodes, a.max_steps, a.timeout_steps, a.success_threshold = E, ms, int(classify_max_steps), \
-        int(success_threshold)
-    a.num_groups, a.num_members, a.tie_cap = G, len(mem), cap
-    a.ep_length, a.ep_success, a.ep_contacts = N.ptr(out_len), N.ptr(out_suc), N.ptr(out_con)
+    s.d_props = torch.from_numpy(np.ascontiguousarray(props, dtype=np.float64).reshape(-1, 3)).to(dev)
+    s.work, s.stats = _zeros(dev, e, dt=torch.uint8), _zeros(dev, g, M, 8, dt=torch.int64)
+    s.totals, s.mprops = _zeros(dev, g, 4, dt=torch.int64), _zeros(dev, g, M, 3, 5, dt=torch.float64)
+    s.hist, s.length, s.contacts, s.mom, s.from_history = out_hist, out_len, out_con, out_mom, out_mom is None
+    s.classify_max_steps, s.success_threshold = int(classify_max_steps), int(success_threshold)
+    a.timeout_steps = int(classify_max_steps)
     a.ep_props = N.ptr(s.d_props)
     a.contact_hist, a.hist_moments = (N.ptr(out_hist), None) if out_mom is None else (None, N.ptr(out_mom))
-    a.group_offsets, a.group_episodes = N.ptr(s.d_off), N.ptr(s.d_mem)
     a.ep_work, a.ep_mode, a.ep_confidence = N.ptr(s.work), None, None
     a.mode_stats, a.group_totals, a.mode_props = N.ptr(s.stats), N.ptr(s.totals), N.ptr(s.mprops)
-    a.status, a.tie_count, a.tie_list = s.flags.data_ptr(), s.flags.data_ptr() + 4, N.ptr(s.ties)
-    s.from_history = out_mom is None
-    s.mom = out_mom
-    s.e2 = torch.cuda.Event(enable_timing=True)
-    s.args = a
     return s
 
 
@@ -740,17 +741,7 @@ class _PendingFailureSummary(_PendingSummary):
     """An enqueued episode launch with ``dxrl_failure_summarize`` behind it."""
 
     def result(self, timing: Optional[Dict] = None) -> FailureSummary:
-        self.stream.synchronize()
-        s = self.summary
-        if timing is not None:
-            timing["kernel_ms"] = self.e0.elapsed_time(self.e1) / self.repeat
-            timing["summary_ms"] = self.e1.elapsed_time(s.e2)
-        if int(self.status.item()):
-            raise N.NativeError("dxrl_evaluate: a parity tape ran out or a segment was malformed")
-        self.keep[0].close()
-        flags = s.flags.cpu().numpy()
-        if int(flags[0]):
-            raise N.NativeError(f"dxrl_failure_summarize: status {int(flags[0])} (group table out of range)")
+        s, flags = self._finish(timing)
         stats, totals, mprops = s.stats.cpu().numpy(), s.totals.cpu().numpy(), s.mprops.cpu().numpy()
         used = self.used.cpu().numpy()
         nbytes = 4 + flags.nbytes + stats.nbytes + totals.nbytes + mprops.nbytes + used.nbytes
@@ -766,8 +757,7 @@ class _PendingFailureSummary(_PendingSummary):
                 nbytes += hist.nbytes + length.nbytes + cont.nbytes
                 settle_failure_ties(stats, mprops, s.off, s.mem, ties, hist, length, cont,
                                     s.d_props[li].cpu().numpy(), s.classify_max_steps, s.success_threshold)
-        G = len(s.off) - 1
-        return FailureSummary(stats[:G], totals[:G], mprops[:G], ties, used, s.from_history, nbytes)
+        return FailureSummary(stats[:s.G], totals[:s.G], mprops[:s.G], ties, used, s.from_history, nbytes)
 
 
 # ------------------------------------------------------------------ device robustness studies
@@ -795,31 +785,20 @@ def _prepare_robustness_summary(dev, groups, E, ms, out_len, out_suc, out_con, o
     episode launch (as ``_prepare_summary``).  ``returns=False`` / ``policy_used=False`` leave
     ``group_return`` / the per-lane draw counts on the device (empty arrays in the result): the
     degradation tables read neither, and the draw counts are four bytes per lane."""
-    off, mem = group_table(groups)
-    G = len(off) - 1
+    s, a, _, g = _new_summary(dev, groups, E, ms, "dxrl_robustness_summarize", N.RobustnessSummaryArgs(), out_len,
+                              out_suc, out_con, success_threshold, tie_cap)
+    G = s.G
     base = np.full(G, -1, np.int32) if baseline_group is None else np.asarray(baseline_group, np.int64).reshape(-1)
     if len(base) != G or ((base < -1) | (base >= G)).any():
         raise ValueError(f"baseline_group needs one entry in [-1, {G}) per group")
-    base = base.astype(np.int32)
-    t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-    z = lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
-    cap = max(1, E) if tie_cap is None else int(tie_cap)
-    s = _Summary(off=off, mem=mem, E=E, ms=ms, base=base, d_off=t(off), d_mem=t(mem) if len(mem) else None,
-                 d_base=t(base) if G else None, stats=z(max(1, G), 16, dt=torch.int64),
-                 ret=z(max(1, G), 3, dt=torch.float64), level=z(max(1, G), 4, dt=torch.float64),
-                 flags=z(2, dt=torch.int32), ties=z(cap, dt=torch.int32), entry="dxrl_robustness_summarize",
-                 copy_returns=bool(returns), copy_used=bool(policy_used))
-    a = N.RobustnessSummaryArgs()
-    a.total_episodes, a.max_steps, a.success_threshold, a.num_groups = E, ms, int(success_threshold), G
-    a.num_members, a.tie_cap = len(mem), cap
-    a.ep_length, a.ep_success, a.ep_contacts = N.ptr(out_len), N.ptr(out_suc), N.ptr(out_con)
-    a.ep_return, a.hist_moments = N.ptr(out_ret), N.ptr(out_mom)
-    a.group_offsets, a.group_episodes, a.baseline_group = N.ptr(s.d_off), N.ptr(s.d_mem), N.ptr(s.d_base)
+    s.base = base.astype(np.int32)
+    s.d_base = torch.from_numpy(s.base).to(dev) if G else None
+    s.stats, s.ret = _zeros(dev, g, 16, dt=torch.int64), _zeros(dev, g, 3, dt=torch.float64)
+    s.level = _zeros(dev, g, 4, dt=torch.float64)
+    s.copy_returns, s.copy_used = bool(returns), bool(policy_used)
+    a.ep_return, a.hist_moments, a.baseline_group = N.ptr(out_ret), N.ptr(out_mom), N.ptr(s.d_base)
     a.group_stats, a.group_return, a.level_table = N.ptr(s.stats), N.ptr(s.ret), N.ptr(s.level)
     a.ep_code = None
-    a.status, a.tie_count, a.tie_list = s.flags.data_ptr(), s.flags.data_ptr() + 4, N.ptr(s.ties)
-    s.e2 = torch.cuda.Event(enable_timing=True)
-    s.args = a
     return s
 
 
@@ -832,19 +811,8 @@ class _PendingRobustnessSummary(_PendingSummary):
         return self.outs[4]
 
     def result(self, timing: Optional[Dict] = None) -> RobustnessSummary:
-        self.stream.synchronize()
-        s = self.summary
-        if timing is not None:
-            timing["kernel_ms"] = self.e0.elapsed_time(self.e1) / self.repeat
-            timing["summary_ms"] = self.e1.elapsed_time(s.e2)
-        if int(self.status.item()):
-            raise N.NativeError("dxrl_evaluate: a parity tape ran out or a segment was malformed")
-        self.keep[0].close()
-        flags = s.flags.cpu().numpy()
-        if int(flags[0]):
-            raise N.NativeError(f"dxrl_robustness_summarize: status {int(flags[0])} (group table or baseline "
-                                "out of range)")
-        G = len(s.off) - 1
+        s, flags = self._finish(timing, "group table or baseline out of range")
+        G = s.G
         stats, level = s.stats.cpu().numpy(), s.level.cpu().numpy()
         ret = s.ret.cpu().numpy()[:G] if s.copy_returns else np.zeros((0, 3))
         used = self.used.cpu().numpy() if s.copy_used else np.zeros(0, np.int32)

@@ -169,9 +169,14 @@ def test_zero_episodes_and_constant_targets_give_nan(N):
     assert g["is_best"] == 0.0 and math.isnan(g["window_mean"])  # a NaN score is never best, never converges
 
 
-def scripted(N, scores, episodes, rewards, num_params=0):
+def uniform_tag(r, params):
+    params.fill_(float(r + 1))
+
+
+def scripted(N, scores, episodes, rewards, num_params=0, tag=uniform_tag):
     """A harness whose row r scores scores[r] (mean_return) over episodes[r] episodes, with
-    mean_step_reward rewards[r]; `play(r, **rules)` uploads row r's inputs and makes the call."""
+    mean_step_reward rewards[r]; `play(r, **rules)` uploads row r's inputs (params tagged by
+    `tag(r, params)`) and makes the call."""
     n, T = 16, 2
     d = inputs(n, T, seed=9)
     h = Harness(N, d, cap=len(scores), num_params=num_params)
@@ -185,7 +190,7 @@ def scripted(N, scores, episodes, rewards, num_params=0):
         h.t["ep_sum_return"][:n].copy_(torch.from_numpy(ret))
         h.t["rew"][:n * T].fill_(float(rewards[r]))
         if h.params is not None:
-            h.params.fill_(float(r + 1))  # the tag of row r
+            tag(r, h.params)  # the tag of row r
         return h.call(r, **rules)
     return h, play
 
@@ -211,6 +216,36 @@ def test_keep_best_copies_exactly_the_expected_rows(N):
     h.params.fill_(99.0)
     table = h.call(6)
     assert table[6, L.IS_BEST] == 0.0 and torch.all(h.best == tag) and h.head()["best_row"] == 5
+
+
+@pytest.mark.parametrize("aligned", [True, False])
+@pytest.mark.parametrize("num_params", [1, 3, 4, 5, 1031])
+def test_keep_best_copies_every_element_and_nothing_beside(N, num_params, aligned):
+    """The copy works a quad of floats per thread: fewer than a quad, a tail of three, exactly one
+    quad, one over, and many quads with a tail of three; on 16-byte aligned params / best_params
+    (16-byte copies of whole quads) and on views one float in (scalar copies).  Every element
+    carries its own tag, and a guard element stands on each side of best_params."""
+    GUARD, OLD = -777.0, -1.0
+    scores, episodes = [1.0, 0.5, 2.0], [4, 4, 4]
+    want_rows, _, _ = L.series_rules(scores, episodes, 1, [0.0] * 3, 1, 1e9)
+    assert want_rows == [0, 2]
+    h, play = scripted(N, scores, episodes, [0.0] * 3,
+                       tag=lambda r, p: p.copy_(1000.0 * (r + 1) + torch.arange(p.numel(), device=p.device)))
+    dev = torch.device("cuda:0")
+    lead = 4 if aligned else 1  # floats in front of the views: 16 bytes or 4
+    h.params = torch.zeros(lead + num_params, device=dev)[lead:]
+    store = torch.full((lead + num_params + 1,), GUARD, device=dev)
+    h.best = store[lead:lead + num_params]
+    h.best.fill_(OLD)
+    assert (h.params.data_ptr() % 16 == 0) == aligned and (h.best.data_ptr() % 16 == 0) == aligned
+    want = torch.full((num_params,), OLD, device=dev)
+    for r in range(len(scores)):
+        table = play(r, score_col=L.IDX["mean_return"])
+        assert table[r, L.IS_BEST] == float(r in want_rows), r
+        if r in want_rows:
+            want = h.params.clone()  # row r's tags, every element its own
+        assert torch.equal(h.best, want), r
+        assert torch.all(store[:lead] == GUARD) and store[lead + num_params] == GUARD, r
 
 
 def test_convergence_is_strict_and_sticks(N):
