@@ -154,7 +154,8 @@ class EvalArgs(C.Structure):
                 ("total_episodes", C.c_int32), ("lane_segments", C.c_void_p), ("segments", C.c_void_p),
                 ("mean_action", C.c_void_p), ("exploration_noise", C.c_double), ("policy_tape", C.c_void_p),
                 ("policy_stride", C.c_int64), ("noise_tape", C.c_void_p), ("reset_tape", C.c_void_p),
-                ("policy_seed", C.c_uint64), ("noise_seed", C.c_uint64), ("reset_seed", C.c_uint64)] + \
+                ("policy_seed", C.c_uint64), ("noise_seed", C.c_uint64), ("reset_seed", C.c_uint64),
+                ("stream_period", C.c_int64)] + \
                [(k, C.c_void_p) for k in ("ep_return", "ep_length", "ep_success", "ep_contacts", "contact_hist",
                                           "policy_used", "status", "obs_traj", "act_traj", "work_queue",
                                           "hist_moments")]
@@ -279,11 +280,24 @@ class PgValLevelsArgs(C.Structure):
                                           "object_successes", "header")]
 
 
+# enum dxrl_pg_val_paired_col: the per-level paired table of dxrl_pg_val_paired_row, in table order
+PG_VAL_PAIRED_COLUMNS = ("pairs", "lost", "gained", "both_success", "both_fail", "mean_return_diff",
+                         "return_diff_std", "return_diff_stderr", "mean_length_diff", "paired_degradation",
+                         "paired_degradation_stderr", "mcnemar", "objects_with_loss", "max_object_lost")
+PG_VAL_PAIRED_COLS = len(PG_VAL_PAIRED_COLUMNS)  # DXRL_PG_VAL_PAIRED_COLS
+
+
+class PgValPairedArgs(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("num_objects", "episodes_per_object", "row", "cap", "partial_doubles")] + \
+               [("num_levels", C.c_int32), ("reserved", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("ep_return", "ep_length", "ep_success", "partial", "paired", "object_lost")]
+
+
 # the structs added after tests/test_native_abi.py fixed its list: (C name, mirror), sized against
 # include/dxrl.h by the tests of the layers that use them
 LATER_STRUCTS = (("dxrl_pg_log_args", PgLogArgs), ("dxrl_pg_log_header", PgLogHeader),
                  ("dxrl_pg_val_args", PgValArgs), ("dxrl_pg_val_header", PgValHeader),
-                 ("dxrl_pg_val_levels_args", PgValLevelsArgs))
+                 ("dxrl_pg_val_levels_args", PgValLevelsArgs), ("dxrl_pg_val_paired_args", PgValPairedArgs))
 
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
@@ -344,6 +358,8 @@ _SIGS = {
     "dxrl_pg_val_row": (C.c_int, [_I32, C.POINTER(PgValArgs), _P]),
     "dxrl_pg_val_levels_partial_doubles": (C.c_int, [_I32, _I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_val_levels_row": (C.c_int, [_I32, C.POINTER(PgValLevelsArgs), _P]),
+    "dxrl_pg_val_paired_partial_doubles": (C.c_int, [_I32, _I64, _I64, C.POINTER(_I64)]),
+    "dxrl_pg_val_paired_row": (C.c_int, [_I32, C.POINTER(PgValPairedArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

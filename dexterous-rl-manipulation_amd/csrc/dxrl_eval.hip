@@ -601,6 +601,8 @@ extern "C" int dxrl_evaluate(dxrl_env* env, const dxrl_eval_args* args, void* st
                  "hist_moments packs its sums for max_steps <= %d, got %d", kHistMomentsMaxSteps, a.max_steps);
     const bool tape = a.policy_tape != nullptr;
     DXRL_REQUIRE(!tape || a.policy_stride >= 0, "bad policy tape stride");
+    DXRL_REQUIRE(a.stream_period == 0, "stream_period is built for dxrl_evaluate_mlp only, got %lld",
+                 (long long)a.stream_period);
     EvalParams p{weights_of(env->cfg),
                  env->cfg.max_episode_steps,
                  env->cfg.reward_type == DXRL_REWARD_DENSE,

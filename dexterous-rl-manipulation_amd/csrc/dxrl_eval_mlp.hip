@@ -44,7 +44,9 @@ constexpr int kEmW1p = kIn + 16, kEmW3p = kH + 16, kEmXp = kIn + 16;  // LDS pit
 constexpr int kEmObsP = 48, kEmMuP = 17;                              // f32 staging row, mu row
 constexpr uint32_t kEvalObsBlock = 1u;  // 4th Philox counter word of the observation-noise blocks (dynamics: 0)
 
-template <int kMode>
+// kPeriod: the launch has a stream period (dxrl_eval_args.stream_period > 0).  Without one the
+// kernel is the code it was before the period existed.
+template <int kMode, bool kPeriod = false>
 __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curriculum* __restrict__ curricula,
                                                               EvalParams p, EvalMlpWeights w,
                                                               int32_t* __restrict__ queue) {
@@ -63,6 +65,14 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
     const int sa = s < kD ? s : 0;
     const int s2 = s < DXRL_RESET_EXTRA ? s : 0;
     const bool ntape = a.noise_tape != nullptr;
+    // stream period P > 0: the device streams of lane, segment and record i are keyed by i % P
+    // (the entry point refuses the tapes then).  Taken once per lane, segment and episode in part A.
+    // The three indices are i32 counts, so the entry point launches a period above INT32_MAX,
+    // which leaves every index as it is, as no period, and the modulo is a 32-bit one.
+    const uint32_t period = kPeriod ? (uint32_t)a.stream_period : 0u;
+    const auto keyed = [&](int64_t i) __attribute__((always_inline)) {
+        return kPeriod ? (int64_t)((uint32_t)i % period) : i;
+    };
 
     // ---- weights, once per launch
     bf16x8 w2[4][kH / 32];  // this wave's L2 columns 64 wave .. + 63 as four 16-column tiles
@@ -178,7 +188,7 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
                 pcur = 0;
                 pctr = 0;
                 if (kMode == kMlpTape) ptape = a.policy_tape + (int64_t)ln * a.policy_stride;
-                if (kMode == kMlpDevice) env_key(a.policy_seed, ln, pk0, pk1);
+                if (kMode == kMlpDevice) env_key(a.policy_seed, keyed(ln), pk0, pk1);
                 si = a.lane_segments[ln];
                 s1 = a.lane_segments[ln + 1];
                 phase = kNeedSeg;
@@ -221,7 +231,7 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
                     navail = sg.noise_count;
                     ncur = 0;
                 } else {
-                    env_key(a.noise_seed, si, nk0, nk1);
+                    env_key(a.noise_seed, keyed(si), nk0, nk1);
                     nctr = 0;
                     octr = 0;
                 }
@@ -267,7 +277,7 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
                     v2 = has2 ? a.reset_tape[rec * kReset + kD + s2] : cst2;
                 } else {
                     uint32_t rk0, rk1;
-                    env_key(a.reset_seed, rec, rk0, rk1);
+                    env_key(a.reset_seed, keyed(rec), rk0, rk1);
                     u1 = -0.1 + (0.1 - -0.1) * reset_uniform_at(sa, rk0, rk1, 0);
                     v2 = has2 ? lo2 + (hi2 - lo2) * reset_uniform_at(kD + s2, rk0, rk1, 0) : cst2;
                 }
@@ -551,6 +561,9 @@ extern "C" int dxrl_evaluate_mlp(dxrl_env* env, const dxrl_eval_args* args, cons
     DXRL_REQUIRE(stochastic || !tape, "a policy tape was given in deterministic mode (action_std == NULL takes no draws)");
     DXRL_REQUIRE(!tape || a.policy_stride >= 0, "bad policy tape stride");
     DXRL_REQUIRE(a.work_queue, "null work_queue (device i32[1] scratch of this launch)");
+    DXRL_REQUIRE(a.stream_period >= 0, "stream_period must be >= 0, got %lld", (long long)a.stream_period);
+    DXRL_REQUIRE(a.stream_period == 0 || (!a.policy_tape && !a.noise_tape && !a.reset_tape),
+                 "stream_period keys the device Philox streams: it cannot be combined with a parity tape");
     EvalParams p{weights_of(env->cfg),
                  env->cfg.max_episode_steps,
                  env->cfg.reward_type == DXRL_REWARD_DENSE,
@@ -571,10 +584,15 @@ extern "C" int dxrl_evaluate_mlp(dxrl_env* env, const dxrl_eval_args* args, cons
     const int64_t resident = cus > 0 ? cus : 256;
     if (blocks > resident) blocks = resident;
     const dim3 grid((unsigned)blocks), block(kEvalThreads);
-    if (!stochastic)
+    const bool period = a.stream_period > 0 && a.stream_period <= (int64_t)INT32_MAX;  // no tape then (above)
+    if (!stochastic && period)
+        hipLaunchKernelGGL((k_eval_mlp<kMlpDet, true>), grid, block, 0, st, env->curricula, p, w, a.work_queue);
+    else if (!stochastic)
         hipLaunchKernelGGL(k_eval_mlp<kMlpDet>, grid, block, 0, st, env->curricula, p, w, a.work_queue);
     else if (tape)
         hipLaunchKernelGGL(k_eval_mlp<kMlpTape>, grid, block, 0, st, env->curricula, p, w, a.work_queue);
+    else if (period)
+        hipLaunchKernelGGL((k_eval_mlp<kMlpDevice, true>), grid, block, 0, st, env->curricula, p, w, a.work_queue);
     else
         hipLaunchKernelGGL(k_eval_mlp<kMlpDevice>, grid, block, 0, st, env->curricula, p, w, a.work_queue);
     return launch_check("k_eval_mlp");

@@ -6,7 +6,8 @@
 // wave_moments are dxrl_moments.h's; wave_sum, wave_min, quiet_nan and aligned16 dxrl_reduce.h's;
 // the conditional parameter copy (launch_keep_best) dxrl_keep_best.h's.  A record enters the
 // moments by merge(m, {1, x, 0}), not by push: the two round differently, and this form is the
-// contract here.
+// contract here.  dxrl_pg_val_paired.hip takes the chunking constants, val_grid and the scratch
+// size from here: its pairs are reduced in the chunks and the order of the records.
 #pragma once
 #include "dxrl_keep_best.h"
 #include "dxrl_moments.h"

@@ -30,6 +30,14 @@ __device__ __forceinline__ int wave_min(int v) {
     }
     return v;
 }
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int b = __shfl_down(v, o, 64);
+        v = b > v ? b : v;
+    }
+    return v;
+}
 
 // The flagged rows of [0, rows) listed in ascending order by one workgroup of NT threads: thread t
 // owns rows [t c, (t + 1) c), counts its flagged rows (first(r), called once per row), an inclusive

@@ -293,20 +293,21 @@ class EpisodeProgram:
             host_noise: bool = True, device_seed: int = 0, keep_history: Optional[bool] = None,
             repeat: int = 1, timing: Optional[Dict] = None, trajectories: bool = False,
             groups: Optional[Sequence[Sequence[int]]] = None, summary: str = "metrics",
-            summary_options: Optional[Dict] = None, hist_moments: bool = False):
+            summary_options: Optional[Dict] = None, hist_moments: bool = False, stream_period: int = 0):
         """Launch the plan (``repeat`` back-to-back launches; ``timing['kernel_ms']`` =
         HIP-event time per launch on the launch stream).  With ``groups`` (episode-index lists)
         the records are reduced on the device and an ``EvalSummary`` comes back instead of
-        ``EvalRecords`` (``timing['summary_ms']`` = event time of the two summary launches)."""
+        ``EvalRecords`` (``timing['summary_ms']`` = event time of the two summary launches).
+        ``stream_period``: see ``launch``."""
         return self.launch(prog, policy_tapes, host_resets, host_noise, device_seed, keep_history, repeat,
-                           trajectories, groups=groups, summary=summary,
-                           summary_options=summary_options, hist_moments=hist_moments).result(timing)
+                           trajectories, groups=groups, summary=summary, summary_options=summary_options,
+                           hist_moments=hist_moments, stream_period=stream_period).result(timing)
 
     def launch(self, prog: _PolicyProgram, policy_tapes: Optional[np.ndarray] = None, host_resets: bool = True,
                host_noise: bool = True, device_seed: int = 0, keep_history: Optional[bool] = None, repeat: int = 1,
                trajectories: bool = False, stream: Optional[torch.cuda.Stream] = None,
                groups: Optional[Sequence[Sequence[int]]] = None, summary: str = "metrics",
-               summary_options: Optional[Dict] = None, hist_moments: bool = False):
+               summary_options: Optional[Dict] = None, hist_moments: bool = False, stream_period: int = 0):
         """Enqueue the plan on ``stream`` (default: the device's current stream) without waiting;
         ``.result()`` synchronises and returns the records.  Every launch owns its buffers,
         including the work-queue counter, so launches on different streams may overlap.
@@ -322,9 +323,22 @@ class EpisodeProgram:
         ``returns`` / ``policy_used`` = False to leave those tables on the device), which
         reads the moments alone, and ``.result()`` returns a ``RobustnessSummary``; its
         ``keep_history`` defaults to False (every other launch: True), and True writes the
-        history beside the moments."""
+        history beside the moments.
+        ``stream_period=P`` (the MLP actor with device streams only: no ``host_resets``,
+        ``host_noise`` or ``policy_tapes``) keys the device streams of lane, segment and record i
+        by i % P, so a level-major plan of one-episode lanes with P lanes per level runs every
+        level on the episodes of a P-lane launch of that level alone (common random numbers)."""
         if summary not in ("metrics", "failure", "robustness"):
             raise ValueError(f"unknown summary kind {summary!r}")
+        stream_period = int(stream_period)
+        if stream_period < 0:
+            raise ValueError(f"stream_period must be >= 0, got {stream_period}")
+        if stream_period:
+            if host_resets or host_noise or policy_tapes is not None:
+                raise ValueError("stream_period keys the device streams: it cannot be combined with host_resets, "
+                                 "host_noise or policy_tapes")
+            if prog.kind != N.EVAL_POLICY_MLP:
+                raise ValueError("stream_period is built for the MLP actor's episode kernel only")
         failure = groups is not None and summary == "failure"
         robust = groups is not None and summary == "robustness"
         if keep_history is None:
@@ -377,6 +391,7 @@ class EpisodeProgram:
         a.policy_used, a.status = N.ptr(used), N.ptr(status)
         a.obs_traj, a.act_traj, a.work_queue = N.ptr(o_traj), N.ptr(a_traj), N.ptr(queue)
         a.hist_moments = N.ptr(out_mom)
+        a.stream_period = stream_period
         mlp_t = ()
         if prog.kind == N.EVAL_POLICY_MLP:
             if prog.draws == 0 and policy_tapes is not None:

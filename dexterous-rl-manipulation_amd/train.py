@@ -52,6 +52,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                    help="observation-noise levels of the validation sweep")
     p.add_argument("--val-dyn-noise", type=float, nargs="+", default=None, metavar="S",
                    help="dynamics-noise levels of the validation sweep")
+    p.add_argument("--val-common-random-numbers", action="store_true",
+                   help="every noise level replays the baseline's episodes; logs the paired table")
     p.add_argument("--patience", type=int, default=0, metavar="P")
     p.add_argument("--envs", type=int, default=None, help="envs (default: the workload's, 4096 with --config)")
     p.add_argument("--horizon", type=int, default=200)
@@ -95,6 +97,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(str(e))
     if a.val_keep_best in _VAL_ROBUST_SCORE_COLUMNS and a.val_noise_levels is None:
         p.error(f"--val-keep-best {a.val_keep_best} needs --val-obs-noise / --val-dyn-noise")
+    if a.val_common_random_numbers and a.val_noise_levels is None:
+        p.error("--val-common-random-numbers needs --val-obs-noise / --val-dyn-noise")
     if a.config_name is None and a.config is None:
         a.config_name = "easy"
     return a
@@ -145,7 +149,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     if a.validate_every:
         from .evaluation import HeldOutObjectSet
         plan = tr.validation_plan(HeldOutObjectSet(base_config), episodes_per_object=a.val_episodes,
-                                  seed=a.val_seed, max_steps=a.max_steps, noise_levels=a.val_noise_levels)
+                                  seed=a.val_seed, max_steps=a.max_steps, noise_levels=a.val_noise_levels,
+                                  common_random_numbers=a.val_common_random_numbers)
         kw = dict(validation=plan, validate_every=a.validate_every, val_keep_best=a.val_keep_best,
                   patience=a.patience, stop_on_patience=bool(a.patience and a.poll_every))
     log = tr.fit(a.iterations, keep_best=a.keep_best, min_episodes=a.min_episodes, converge=a.converge,

@@ -23,7 +23,11 @@ checkpoint carries the validation tables and the plan's fingerprint as optional 
 A plan built with ``noise_levels`` validates under every (obs_std, dyn_std) level in the one
 episode launch, and ``dxrl_pg_val_levels_row`` (csrc/dxrl_pg_val_levels.hip) writes the clean
 row, a row per level with the degradation columns, and a row of scores over the levels
-(worst / mean success rate, worst mean return) that keep-best and patience may follow.
+(worst / mean success rate, worst mean return) that keep-best and patience may follow.  With
+``common_random_numbers`` the episode launch runs with ``stream_period = G K``, so every level
+replays the baseline's episodes under its own noise scale, and ``dxrl_pg_val_paired_row``
+(csrc/dxrl_pg_val_paired.hip) adds a paired table: per level the episodes lost and gained against
+the baseline and the mean and error of the per-episode return difference.
 """
 from __future__ import annotations
 
@@ -55,6 +59,8 @@ VAL_LEVEL_COLUMNS = N.PG_VAL_LEVEL_COLUMNS
 VAL_LEVEL_COLS = N.PG_VAL_LEVEL_COLS
 VAL_ROBUST_COLUMNS = N.PG_VAL_ROBUST_COLUMNS
 VAL_ROBUST_COLS = N.PG_VAL_ROBUST_COLS
+VAL_PAIRED_COLUMNS = N.PG_VAL_PAIRED_COLUMNS
+VAL_PAIRED_COLS = N.PG_VAL_PAIRED_COLS
 # columns of the robust row the validation keep-best may read (a plan with noise levels)
 _VAL_ROBUST_SCORE_COLUMNS = ("worst_success_rate", "mean_success_rate", "mean_noisy_success_rate",
                              "worst_mean_return")
@@ -214,11 +220,16 @@ class ValidationLog:
     ``levels`` (f64 [rows][L][12], ``level_column(name)`` -> [rows][L]), ``robust`` (f64 [rows][8],
     ``robust_column(name)``), ``level_results(row)``, and ``object_successes`` becomes
     [rows][L][objects]; the main table is then level 0, the clean curve.  Without levels these
-    are None."""
+    are None.
+
+    A plan with common random numbers across the levels adds ``paired`` (f64 [rows][L][14],
+    ``paired_column(name)`` -> [rows][L]: every level's episodes paired with the baseline's) and
+    ``object_lost`` (i32 [rows][L][objects]: the lost pairs of each object).  Without it these are
+    None."""
 
     def __init__(self, table=None, header: Optional[Dict[str, Any]] = None, object_successes=None,
                  object_names=(), settings: Optional[Dict[str, Any]] = None, _pending=None, noise_levels=None,
-                 levels=None, robust=None):
+                 levels=None, robust=None, paired=None, object_lost=None):
         self._pending = _pending
         self.object_names = list(object_names)
         self.noise_levels = None if noise_levels is None else [(float(o), float(d)) for o, d in noise_levels]
@@ -231,6 +242,10 @@ class ValidationLog:
             np.array(levels, dtype=np.float64).reshape(-1, L, VAL_LEVEL_COLS)
         self._robust = None if robust is None or not L else \
             np.array(robust, dtype=np.float64).reshape(-1, VAL_ROBUST_COLS)
+        self._paired = None if paired is None or not L else \
+            np.array(paired, dtype=np.float64).reshape(-1, L, VAL_PAIRED_COLS)
+        self._object_lost = None if object_lost is None or self._paired is None else \
+            np.array(object_lost, dtype=np.int32).reshape(-1, L, len(self.object_names))
         self.settings = dict(settings or {})
 
     @property
@@ -245,7 +260,9 @@ class ValidationLog:
             self._header = val_header_dict(host_header.numpy())
             self._objects = host_objects[:rows].numpy().copy()
             if more:
-                self._levels, self._robust = (t[:rows].numpy().copy() for t in more)
+                self._levels, self._robust = (t[:rows].numpy().copy() for t in more[:2])
+            if len(more) > 2:
+                self._paired, self._object_lost = (t[:rows].numpy().copy() for t in more[2:])
             self._pending = None
 
     @property
@@ -276,6 +293,26 @@ class ValidationLog:
         """f64 [rows][8] (VAL_ROBUST_COLUMNS), or None without noise levels."""
         self._resolve()
         return self._robust
+
+    @property
+    def paired(self) -> Optional[np.ndarray]:
+        """f64 [rows][L][14] (VAL_PAIRED_COLUMNS), or None without common random numbers."""
+        self._resolve()
+        return self._paired
+
+    @property
+    def object_lost(self) -> Optional[np.ndarray]:
+        """i32 [rows][L][objects]: per object, the episodes the baseline solved and the level did
+        not; None without common random numbers."""
+        self._resolve()
+        return self._object_lost
+
+    def paired_column(self, name: str) -> np.ndarray:
+        """[rows][L]: one column of the paired rows."""
+        if self.paired is None:
+            raise ValueError("this validation has no paired table (validation_plan(..., noise_levels=..., "
+                             "common_random_numbers=True))")
+        return self.paired[:, :, VAL_PAIRED_COLUMNS.index(name)]
 
     def _need_levels(self):
         if not self.num_levels:
@@ -354,6 +391,11 @@ class ValidationLog:
             out["noise_levels"] = self.num_levels
             for name in ("worst_success_rate", "mean_success_rate", "max_degradation_percentage"):
                 out[f"final_{name}"] = float(self.robust_column(name)[-1])
+        if self.paired is not None:
+            out["common_random_numbers"] = True
+            if self.num_levels > 1:  # over the noisy levels of the last row
+                out["final_max_lost"] = float(self.paired_column("lost")[-1, 1:].max())
+                out["final_min_mean_return_diff"] = float(self.paired_column("mean_return_diff")[-1, 1:].min())
         return out
 
     def to_dict(self) -> Dict[str, Any]:
@@ -366,6 +408,10 @@ class ValidationLog:
             out["level_columns"], out["robust_columns"] = list(VAL_LEVEL_COLUMNS), list(VAL_ROBUST_COLUMNS)
             out["levels"] = [[[_enc(x) for x in lv] for lv in row] for row in self.levels.tolist()]
             out["robust"] = [[_enc(x) for x in row] for row in self.robust.tolist()]
+        if self.paired is not None:  # a validation without common random numbers serialises as it always did
+            out["paired_columns"] = list(VAL_PAIRED_COLUMNS)
+            out["paired"] = [[[_enc(x) for x in lv] for lv in row] for row in self.paired.tolist()]
+            out["object_lost"] = self.object_lost.tolist()
         return out
 
     @classmethod
@@ -383,8 +429,15 @@ class ValidationLog:
                 raise ValueError("not a validation log with this build's level / robust columns")
             levels = np.array([[[_dec(x) for x in lv] for lv in row] for row in d["levels"]], dtype=np.float64)
             robust = np.array([[_dec(x) for x in row] for row in d["robust"]], dtype=np.float64)
+        paired = object_lost = None
+        if noise is not None and d.get("paired") is not None:  # absent without common random numbers
+            if list(d.get("paired_columns", [])) != list(VAL_PAIRED_COLUMNS):
+                raise ValueError("not a validation log with this build's paired columns")
+            paired = np.array([[[_dec(x) for x in lv] for lv in row] for row in d["paired"]], dtype=np.float64)
+            object_lost = d["object_lost"]
         return cls(table, {k: _dec(v) for k, v in d["header"].items()}, d["object_successes"], d["object_names"],
-                   d.get("settings"), noise_levels=noise, levels=levels, robust=robust)
+                   d.get("settings"), noise_levels=noise, levels=levels, robust=robust, paired=paired,
+                   object_lost=object_lost)
 
 
 def val_header_dict(raw: np.ndarray) -> Dict[str, Any]:
@@ -450,21 +503,28 @@ class ValidationPlan:
     and segment tables, record buffers, work-queue counter and status word kept for the plan's
     life.  ``run`` enqueues ``dxrl_evaluate_mlp`` on the trainer's packed weights and
     ``dxrl_pg_val_row`` behind it and reads nothing back.  Every run uses the same seeds (common
-    random numbers), so rows are comparable across iterations.  The plan touches neither the
-    training env nor the trainer's streams or buffers.
+    random numbers across iterations), so rows are comparable across iterations.  The plan touches
+    neither the training env nor the trainer's streams or buffers.
 
     ``noise_levels`` (a sequence of (obs_std, dyn_std) pairs; ``parse_noise_levels``) makes it a
     robustness sweep of the live actor: one lane per episode of every level, level-major (level
     l, object o, episode k is lane, segment and record (l G + o) K + k), each lane the segment
     ``Segment(o, [seed + k], obs_std, dyn_std)`` with device Philox noise, and
     ``dxrl_pg_val_levels_row`` behind the one episode launch.  Level 0 is the baseline and holds
-    records 0 .. G K - 1, which are the plan without levels' records; the device streams are keyed
-    by record index, so the levels do not share spawns or noise draws (no common random numbers
-    across levels)."""
+    records 0 .. G K - 1, which are the plan without levels' records.  The device streams are keyed
+    by lane, segment and record index, so by default the levels do not share spawns or noise draws
+    and a degradation is the difference of two independent samples.
+
+    ``common_random_numbers=True`` (needs ``noise_levels``) makes the random numbers common across
+    the levels too: the episode launch runs with ``stream_period = G K``, so level l's episode i
+    has the spawn, the object properties, the standard normals (scaled by the level's stds) and
+    the action noise of the baseline's episode i.  Level 0 keeps its records; every level is what
+    a plan of that level alone would run.  ``dxrl_pg_val_paired_row`` then adds the paired table
+    (``ValidationLog.paired`` / ``.object_lost``) behind the levels row."""
 
     def __init__(self, tr, heldout_set, episodes_per_object: int = 5, seed: int = 0, device_seed: int = 0,
                  max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0,
-                 noise_levels=None):
+                 noise_levels=None, common_random_numbers: bool = False):
         from .envs import VecEnv
         from .evaluator import Evaluator, Segment
         objs = list(heldout_set.heldout_objects)
@@ -478,6 +538,9 @@ class ValidationPlan:
             raise ValueError("a validation repeats the same episodes every time: seed must be an integer")
         self.noise_levels = None if noise_levels is None else parse_noise_levels(noise_levels)
         L = self.L = 0 if self.noise_levels is None else len(self.noise_levels)
+        self.common_random_numbers = bool(common_random_numbers)
+        if self.common_random_numbers and not L:
+            raise ValueError("common_random_numbers pairs the episodes of the noise levels: it needs noise_levels")
         ms = int(max_steps or tr.env.max_episode_steps)
         dev = self.dev = tr.dev
         self.G, self.K, self.E, self.max_steps = G, K, max(L, 1) * G * K, ms
@@ -501,6 +564,8 @@ class ValidationPlan:
                             "reward_type": tr.env.reward_type}
         if L:  # a plan without levels keeps the fingerprint it always had
             self.fingerprint["noise_levels"] = [list(p) for p in self.noise_levels]
+        if self.common_random_numbers:  # only when set: every other plan keeps its fingerprint
+            self.fingerprint["common_random_numbers"] = True
         self.fingerprint = json.loads(json.dumps(self.fingerprint))  # as a checkpoint returns it
         E = self.E
         self.env = VecEnv(E, reward_type=tr.env.reward_type, reward_shaping=tr.env.reward_shaping,
@@ -521,6 +586,10 @@ class ValidationPlan:
         else:
             N.call("dxrl_pg_val_partial_doubles", G, K, C.byref(nb))
         self.partial = torch.zeros(nb.value, dtype=torch.float64, device=dev)
+        self.paired_partial = None
+        if self.common_random_numbers:
+            N.call("dxrl_pg_val_paired_partial_doubles", L, G, K, C.byref(nb))
+            self.paired_partial = torch.zeros(nb.value, dtype=torch.float64, device=dev)
         self.action_std = None  # exp(log_std) of the last stochastic run (kept alive for its launch)
         a = self.args = N.EvalArgs()
         a.num_lanes, a.policy, a.max_steps, a.total_episodes = E, N.EVAL_POLICY_MLP, ms, E
@@ -528,6 +597,7 @@ class ValidationPlan:
         a.policy_seed = a.noise_seed = a.reset_seed = self.device_seed & (2**64 - 1)
         a.ep_return, a.ep_length, a.ep_success = N.ptr(self.ep_return), N.ptr(self.ep_length), N.ptr(self.ep_success)
         a.ep_contacts, a.status, a.work_queue = N.ptr(self.ep_contacts), N.ptr(self.status), N.ptr(self.queue)
+        a.stream_period = G * K if self.common_random_numbers else 0
 
     @staticmethod
     def sweep_levels(observation_noise_levels, dynamics_noise_levels):
@@ -578,6 +648,13 @@ class ValidationPlan:
                 v.num_levels, v.score_table, v.level_noise = self.L, int(score_table), p(self.level_noise)
                 v.levels, v.robust = p(val.levels), p(val.robust)
                 N.call("dxrl_pg_val_levels_row", self.dev.index, C.byref(v), tr._s())
+                if self.common_random_numbers:
+                    q = N.PgValPairedArgs()
+                    q.num_objects, q.episodes_per_object, q.row, q.cap = self.G, self.K, val.rows, val.cap
+                    q.num_levels, q.partial_doubles = self.L, self.paired_partial.numel()
+                    q.ep_return, q.ep_length, q.ep_success = v.ep_return, v.ep_length, v.ep_success
+                    q.partial, q.paired, q.object_lost = p(self.paired_partial), p(val.paired), p(val.object_lost)
+                    N.call("dxrl_pg_val_paired_row", self.dev.index, C.byref(q), tr._s())
             else:
                 N.call("dxrl_pg_val_row", self.dev.index, C.byref(v), tr._s())
         val.rows += 1
@@ -591,7 +668,8 @@ class _ValState:
     """The device validation table, per-object table, header and validation-best parameters of a
     trainer's run (a second, independent set beside the training log's).  For a plan with noise
     levels (the fingerprint's noise_levels) also the level and robust tables, and the per-object
-    table holds a row per level."""
+    table holds a row per level; with common random numbers (the fingerprint's
+    common_random_numbers) also the paired table and the per-object lost pairs."""
 
     def __init__(self, tr, fingerprint: Dict[str, Any], object_names, cap: int = 0):
         d = self.dev = tr.dev
@@ -599,9 +677,11 @@ class _ValState:
         noise = fingerprint.get("noise_levels")
         self.noise_levels = None if noise is None else [(float(o), float(dd)) for o, dd in noise]
         self.L = 0 if noise is None else len(noise)
+        self.crn = bool(self.L and fingerprint.get("common_random_numbers"))
         self.cap = 0
         self.table = self.objects = self.host_table = self.host_objects = None
         self.levels = self.robust = self.host_levels = self.host_robust = None
+        self.paired = self.object_lost = self.host_paired = self.host_object_lost = None
         self.header = torch.zeros(_VAL_HEADER_BYTES, dtype=torch.uint8, device=d)
         self.header[8:24].view(torch.int64).fill_(-1)                  # best_row, stopped_row
         self.header[32:40].view(torch.float64).fill_(-math.inf)        # best_score
@@ -620,6 +700,9 @@ class _ValState:
         if self.L:
             shapes["levels"] = ((cap, self.L, VAL_LEVEL_COLS), torch.float64)
             shapes["robust"] = ((cap, VAL_ROBUST_COLS), torch.float64)
+        if self.crn:
+            shapes["paired"] = ((cap, self.L, VAL_PAIRED_COLS), torch.float64)
+            shapes["object_lost"] = ((cap, self.L, self.G), torch.int32)
         return shapes
 
     def reserve(self, cap: int):
@@ -643,8 +726,8 @@ def val_state(tr, st: "_RunState", plan: ValidationPlan) -> _ValState:
     elif st.val.fingerprint != plan.fingerprint:
         raise ValueError("this run is validated by another plan (differs in "
                          f"{', '.join(fingerprint_diff(st.val.fingerprint, plan.fingerprint))}): a validation "
-                         "table holds rows of one held-out set, episode count, seeds, step limit, mode and "
-                         "noise levels")
+                         "table holds rows of one held-out set, episode count, seeds, step limit, mode, "
+                         "noise levels and common-random-numbers setting")
     return st.val
 
 
@@ -657,13 +740,16 @@ def validation_log(tr) -> Optional[ValidationLog]:
     last = v.last_log() if v.last_log is not None else None
     if last is not None:
         last._resolve()
-    names = ("table", "objects") + (("levels", "robust") if v.L else ())
+    names = ("table", "objects") + (("levels", "robust") if v.L else ()) + \
+        (("paired", "object_lost") if v.crn else ())
     if v.rows:
         for name in names:
             getattr(v, "host_" + name)[:v.rows].copy_(getattr(v, name)[:v.rows], non_blocking=True)
     v.host_header.copy_(v.header, non_blocking=True)
     v.event.record(torch.cuda.current_stream(tr.dev))
     more = (v.host_levels, v.host_robust) if v.L else ()
+    if v.crn:
+        more += (v.host_paired, v.host_object_lost)
     log = ValidationLog(object_names=v.object_names, settings=v.settings, noise_levels=v.noise_levels,
                         _pending=(v.event, v.host_table, v.host_header, v.host_objects, v.rows) + more)
     v.last_log = weakref.ref(log)
@@ -768,7 +854,9 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
     (``dxrl_pg_val_levels_row``): ``log.validation`` keeps its columns as the clean (level 0)
     curve and gains ``levels`` / ``robust``, and val_keep_best may also name a score over the
     levels -- "worst_success_rate", "mean_success_rate", "mean_noisy_success_rate" or
-    "worst_mean_return" -- which min_delta, patience and stop_on_patience then follow."""
+    "worst_mean_return" -- which min_delta, patience and stop_on_patience then follow.  A plan
+    built with common_random_numbers=True also logs ``paired`` / ``object_lost``
+    (``dxrl_pg_val_paired_row``); keep-best and patience do not read them."""
     if tr.collective:
         raise ValueError("fit() runs on one rank: a collective trainer (world > 1 or a process group) would need "
                          "the ranks' log sums merged between the reduce and the finish stage, which is not built")
@@ -919,16 +1007,22 @@ def save_checkpoint(tr, path):
             arrays.update(validation_arrays(host(v.table[:v.rows]), host(v.header), host(v.best_params),
                                             host(v.objects[:v.rows]),
                                             host(v.levels[:v.rows]) if v.L else None,
-                                            host(v.robust[:v.rows]) if v.L else None))
+                                            host(v.robust[:v.rows]) if v.L else None,
+                                            host(v.paired[:v.rows]) if v.crn else None,
+                                            host(v.object_lost[:v.rows]) if v.crn else None))
             meta["validation"] = validation_meta(st.val.rows, st.val.fingerprint, st.val.object_names, st.val.settings)
     write_checkpoint(path, arrays, meta)
 
 
-def validation_arrays(table, header, best_params, objects, levels=None, robust=None) -> Dict[str, np.ndarray]:
-    """The checkpoint's optional validation arrays (levels / robust: a plan with noise levels)."""
+def validation_arrays(table, header, best_params, objects, levels=None, robust=None, paired=None,
+                      object_lost=None) -> Dict[str, np.ndarray]:
+    """The checkpoint's optional validation arrays (levels / robust: a plan with noise levels;
+    paired / object_lost: one with common random numbers)."""
     out = {"val_table": table, "val_header": header, "val_best_params": best_params, "val_objects": objects}
     if levels is not None:
         out.update(val_levels=levels, val_robust=robust)
+    if paired is not None:
+        out.update(val_paired=paired, val_object_lost=object_lost)
     return out
 
 
@@ -945,10 +1039,13 @@ def validation_log_of_checkpoint(arrays: Dict[str, np.ndarray], meta: Dict[str, 
     if v is None:
         return None
     noise = v["fingerprint"].get("noise_levels")  # absent: a plan without levels, or an older file
+    crn = noise is not None and bool(v["fingerprint"].get("common_random_numbers"))  # absent likewise
     return ValidationLog(arrays["val_table"], val_header_dict(arrays["val_header"]), arrays["val_objects"],
                          v["object_names"], v.get("settings"), noise_levels=noise,
                          levels=arrays["val_levels"] if noise is not None else None,
-                         robust=arrays["val_robust"] if noise is not None else None)
+                         robust=arrays["val_robust"] if noise is not None else None,
+                         paired=arrays["val_paired"] if crn else None,
+                         object_lost=arrays["val_object_lost"] if crn else None)
 
 
 def load_checkpoint(cls, path, env):
@@ -1000,6 +1097,9 @@ def load_checkpoint(cls, path, env):
                 if val.L:
                     put(val.levels[:val.rows], "val_levels")
                     put(val.robust[:val.rows], "val_robust")
+                if val.crn:
+                    put(val.paired[:val.rows], "val_paired")
+                    put(val.object_lost[:val.rows], "val_object_lost")
             put(val.header, "val_header")
             put(val.best_params, "val_best_params")
     torch.cuda.synchronize(dev)

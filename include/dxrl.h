@@ -656,6 +656,16 @@ typedef struct dxrl_eval_args {
     const double* noise_tape;        /* f64 standard normals, addressed by segment offsets   */
     const double* reset_tape;        /* f64 [total_episodes][D+6] resolved reset draws       */
     uint64_t policy_seed, noise_seed, reset_seed; /* Philox keys of the device streams       */
+    /* Stream period of dxrl_evaluate_mlp's device Philox streams.  0: the policy stream is keyed by
+       the lane index, the noise stream by the segment index, the reset draw by the record index.
+       P > 0: by that index modulo P (counters, blocks and stream constants unchanged; records,
+       trajectories, policy_used and hist_moments stay addressed by the true index), so indices
+       below P keep their keys and lane / segment / record i + m P replays the draws of i: in a
+       level-major launch of L levels x P one-episode lanes every level sees the spawns, standard
+       normals and action noise of a P-lane launch of that level alone (common random numbers).
+       DXRL_E_INVALID: P < 0, P > 0 with any parity tape, P != 0 in dxrl_evaluate.  The field sits
+       with the keys it addresses; hist_moments stays the struct's last field. */
+    int64_t stream_period;
     /* per-episode records [total_episodes] */
     double* ep_return;               /* episode_reward (f64, sequential sum)                 */
     int32_t* ep_length;              /* episode_steps                                        */
@@ -1359,6 +1369,88 @@ typedef struct dxrl_pg_val_levels_args {
 int dxrl_pg_val_levels_partial_doubles(int32_t num_levels, int64_t num_objects, int64_t episodes_per_object,
                                        int64_t* out);
 int dxrl_pg_val_levels_row(int32_t device, const dxrl_pg_val_levels_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Paired rows of a noise-level validation run with common random numbers
+ * (csrc/dxrl_pg_val_paired.hip).  Enqueued behind dxrl_pg_val_levels_row on the same stream, on
+ * the same level-major records, when the episode launch ran with
+ * dxrl_eval_args.stream_period = G K: episode i of every level is then the same spawn, the same
+ * standard normals and the same action noise, and only the level's noise scale differs.  It reads
+ * the records and writes two tables of its own; the header, the three tables of
+ * dxrl_pg_val_levels_row and keep-best are not touched.
+ *
+ * For level l, pair i in [0, G K) is (record l G K + i, record i); s0 / sl are the two success
+ * flags (non-zero ep_success bytes), d_i = ep_return[l G K + i] - ep_return[i], n = G K.
+ * paired[row][l] (DXRL_PG_VAL_PAIRED_COLS columns, enum dxrl_pg_val_paired_col):
+ *   pairs                       n
+ *   lost, gained                pairs with s0 and not sl; with sl and not s0
+ *   both_success, both_fail     pairs with s0 and sl; with neither
+ *   mean_return_diff            mean of d
+ *   return_diff_std             sqrt(M2 / n), M2 the sum of squared deviations of d
+ *   return_diff_stderr          sqrt(M2 / (n (n - 1))), NaN for n = 1
+ *   mean_length_diff            (sum of ep_length[l G K + i] - ep_length[i], an exact integer) / n
+ *   paired_degradation          (lost - gained) / n
+ *   paired_degradation_stderr   with dn = (double)(lost - gained), dc = (double)(lost + gained),
+ *                               N = (double)n, in f64 and in this order: q = dn * dn; q = q / N;
+ *                               v = dc - q; v = v / N; v = v > 0 ? v : 0; sqrt(v) / sqrt(N)
+ *   mcnemar                     dc > 0 ? (dn * dn) / dc : 0
+ *   objects_with_loss           objects o with object_lost[o] > 0
+ *   max_object_lost             the largest object_lost[o]
+ * object_lost (nullable): i32 [cap][L][G], row `row`: lost pairs of each object (object o holds
+ * pairs o K .. o K + K - 1).
+ * Level 0 is paired with itself by the same code: zeros, and NaN where n = 1 says so.
+ *
+ * Integer columns are exact.  The moments of d are (count, mean, M2) triples of d - d_0 (d_0 the
+ * level's first difference), each pair entering by merge(m, {1, d - d_0, 0}), merged in
+ * dxrl_pg_val_row's fixed order (the same 1,024-pair chunks, four consecutive pairs per thread,
+ * lanes by shuffles, waves and workgroup partials in index order).  Two launches whatever L is:
+ * reduce (val_grid(G, K) workgroups x L), finish (one workgroup, one wave per level).  No
+ * floating-point atomics; the same inputs give the same bytes.
+ * DXRL_E_INVALID before any launch, outputs untouched: null args or required pointer (the records,
+ * partial, paired), L outside [1, DXRL_PG_VAL_MAX_LEVELS], G or K < 1, L G K above INT32_MAX, row
+ * outside [0, cap), partial_doubles smaller than dxrl_pg_val_paired_partial_doubles(L, G, K).
+ * ------------------------------------------------------------------------ */
+#define DXRL_PG_VAL_PAIRED_COLS 14
+enum dxrl_pg_val_paired_col {
+    DXRL_PG_VAL_PAIRED_PAIRS = 0,
+    DXRL_PG_VAL_PAIRED_LOST,
+    DXRL_PG_VAL_PAIRED_GAINED,
+    DXRL_PG_VAL_PAIRED_BOTH_SUCCESS,
+    DXRL_PG_VAL_PAIRED_BOTH_FAIL,
+    DXRL_PG_VAL_PAIRED_MEAN_RETURN_DIFF,
+    DXRL_PG_VAL_PAIRED_RETURN_DIFF_STD,
+    DXRL_PG_VAL_PAIRED_RETURN_DIFF_STDERR,
+    DXRL_PG_VAL_PAIRED_MEAN_LENGTH_DIFF,
+    DXRL_PG_VAL_PAIRED_DEGRADATION,
+    DXRL_PG_VAL_PAIRED_DEGRADATION_STDERR,
+    DXRL_PG_VAL_PAIRED_MCNEMAR,
+    DXRL_PG_VAL_PAIRED_OBJECTS_WITH_LOSS,
+    DXRL_PG_VAL_PAIRED_MAX_OBJECT_LOST,
+    DXRL_PG_VAL_PAIRED_NAMED /* == DXRL_PG_VAL_PAIRED_COLS */
+};
+
+typedef struct dxrl_pg_val_paired_args {
+    int64_t num_objects;             /* G                                                    */
+    int64_t episodes_per_object;     /* K                                                    */
+    int64_t row;                     /* table row this call writes, 0 <= row < cap           */
+    int64_t cap;                     /* rows of the tables                                   */
+    int64_t partial_doubles;         /* f64 elements of partial                              */
+    int32_t num_levels;              /* L, 1 .. DXRL_PG_VAL_MAX_LEVELS                       */
+    int32_t reserved;
+    /* device inputs */
+    const double*  ep_return;        /* f64 [L G K]                                          */
+    const int32_t* ep_length;        /* i32 [L G K]                                          */
+    const uint8_t* ep_success;       /* u8  [L G K]                                          */
+    /* device scratch and outputs */
+    double*  partial;                /* f64 [partial_doubles] scratch (its own, not the levels row's) */
+    double*  paired;                 /* f64 [cap][L][DXRL_PG_VAL_PAIRED_COLS]                */
+    int32_t* object_lost;            /* i32 [cap][L][G] (nullable)                           */
+} dxrl_pg_val_paired_args;
+
+/* f64 elements of dxrl_pg_val_paired_row's `partial` scratch for L levels of G objects x K episodes. */
+int dxrl_pg_val_paired_partial_doubles(int32_t num_levels, int64_t num_objects, int64_t episodes_per_object,
+                                       int64_t* out);
+int dxrl_pg_val_paired_row(int32_t device, const dxrl_pg_val_paired_args* args, void* stream);
 
 #ifdef __cplusplus
 }

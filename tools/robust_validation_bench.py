@@ -17,6 +17,14 @@ events.  Prints one JSON line: ms per iteration per arm (median, min, max over r
 
     python tools/robust_validation_bench.py [--iters 30] [--repeats 7] [--out FILE]
     python tools/robust_validation_bench.py --profile   # a short validated fit for rocprofv3 --kernel-trace --stats
+
+--common-random-numbers is another arm of its own (with --profile: the validated fit runs the plan
+built with common_random_numbers=True).  On one trainer it alternates, over the repeats, plan.run
+back to back for the levels plan without and with common random numbers (device events), then
+runs fit(--paired-iters, validation=the CRN plan) and prints, for the last validation's weights
+and every level, return_diff_std and paired_degradation_stderr from the device's paired table
+beside the same formulas applied on the host to the records of the plan without common random
+numbers (independent episodes per level): the variance reduction the pairing buys.
 """
 import argparse
 import json
@@ -32,6 +40,64 @@ OBS_LEVELS = [0.0, 0.01, 0.05, 0.1]
 DYN_LEVELS = [0.0, 0.01, 0.05, 0.1]
 
 
+def host_paired(ret0, ret1, suc0, suc1):
+    """return_diff_std and paired_degradation_stderr (include/dxrl.h's definitions) of two record
+    sets on the host."""
+    d = ret1 - ret0
+    n = d.size
+    lost, gained = int(((suc0 != 0) & (suc1 == 0)).sum()), int(((suc0 == 0) & (suc1 != 0)).sum())
+    v = max(((lost + gained) - (lost - gained) ** 2 / n) / n, 0.0)
+    return {"mean_return_diff": float(d.mean()), "return_diff_std": float(d.std()),
+            "paired_degradation": (lost - gained) / n, "paired_degradation_stderr": v ** 0.5 / n ** 0.5}
+
+
+def paired_arm(a, tr, plan, crn, score, torch):
+    from dexterous_rl_manipulation_amd import training_run as run
+    tr.fit(a.warmup)
+    arms = {"levels": (plan, run._ValState(tr, plan.fingerprint, plan.object_names)),
+            "levels_crn": (crn, run._ValState(tr, crn.fingerprint, crn.object_names))}
+    for pl, val in arms.values():
+        pl.run(tr, val, 0, 0, 0)
+    torch.cuda.synchronize()
+    alone = {k: [] for k in arms}
+    for _ in range(a.repeats):
+        for name, (pl, val) in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            val.rows = 0  # the tables are scratch here
+            e0.record()
+            for _ in range(10):
+                pl.run(tr, val, 0, 0, 0)
+            e1.record()
+            e1.synchronize()
+            alone[name].append(e0.elapsed_time(e1) / 10)
+    log = tr.fit(a.paired_iters, validation=crn, validate_every=a.every, val_keep_best=score)
+    v = log.validation
+    pl, val = arms["levels"]
+    val.rows = 0
+    pl.run(tr, val, 0, 0, 0)  # independent episodes per level, on the weights of the last validation
+    torch.cuda.synchronize()
+    ret, suc = pl.ep_return.cpu().numpy(), pl.ep_success.cpu().numpy()
+    n = pl.G * pl.K
+    per_level = []
+    for l, (o, d) in enumerate(crn.noise_levels):
+        s = slice(l * n, (l + 1) * n)
+        row = {"obs_noise_std": o, "dyn_noise_std": d,
+               "success_rate_crn": float(v.level_column("success_rate")[-1, l]),
+               "success_rate_independent": float((suc[s] != 0).mean()),
+               "crn": {k: float(v.paired_column(k)[-1, l]) for k in ("mean_return_diff", "return_diff_std",
+                                                                      "paired_degradation",
+                                                                      "paired_degradation_stderr", "lost", "gained")},
+               "independent": host_paired(ret[:n], ret[s], suc[:n], suc[s])}
+        per_level.append(row)
+    res = {"envs": a.envs, "horizon": a.horizon, "paired_iters": a.paired_iters, "validate_every": a.every,
+           "repeats": a.repeats, "objects": a.objects, "episodes_per_object": a.episodes,
+           "noise_levels": [list(x) for x in crn.noise_levels], "pairs_per_level": n,
+           "validations": len(v), "device": torch.cuda.get_device_name(tr.dev), "per_level_last_row": per_level}
+    for name, t in alone.items():
+        res[f"validation_alone_ms_{name}"] = {"median": statistics.median(t), "min": min(t), "max": max(t), "all": t}
+    return res
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=30)
@@ -44,6 +110,8 @@ def main():
     p.add_argument("--episodes", type=int, default=10)
     p.add_argument("--out", default=None)
     p.add_argument("--profile", action="store_true")
+    p.add_argument("--common-random-numbers", action="store_true")
+    p.add_argument("--paired-iters", type=int, default=200)
     a = p.parse_args()
     import torch
     from dexterous_rl_manipulation_amd import CurriculumConfig, workloads
@@ -56,9 +124,21 @@ def main():
     levels = ValidationPlan.sweep_levels(OBS_LEVELS, DYN_LEVELS)
     plan = tr.validation_plan(heldout, episodes_per_object=a.episodes, seed=0, device_seed=0, noise_levels=levels)
     score = "worst_success_rate"
+    crn = None
+    if a.common_random_numbers:
+        crn = tr.validation_plan(heldout, episodes_per_object=a.episodes, seed=0, device_seed=0, noise_levels=levels,
+                                 common_random_numbers=True)
     if a.profile:
-        tr.fit(a.iters, validation=plan, validate_every=a.every, val_keep_best=score)
+        tr.fit(a.iters, validation=crn or plan, validate_every=a.every, val_keep_best=score)
         torch.cuda.synchronize()
+        return
+    if crn is not None:
+        line = json.dumps(paired_arm(a, tr, plan, crn, score, torch))
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
         return
 
     def plain():
