@@ -293,11 +293,33 @@ class PgValPairedArgs(C.Structure):
                [(k, C.c_void_p) for k in ("ep_return", "ep_length", "ep_success", "partial", "paired", "object_lost")]
 
 
+# enum dxrl_pg_val_failure_mode_col / dxrl_pg_val_failure_level_col: the failure tables of
+# dxrl_pg_val_failure_row, in table order; the classes of its transitions (success, then the modes)
+PG_VAL_FAILURE_MAX_EPISODES = 1 << 19  # DXRL_PG_VAL_FAILURE_MAX_EPISODES
+PG_VAL_FAILURE_CLASSES = FAILURE_MODES + 1  # DXRL_PG_VAL_FAILURE_CLASSES
+PG_VAL_FAILURE_MODE_COLUMNS = ("count", "frequency", "episode_share", "mean_episode_length", "std_episode_length",
+                               "mean_final_contacts", "mean_confidence", "objects", "max_object_count",
+                               "worst_object")
+PG_VAL_FAILURE_MODE_COLS = len(PG_VAL_FAILURE_MODE_COLUMNS)    # DXRL_PG_VAL_FAILURE_MODE_COLS
+PG_VAL_FAILURE_LEVEL_COLUMNS = ("episodes", "failures", "failure_rate", "dominant_mode", "dominant_frequency",
+                                "modes_present", "tie_rows", "mean_confidence")
+PG_VAL_FAILURE_LEVEL_COLS = len(PG_VAL_FAILURE_LEVEL_COLUMNS)  # DXRL_PG_VAL_FAILURE_LEVEL_COLS
+
+
+class PgValFailureArgs(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("num_objects", "episodes_per_object", "row", "cap", "partial_doubles")] + \
+               [(k, C.c_int32) for k in ("num_levels", "paired", "max_steps", "timeout_steps", "success_threshold",
+                                         "reserved")] + \
+               [(k, C.c_void_p) for k in ("ep_length", "ep_success", "ep_contacts", "hist_moments", "partial",
+                                          "failure_modes", "failure_levels", "failure_transitions")]
+
+
 # the structs added after tests/test_native_abi.py fixed its list: (C name, mirror), sized against
 # include/dxrl.h by the tests of the layers that use them
 LATER_STRUCTS = (("dxrl_pg_log_args", PgLogArgs), ("dxrl_pg_log_header", PgLogHeader),
                  ("dxrl_pg_val_args", PgValArgs), ("dxrl_pg_val_header", PgValHeader),
-                 ("dxrl_pg_val_levels_args", PgValLevelsArgs), ("dxrl_pg_val_paired_args", PgValPairedArgs))
+                 ("dxrl_pg_val_levels_args", PgValLevelsArgs), ("dxrl_pg_val_paired_args", PgValPairedArgs),
+                 ("dxrl_pg_val_failure_args", PgValFailureArgs))
 
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
@@ -360,6 +382,8 @@ _SIGS = {
     "dxrl_pg_val_levels_row": (C.c_int, [_I32, C.POINTER(PgValLevelsArgs), _P]),
     "dxrl_pg_val_paired_partial_doubles": (C.c_int, [_I32, _I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_val_paired_row": (C.c_int, [_I32, C.POINTER(PgValPairedArgs), _P]),
+    "dxrl_pg_val_failure_partial_doubles": (C.c_int, [_I32, _I64, _I64, C.POINTER(_I64)]),
+    "dxrl_pg_val_failure_row": (C.c_int, [_I32, C.POINTER(PgValFailureArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

@@ -3,7 +3,8 @@
 // confidence), and per (group, mode) the sums behind compute_failure_distribution /
 // compute_correlations (evaluation/failure_statistics.py:34-159) and analyze_failure_modes
 // (evaluation/failure_analysis.py:61-99), on the record buffers dxrl_evaluate / dxrl_evaluate_mlp
-// wrote.  The rules, the tie rows and the table layouts are stated in include/dxrl.h.
+// wrote.  The rules, the tie rows and the table layouts are stated in include/dxrl.h; Verdict /
+// classify are dxrl_failure_rules.h's.
 //
 // Two launches on the caller's stream, no host synchronisation between:
 //   k_failure_episodes  history form: a wave per contact_hist row (the shared row reduction of
@@ -17,6 +18,7 @@
 //                       min / max are exact.  Mode 0's workgroup also writes group_totals; one
 //                       extra workgroup compacts the tie rows into tie_list in ascending order
 //                       (compact_rows, dxrl_reduce.h).
+#include "dxrl_failure_rules.h"
 #include "dxrl_hist_row.h"
 #include "dxrl_moments.h"
 #include "dxrl_reduce.h"
@@ -28,43 +30,6 @@ constexpr int kFsThreads = 256, kFsWaves = kFsThreads / 64;
 constexpr int kModes = DXRL_FAILURE_MODES;
 constexpr int kFsTie = 0x80;   // ep_work: low bits mode + 1, bit 7 a tie row,
 constexpr int kFsSkip = 0x40;  //          bit 6 left out of the mode tables (tie row, history form)
-
-// list(FailureMode) order
-enum : int { M_SLIPPAGE = 0, M_UNSTABLE = 1, M_MISALIGNMENT = 2, M_TIMEOUT = 3, M_DROPPED = 4, M_INSUFFICIENT = 5 };
-
-struct Verdict {
-    int mode, tie;
-    double conf;
-};
-
-// failure_taxonomy.py:171-239 on the integer moments of the episode's contact counts
-__device__ __forceinline__ Verdict classify(bool success, int len, int n, int s1, int s2, int f5, int l5, int peak,
-                                            int nc, int timeout_steps, int success_threshold) {
-    if (success) return Verdict{-1, 0, 0.0};  // :171-173
-    if (n == 0) peak = nc;                    // :190-193 no history: max_contacts = num_contacts
-    if (len >= timeout_steps) return Verdict{M_TIMEOUT, 0, 1.0};       // :196-198
-    if (nc == 0 && peak > 0) return Verdict{M_DROPPED, 0, 1.0};        // :201-203
-    const long long nn = n;
-    const long long num = nn * (long long)s2 - (long long)s1 * (long long)s1;  // n^2 var, below 2^41
-    int tie = 0;
-    if (n > 5) {  // :206-222
-        if (n > 10) {
-            const double trend = ((double)l5 / 5.0) - ((double)f5 / 5.0);  // np.mean of five small integers
-            if (trend < -1.0 && peak >= 1) return Verdict{M_SLIPPAGE, 0, fmin(1.0, fabs(trend) / 2.0)};
-        }
-        if (num > 2 * nn * nn) {
-            const double var = (double)num / (double)(nn * nn);  // both exact: the correctly rounded variance
-            return Verdict{M_UNSTABLE, 0, fmin(1.0, var / 5.0)};
-        }
-        tie = num == 2 * nn * nn;  // np.var's own rounding decides
-    }
-    if (nc >= 1 && nc <= 2) {  // :225-230 (variance 0.0 for a history of one entry or none)
-        if (n <= 1 || num < nn * nn) return Verdict{M_MISALIGNMENT, tie, 0.8};
-        tie |= num == nn * nn;
-    }
-    if (peak < success_threshold) return Verdict{M_INSUFFICIENT, tie, 1.0};  // :233-235
-    return Verdict{M_INSUFFICIENT, tie, 0.5};                                 // :238-239
-}
 
 template <bool kMoments>
 __global__ __launch_bounds__(kFsThreads) void k_failure_episodes(

@@ -54,6 +54,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                    help="dynamics-noise levels of the validation sweep")
     p.add_argument("--val-common-random-numbers", action="store_true",
                    help="every noise level replays the baseline's episodes; logs the paired table")
+    p.add_argument("--val-failure-modes", action="store_true",
+                   help="classify every validation episode with the failure taxonomy; logs the failure tables")
+    p.add_argument("--val-classify-max-steps", type=int, default=None, metavar="T",
+                   help="the taxonomy's timeout bound (default: the validation's step limit)")
     p.add_argument("--patience", type=int, default=0, metavar="P")
     p.add_argument("--envs", type=int, default=None, help="envs (default: the workload's, 4096 with --config)")
     p.add_argument("--horizon", type=int, default=200)
@@ -99,6 +103,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error(f"--val-keep-best {a.val_keep_best} needs --val-obs-noise / --val-dyn-noise")
     if a.val_common_random_numbers and a.val_noise_levels is None:
         p.error("--val-common-random-numbers needs --val-obs-noise / --val-dyn-noise")
+    if a.val_failure_modes and not a.validate_every:
+        p.error("--val-failure-modes needs --validate-every")
+    if a.val_classify_max_steps is not None and not a.val_failure_modes:
+        p.error("--val-classify-max-steps needs --val-failure-modes")
+    if a.val_classify_max_steps is not None and a.val_classify_max_steps < 1:
+        p.error("--val-classify-max-steps must be >= 1")
     if a.config_name is None and a.config is None:
         a.config_name = "easy"
     return a
@@ -150,7 +160,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         from .evaluation import HeldOutObjectSet
         plan = tr.validation_plan(HeldOutObjectSet(base_config), episodes_per_object=a.val_episodes,
                                   seed=a.val_seed, max_steps=a.max_steps, noise_levels=a.val_noise_levels,
-                                  common_random_numbers=a.val_common_random_numbers)
+                                  common_random_numbers=a.val_common_random_numbers,
+                                  failure_modes=a.val_failure_modes, classify_max_steps=a.val_classify_max_steps)
         kw = dict(validation=plan, validate_every=a.validate_every, val_keep_best=a.val_keep_best,
                   patience=a.patience, stop_on_patience=bool(a.patience and a.poll_every))
     log = tr.fit(a.iterations, keep_best=a.keep_best, min_episodes=a.min_episodes, converge=a.converge,

@@ -792,15 +792,19 @@ class PGTrainer:
 
     def validation_plan(self, heldout_set, episodes_per_object: int = 5, seed: int = 0, device_seed: int = 0,
                         max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0,
-                        noise_levels=None, common_random_numbers: bool = False):
+                        noise_levels=None, common_random_numbers: bool = False, failure_modes: bool = False,
+                        classify_max_steps: Optional[int] = None, success_threshold: int = 3):
         """A held-out evaluation of this trainer's live actor, built once for fit(validation=...).
         noise_levels: (obs_std, dyn_std) pairs (ValidationPlan.sweep_levels builds the reference's
         sweep) -- every validation then runs all levels and logs per-level and robust rows.
         common_random_numbers (needs noise_levels): every level replays the baseline's episodes --
-        same spawns, standard normals and action noise -- and a paired table is logged too."""
+        same spawns, standard normals and action noise -- and a paired table is logged too.
+        failure_modes: every episode is classified with the failure taxonomy on the device (timeout
+        bound classify_max_steps, default max_steps) and per-level failure tables are logged too."""
         from . import training_run
         return training_run.ValidationPlan(self, heldout_set, episodes_per_object, seed, device_seed, max_steps,
-                                           deterministic, solve_threshold, noise_levels, common_random_numbers)
+                                           deterministic, solve_threshold, noise_levels, common_random_numbers,
+                                           failure_modes, classify_max_steps, success_threshold)
 
     def training_log(self):
         from . import training_run

@@ -27,7 +27,11 @@ row, a row per level with the degradation columns, and a row of scores over the 
 ``common_random_numbers`` the episode launch runs with ``stream_period = G K``, so every level
 replays the baseline's episodes under its own noise scale, and ``dxrl_pg_val_paired_row``
 (csrc/dxrl_pg_val_paired.hip) adds a paired table: per level the episodes lost and gained against
-the baseline and the mean and error of the per-episode return difference.
+the baseline and the mean and error of the per-episode return difference.  With ``failure_modes``
+the episode launch also accumulates the five history words of every episode, and
+``dxrl_pg_val_failure_row`` (csrc/dxrl_pg_val_failure.hip) classifies every episode with the failure
+taxonomy and adds, per level, a table of the modes, a row of totals and -- with common random
+numbers -- the class transitions against the baseline.
 """
 from __future__ import annotations
 
@@ -61,6 +65,18 @@ VAL_ROBUST_COLUMNS = N.PG_VAL_ROBUST_COLUMNS
 VAL_ROBUST_COLS = N.PG_VAL_ROBUST_COLS
 VAL_PAIRED_COLUMNS = N.PG_VAL_PAIRED_COLUMNS
 VAL_PAIRED_COLS = N.PG_VAL_PAIRED_COLS
+VAL_FAILURE_MODE_COLUMNS = N.PG_VAL_FAILURE_MODE_COLUMNS
+VAL_FAILURE_MODE_COLS = N.PG_VAL_FAILURE_MODE_COLS
+VAL_FAILURE_LEVEL_COLUMNS = N.PG_VAL_FAILURE_LEVEL_COLUMNS
+VAL_FAILURE_LEVEL_COLS = N.PG_VAL_FAILURE_LEVEL_COLS
+# list(FailureMode) order, as ep_mode has it; the classes of the transitions: success, then the modes
+FAILURE_MODE_NAMES = ("slippage", "unstable_grasp", "misalignment", "timeout", "object_dropped",
+                      "insufficient_contacts")
+FAILURE_CLASS_NAMES = ("success",) + FAILURE_MODE_NAMES
+_MODES, _CLASSES = N.FAILURE_MODES, N.PG_VAL_FAILURE_CLASSES
+# the entries of failure_distribution: compute_failure_distribution's, minus the object properties
+_DISTRIBUTION_KEYS = ("count", "frequency", "mean_episode_length", "std_episode_length", "mean_final_contacts",
+                      "mean_confidence")
 # columns of the robust row the validation keep-best may read (a plan with noise levels)
 _VAL_ROBUST_SCORE_COLUMNS = ("worst_success_rate", "mean_success_rate", "mean_noisy_success_rate",
                              "worst_mean_return")
@@ -225,11 +241,18 @@ class ValidationLog:
     A plan with common random numbers across the levels adds ``paired`` (f64 [rows][L][14],
     ``paired_column(name)`` -> [rows][L]: every level's episodes paired with the baseline's) and
     ``object_lost`` (i32 [rows][L][objects]: the lost pairs of each object).  Without it these are
-    None."""
+    None.
+
+    A plan with failure modes adds ``failure_modes`` (f64 [rows][L][6][10], ``failure_column(name)``
+    -> [rows][L][6], modes in FAILURE_MODE_NAMES order), ``failure_levels`` (f64 [rows][L][8],
+    ``failure_level_column(name)`` -> [rows][L]), ``failure_distribution(row, level)`` and -- with
+    common random numbers -- ``failure_transitions`` (i32 [rows][L][7][7], ``transitions(row,
+    level)``); L is 1 for a plan without noise levels.  Without the option these are None."""
 
     def __init__(self, table=None, header: Optional[Dict[str, Any]] = None, object_successes=None,
                  object_names=(), settings: Optional[Dict[str, Any]] = None, _pending=None, noise_levels=None,
-                 levels=None, robust=None, paired=None, object_lost=None):
+                 levels=None, robust=None, paired=None, object_lost=None, failure_modes=None, failure_levels=None,
+                 failure_transitions=None):
         self._pending = _pending
         self.object_names = list(object_names)
         self.noise_levels = None if noise_levels is None else [(float(o), float(d)) for o, d in noise_levels]
@@ -246,6 +269,13 @@ class ValidationLog:
             np.array(paired, dtype=np.float64).reshape(-1, L, VAL_PAIRED_COLS)
         self._object_lost = None if object_lost is None or self._paired is None else \
             np.array(object_lost, dtype=np.int32).reshape(-1, L, len(self.object_names))
+        Lf = max(L, 1)  # a validation without levels is one level
+        self._failure_modes = None if failure_modes is None else \
+            np.array(failure_modes, dtype=np.float64).reshape(-1, Lf, _MODES, VAL_FAILURE_MODE_COLS)
+        self._failure_levels = None if failure_levels is None or self._failure_modes is None else \
+            np.array(failure_levels, dtype=np.float64).reshape(-1, Lf, VAL_FAILURE_LEVEL_COLS)
+        self._failure_transitions = None if failure_transitions is None or self._failure_modes is None else \
+            np.array(failure_transitions, dtype=np.int32).reshape(-1, Lf, _CLASSES, _CLASSES)
         self.settings = dict(settings or {})
 
     @property
@@ -254,15 +284,13 @@ class ValidationLog:
 
     def _resolve(self):
         if self._pending is not None:
-            event, host_table, host_header, host_objects, rows, *more = self._pending
+            event, host_table, host_header, host_objects, rows, more = self._pending
             event.synchronize()
             self._table = host_table[:rows].numpy().copy()
             self._header = val_header_dict(host_header.numpy())
             self._objects = host_objects[:rows].numpy().copy()
-            if more:
-                self._levels, self._robust = (t[:rows].numpy().copy() for t in more[:2])
-            if len(more) > 2:
-                self._paired, self._object_lost = (t[:rows].numpy().copy() for t in more[2:])
+            for name, t in more.items():  # the optional tables of the plan, by _ValState's names
+                setattr(self, "_" + name, t[:rows].numpy().copy())
             self._pending = None
 
     @property
@@ -313,6 +341,75 @@ class ValidationLog:
             raise ValueError("this validation has no paired table (validation_plan(..., noise_levels=..., "
                              "common_random_numbers=True))")
         return self.paired[:, :, VAL_PAIRED_COLUMNS.index(name)]
+
+    @property
+    def failure_modes(self) -> Optional[np.ndarray]:
+        """f64 [rows][L][6][10] (FAILURE_MODE_NAMES x VAL_FAILURE_MODE_COLUMNS), or None without
+        failure modes; L is 1 without noise levels."""
+        self._resolve()
+        return self._failure_modes
+
+    @property
+    def failure_levels(self) -> Optional[np.ndarray]:
+        """f64 [rows][L][8] (VAL_FAILURE_LEVEL_COLUMNS), or None without failure modes."""
+        self._resolve()
+        return self._failure_levels
+
+    @property
+    def failure_transitions(self) -> Optional[np.ndarray]:
+        """i32 [rows][L][7][7] ([from][to] over FAILURE_CLASS_NAMES: the baseline's class against
+        the level's, per pair), or None without failure modes or without common random numbers."""
+        self._resolve()
+        return self._failure_transitions
+
+    def _need_failure_modes(self):
+        if self.failure_modes is None:
+            raise ValueError("this validation has no failure tables (validation_plan(..., failure_modes=True))")
+
+    def _failure_cell(self, row: int, level: int):
+        self._need_failure_modes()
+        rows, levels = self.failure_modes.shape[:2]
+        if not -rows <= row < rows:
+            raise IndexError(f"row {row} outside the {rows} validations of this log")
+        if not 0 <= level < levels:
+            raise IndexError(f"level {level} outside the {levels} levels of this validation")
+        return row, level
+
+    def failure_column(self, name: str) -> np.ndarray:
+        """[rows][L][6]: one column of the mode rows."""
+        self._need_failure_modes()
+        if name not in VAL_FAILURE_MODE_COLUMNS:
+            raise ValueError(f"a failure column is one of {list(VAL_FAILURE_MODE_COLUMNS)}, got {name!r}")
+        return self.failure_modes[:, :, :, VAL_FAILURE_MODE_COLUMNS.index(name)]
+
+    def failure_level_column(self, name: str) -> np.ndarray:
+        """[rows][L]: one column of the per-level failure rows."""
+        self._need_failure_modes()
+        if name not in VAL_FAILURE_LEVEL_COLUMNS:
+            raise ValueError(f"a failure level column is one of {list(VAL_FAILURE_LEVEL_COLUMNS)}, got {name!r}")
+        return self.failure_levels[:, :, VAL_FAILURE_LEVEL_COLUMNS.index(name)]
+
+    def failure_distribution(self, row: int, level: int = 0) -> Dict[str, Dict[str, Any]]:
+        """The modes of one validation and level in ``compute_failure_distribution``'s shape (its
+        entries minus the object properties), keyed by mode name, for the modes that occurred."""
+        row, level = self._failure_cell(row, level)
+        out = {}
+        for m, name in enumerate(FAILURE_MODE_NAMES):
+            r = self.failure_modes[row, level, m]
+            if r[0] > 0:
+                out[name] = {k: (int(r[0]) if k == "count" else float(r[VAL_FAILURE_MODE_COLUMNS.index(k)]))
+                             for k in _DISTRIBUTION_KEYS}
+        return out
+
+    def transitions(self, row: int, level: int) -> Dict[str, Any]:
+        """The class pairs of one validation and level: ``{"classes": FAILURE_CLASS_NAMES,
+        "counts": i32 [7][7]}`` with counts[from][to] the pairs whose baseline episode has class
+        ``from`` and whose episode in the level has class ``to``."""
+        row, level = self._failure_cell(row, level)
+        if self.failure_transitions is None:
+            raise ValueError("this validation has no transitions (validation_plan(..., noise_levels=..., "
+                             "common_random_numbers=True, failure_modes=True))")
+        return {"classes": list(FAILURE_CLASS_NAMES), "counts": self.failure_transitions[row, level].copy()}
 
     def _need_levels(self):
         if not self.num_levels:
@@ -396,6 +493,12 @@ class ValidationLog:
             if self.num_levels > 1:  # over the noisy levels of the last row
                 out["final_max_lost"] = float(self.paired_column("lost")[-1, 1:].max())
                 out["final_min_mean_return_diff"] = float(self.paired_column("mean_return_diff")[-1, 1:].min())
+        if self.failure_modes is not None:  # per level of the last row (None: no failure in the level)
+            dominant = self.failure_level_column("dominant_mode")[-1]
+            out["final_dominant_failure_mode"] = [FAILURE_MODE_NAMES[int(m)] if m >= 0 else None for m in dominant]
+            out["final_dominant_failure_frequency"] = [float(x) for x in
+                                                       self.failure_level_column("dominant_frequency")[-1]]
+            out["final_failure_rate"] = [float(x) for x in self.failure_level_column("failure_rate")[-1]]
         return out
 
     def to_dict(self) -> Dict[str, Any]:
@@ -412,6 +515,14 @@ class ValidationLog:
             out["paired_columns"] = list(VAL_PAIRED_COLUMNS)
             out["paired"] = [[[_enc(x) for x in lv] for lv in row] for row in self.paired.tolist()]
             out["object_lost"] = self.object_lost.tolist()
+        if self.failure_modes is not None:  # a validation without failure modes serialises as it always did
+            out["failure_mode_names"] = list(FAILURE_MODE_NAMES)
+            out["failure_mode_columns"] = list(VAL_FAILURE_MODE_COLUMNS)
+            out["failure_level_columns"] = list(VAL_FAILURE_LEVEL_COLUMNS)
+            out["failure_modes"] = self.failure_modes.tolist()  # finite by construction
+            out["failure_levels"] = self.failure_levels.tolist()
+            if self.failure_transitions is not None:
+                out["failure_transitions"] = self.failure_transitions.tolist()
         return out
 
     @classmethod
@@ -435,9 +546,17 @@ class ValidationLog:
                 raise ValueError("not a validation log with this build's paired columns")
             paired = np.array([[[_dec(x) for x in lv] for lv in row] for row in d["paired"]], dtype=np.float64)
             object_lost = d["object_lost"]
+        failure = {}
+        if d.get("failure_modes") is not None:  # absent without failure modes and in older files
+            if list(d.get("failure_mode_names", [])) != list(FAILURE_MODE_NAMES) or \
+                    list(d.get("failure_mode_columns", [])) != list(VAL_FAILURE_MODE_COLUMNS) or \
+                    list(d.get("failure_level_columns", [])) != list(VAL_FAILURE_LEVEL_COLUMNS):
+                raise ValueError("not a validation log with this build's failure modes and columns")
+            failure = dict(failure_modes=d["failure_modes"], failure_levels=d["failure_levels"],
+                           failure_transitions=d.get("failure_transitions"))
         return cls(table, {k: _dec(v) for k, v in d["header"].items()}, d["object_successes"], d["object_names"],
                    d.get("settings"), noise_levels=noise, levels=levels, robust=robust, paired=paired,
-                   object_lost=object_lost)
+                   object_lost=object_lost, **failure)
 
 
 def val_header_dict(raw: np.ndarray) -> Dict[str, Any]:
@@ -520,11 +639,19 @@ class ValidationPlan:
     has the spawn, the object properties, the standard normals (scaled by the level's stds) and
     the action noise of the baseline's episode i.  Level 0 keeps its records; every level is what
     a plan of that level alone would run.  ``dxrl_pg_val_paired_row`` then adds the paired table
-    (``ValidationLog.paired`` / ``.object_lost``) behind the levels row."""
+    (``ValidationLog.paired`` / ``.object_lost``) behind the levels row.
+
+    ``failure_modes=True`` (with or without levels and common random numbers) makes the episode
+    launch accumulate ``hist_moments`` and enqueues ``dxrl_pg_val_failure_row`` last: every episode
+    is classified with the failure taxonomy (timeout bound ``classify_max_steps``, default the
+    plan's ``max_steps``; ``success_threshold`` as ``FailureClassifier``'s) into
+    ``ValidationLog.failure_modes`` / ``.failure_levels`` and, with common random numbers,
+    ``.failure_transitions``.  The records and every other table keep their bytes."""
 
     def __init__(self, tr, heldout_set, episodes_per_object: int = 5, seed: int = 0, device_seed: int = 0,
                  max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0,
-                 noise_levels=None, common_random_numbers: bool = False):
+                 noise_levels=None, common_random_numbers: bool = False, failure_modes: bool = False,
+                 classify_max_steps: Optional[int] = None, success_threshold: int = 3):
         from .envs import VecEnv
         from .evaluator import Evaluator, Segment
         objs = list(heldout_set.heldout_objects)
@@ -542,6 +669,19 @@ class ValidationPlan:
         if self.common_random_numbers and not L:
             raise ValueError("common_random_numbers pairs the episodes of the noise levels: it needs noise_levels")
         ms = int(max_steps or tr.env.max_episode_steps)
+        self.failure_modes = bool(failure_modes)
+        self.classify_max_steps = int(ms if classify_max_steps is None else classify_max_steps)
+        self.success_threshold = int(success_threshold)
+        if self.failure_modes:
+            if ms > N.SUMMARY_MAX_STEPS:
+                raise ValueError(f"failure_modes needs max_steps <= {N.SUMMARY_MAX_STEPS} (the exact integer "
+                                 f"variance rule of the taxonomy), got {ms}")
+            if G * K > N.PG_VAL_FAILURE_MAX_EPISODES:
+                raise ValueError(f"failure_modes needs objects x episodes_per_object <= "
+                                 f"{N.PG_VAL_FAILURE_MAX_EPISODES} (the exact integer variance of the lengths), "
+                                 f"got {G * K}")
+            if self.classify_max_steps < 1:
+                raise ValueError(f"classify_max_steps must be >= 1, got {self.classify_max_steps}")
         dev = self.dev = tr.dev
         self.G, self.K, self.E, self.max_steps = G, K, max(L, 1) * G * K, ms
         if self.E > 2**31 - 1:
@@ -566,6 +706,9 @@ class ValidationPlan:
             self.fingerprint["noise_levels"] = [list(p) for p in self.noise_levels]
         if self.common_random_numbers:  # only when set: every other plan keeps its fingerprint
             self.fingerprint["common_random_numbers"] = True
+        if self.failure_modes:  # likewise
+            self.fingerprint["failure_modes"] = {"classify_max_steps": self.classify_max_steps,
+                                                 "success_threshold": self.success_threshold}
         self.fingerprint = json.loads(json.dumps(self.fingerprint))  # as a checkpoint returns it
         E = self.E
         self.env = VecEnv(E, reward_type=tr.env.reward_type, reward_shaping=tr.env.reward_shaping,
@@ -590,6 +733,11 @@ class ValidationPlan:
         if self.common_random_numbers:
             N.call("dxrl_pg_val_paired_partial_doubles", L, G, K, C.byref(nb))
             self.paired_partial = torch.zeros(nb.value, dtype=torch.float64, device=dev)
+        self.hist_moments = self.failure_partial = None
+        if self.failure_modes:
+            self.hist_moments = torch.zeros(E, 5, dtype=torch.int32, device=dev)
+            N.call("dxrl_pg_val_failure_partial_doubles", max(L, 1), G, K, C.byref(nb))
+            self.failure_partial = torch.zeros(nb.value, dtype=torch.float64, device=dev)
         self.action_std = None  # exp(log_std) of the last stochastic run (kept alive for its launch)
         a = self.args = N.EvalArgs()
         a.num_lanes, a.policy, a.max_steps, a.total_episodes = E, N.EVAL_POLICY_MLP, ms, E
@@ -598,6 +746,7 @@ class ValidationPlan:
         a.ep_return, a.ep_length, a.ep_success = N.ptr(self.ep_return), N.ptr(self.ep_length), N.ptr(self.ep_success)
         a.ep_contacts, a.status, a.work_queue = N.ptr(self.ep_contacts), N.ptr(self.status), N.ptr(self.queue)
         a.stream_period = G * K if self.common_random_numbers else 0
+        a.hist_moments = N.ptr(self.hist_moments)  # NULL without failure modes: the launch it always was
 
     @staticmethod
     def sweep_levels(observation_noise_levels, dynamics_noise_levels):
@@ -657,6 +806,18 @@ class ValidationPlan:
                     N.call("dxrl_pg_val_paired_row", self.dev.index, C.byref(q), tr._s())
             else:
                 N.call("dxrl_pg_val_row", self.dev.index, C.byref(v), tr._s())
+            if self.failure_modes:  # last: behind the rows above, on records they only read
+                q = N.PgValFailureArgs()
+                q.num_objects, q.episodes_per_object, q.row, q.cap = self.G, self.K, val.rows, val.cap
+                q.num_levels, q.paired = max(self.L, 1), int(self.common_random_numbers)
+                q.partial_doubles = self.failure_partial.numel()
+                q.max_steps, q.timeout_steps = self.max_steps, self.classify_max_steps
+                q.success_threshold = self.success_threshold
+                q.ep_length, q.ep_success, q.ep_contacts = v.ep_length, v.ep_success, v.ep_contacts
+                q.hist_moments, q.partial = p(self.hist_moments), p(self.failure_partial)
+                q.failure_modes, q.failure_levels = p(val.failure_modes), p(val.failure_levels)
+                q.failure_transitions = p(val.failure_transitions)
+                N.call("dxrl_pg_val_failure_row", self.dev.index, C.byref(q), tr._s())
         val.rows += 1
 
 
@@ -669,7 +830,9 @@ class _ValState:
     trainer's run (a second, independent set beside the training log's).  For a plan with noise
     levels (the fingerprint's noise_levels) also the level and robust tables, and the per-object
     table holds a row per level; with common random numbers (the fingerprint's
-    common_random_numbers) also the paired table and the per-object lost pairs."""
+    common_random_numbers) also the paired table and the per-object lost pairs; with failure modes
+    (the fingerprint's failure_modes) also the mode and level failure tables and, with common
+    random numbers, the transitions."""
 
     def __init__(self, tr, fingerprint: Dict[str, Any], object_names, cap: int = 0):
         d = self.dev = tr.dev
@@ -678,10 +841,12 @@ class _ValState:
         self.noise_levels = None if noise is None else [(float(o), float(dd)) for o, dd in noise]
         self.L = 0 if noise is None else len(noise)
         self.crn = bool(self.L and fingerprint.get("common_random_numbers"))
+        self.failures = fingerprint.get("failure_modes") is not None
         self.cap = 0
         self.table = self.objects = self.host_table = self.host_objects = None
         self.levels = self.robust = self.host_levels = self.host_robust = None
         self.paired = self.object_lost = self.host_paired = self.host_object_lost = None
+        self.failure_modes = self.failure_levels = self.failure_transitions = None
         self.header = torch.zeros(_VAL_HEADER_BYTES, dtype=torch.uint8, device=d)
         self.header[8:24].view(torch.int64).fill_(-1)                  # best_row, stopped_row
         self.header[32:40].view(torch.float64).fill_(-math.inf)        # best_score
@@ -703,7 +868,17 @@ class _ValState:
         if self.crn:
             shapes["paired"] = ((cap, self.L, VAL_PAIRED_COLS), torch.float64)
             shapes["object_lost"] = ((cap, self.L, self.G), torch.int32)
+        if self.failures:
+            Lf = max(self.L, 1)
+            shapes["failure_modes"] = ((cap, Lf, _MODES, VAL_FAILURE_MODE_COLS), torch.float64)
+            shapes["failure_levels"] = ((cap, Lf, VAL_FAILURE_LEVEL_COLS), torch.float64)
+            if self.crn:
+                shapes["failure_transitions"] = ((cap, Lf, _CLASSES, _CLASSES), torch.int32)
         return shapes
+
+    def optional_tables(self):
+        """The names of the plan's tables beyond the main one and the per-object one."""
+        return [name for name in self._shapes(1) if name not in ("table", "objects")]
 
     def reserve(self, cap: int):
         if self.table is not None and cap <= self.cap:
@@ -727,7 +902,7 @@ def val_state(tr, st: "_RunState", plan: ValidationPlan) -> _ValState:
         raise ValueError("this run is validated by another plan (differs in "
                          f"{', '.join(fingerprint_diff(st.val.fingerprint, plan.fingerprint))}): a validation "
                          "table holds rows of one held-out set, episode count, seeds, step limit, mode, "
-                         "noise levels and common-random-numbers setting")
+                         "noise levels, common-random-numbers and failure-modes setting")
     return st.val
 
 
@@ -740,18 +915,15 @@ def validation_log(tr) -> Optional[ValidationLog]:
     last = v.last_log() if v.last_log is not None else None
     if last is not None:
         last._resolve()
-    names = ("table", "objects") + (("levels", "robust") if v.L else ()) + \
-        (("paired", "object_lost") if v.crn else ())
+    optional = v.optional_tables()
     if v.rows:
-        for name in names:
+        for name in ["table", "objects"] + optional:
             getattr(v, "host_" + name)[:v.rows].copy_(getattr(v, name)[:v.rows], non_blocking=True)
     v.host_header.copy_(v.header, non_blocking=True)
     v.event.record(torch.cuda.current_stream(tr.dev))
-    more = (v.host_levels, v.host_robust) if v.L else ()
-    if v.crn:
-        more += (v.host_paired, v.host_object_lost)
+    more = {name: getattr(v, "host_" + name) for name in optional}
     log = ValidationLog(object_names=v.object_names, settings=v.settings, noise_levels=v.noise_levels,
-                        _pending=(v.event, v.host_table, v.host_header, v.host_objects, v.rows) + more)
+                        _pending=(v.event, v.host_table, v.host_header, v.host_objects, v.rows, more))
     v.last_log = weakref.ref(log)
     return log
 
@@ -856,7 +1028,9 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
     levels -- "worst_success_rate", "mean_success_rate", "mean_noisy_success_rate" or
     "worst_mean_return" -- which min_delta, patience and stop_on_patience then follow.  A plan
     built with common_random_numbers=True also logs ``paired`` / ``object_lost``
-    (``dxrl_pg_val_paired_row``); keep-best and patience do not read them."""
+    (``dxrl_pg_val_paired_row``); keep-best and patience do not read them.  A plan built with
+    failure_modes=True also logs ``failure_modes`` / ``failure_levels`` / ``failure_transitions``
+    (``dxrl_pg_val_failure_row``); keep-best and patience do not read those either."""
     if tr.collective:
         raise ValueError("fit() runs on one rank: a collective trainer (world > 1 or a process group) would need "
                          "the ranks' log sums merged between the reduce and the finish stage, which is not built")
@@ -1009,20 +1183,25 @@ def save_checkpoint(tr, path):
                                             host(v.levels[:v.rows]) if v.L else None,
                                             host(v.robust[:v.rows]) if v.L else None,
                                             host(v.paired[:v.rows]) if v.crn else None,
-                                            host(v.object_lost[:v.rows]) if v.crn else None))
+                                            host(v.object_lost[:v.rows]) if v.crn else None,
+                                            failure={name: host(getattr(v, name)[:v.rows]) for name in
+                                                     v.optional_tables() if name.startswith("failure_")}))
             meta["validation"] = validation_meta(st.val.rows, st.val.fingerprint, st.val.object_names, st.val.settings)
     write_checkpoint(path, arrays, meta)
 
 
 def validation_arrays(table, header, best_params, objects, levels=None, robust=None, paired=None,
-                      object_lost=None) -> Dict[str, np.ndarray]:
+                      object_lost=None, failure=None) -> Dict[str, np.ndarray]:
     """The checkpoint's optional validation arrays (levels / robust: a plan with noise levels;
-    paired / object_lost: one with common random numbers)."""
+    paired / object_lost: one with common random numbers; failure: name -> array of the failure
+    tables of a plan with failure modes)."""
     out = {"val_table": table, "val_header": header, "val_best_params": best_params, "val_objects": objects}
     if levels is not None:
         out.update(val_levels=levels, val_robust=robust)
     if paired is not None:
         out.update(val_paired=paired, val_object_lost=object_lost)
+    for name, array in (failure or {}).items():
+        out["val_" + name] = array
     return out
 
 
@@ -1040,12 +1219,16 @@ def validation_log_of_checkpoint(arrays: Dict[str, np.ndarray], meta: Dict[str, 
         return None
     noise = v["fingerprint"].get("noise_levels")  # absent: a plan without levels, or an older file
     crn = noise is not None and bool(v["fingerprint"].get("common_random_numbers"))  # absent likewise
+    failures = v["fingerprint"].get("failure_modes") is not None  # absent likewise
     return ValidationLog(arrays["val_table"], val_header_dict(arrays["val_header"]), arrays["val_objects"],
                          v["object_names"], v.get("settings"), noise_levels=noise,
                          levels=arrays["val_levels"] if noise is not None else None,
                          robust=arrays["val_robust"] if noise is not None else None,
                          paired=arrays["val_paired"] if crn else None,
-                         object_lost=arrays["val_object_lost"] if crn else None)
+                         object_lost=arrays["val_object_lost"] if crn else None,
+                         failure_modes=arrays["val_failure_modes"] if failures else None,
+                         failure_levels=arrays["val_failure_levels"] if failures else None,
+                         failure_transitions=arrays["val_failure_transitions"] if failures and crn else None)
 
 
 def load_checkpoint(cls, path, env):
@@ -1100,6 +1283,9 @@ def load_checkpoint(cls, path, env):
                 if val.crn:
                     put(val.paired[:val.rows], "val_paired")
                     put(val.object_lost[:val.rows], "val_object_lost")
+                for name in val.optional_tables():
+                    if name.startswith("failure_"):
+                        put(getattr(val, name)[:val.rows], "val_" + name)
             put(val.header, "val_header")
             put(val.best_params, "val_best_params")
     torch.cuda.synchronize(dev)

@@ -1452,6 +1452,117 @@ int dxrl_pg_val_paired_partial_doubles(int32_t num_levels, int64_t num_objects, 
                                        int64_t* out);
 int dxrl_pg_val_paired_row(int32_t device, const dxrl_pg_val_paired_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Failure-mode rows of a validation run (csrc/dxrl_pg_val_failure.hip): how the live actor fails,
+ * per noise level.  Enqueued last on the validation's stream, behind dxrl_pg_val_row or
+ * dxrl_pg_val_levels_row (and dxrl_pg_val_paired_row when that runs), on the same level-major
+ * records plus the five history words of every episode (dxrl_eval_args.hist_moments: S1, S2,
+ * first-five sum F, last-five sum L, peak).  A validation without noise levels is L = 1.  It reads
+ * the records and writes tables of its own; the header, the tables of the other rows and keep-best
+ * are not touched.
+ *
+ * Every episode is classified by the rules of dxrl_failure_summarize above (one statement of
+ * them, csrc/dxrl_failure_rules.h) in its hist_moments form: n = ep_length clamped to
+ * [0, max_steps], timeout_steps the bound of rule 1, and a tie row is included as the exact
+ * comparison decides.  Its class is 0 for a success and 1 + m for failure mode m (list(FailureMode)
+ * order, as ep_mode has it).
+ *
+ * failure_modes[row][l][m] (DXRL_PG_VAL_FAILURE_MODE_COLS columns, enum dxrl_pg_val_failure_mode_col),
+ * formed in f64 from exact integer sums over the episodes of mode m in level l: c their number,
+ * S1 / S2 the sums of ep_length and its square, C1 the sum of ep_contacts, F the failures of the
+ * level, n = G K:
+ *   count                 c
+ *   frequency             F > 0 ? c / F : 0
+ *   episode_share         c / n
+ *   mean_episode_length   c > 0 ? S1 / c : 0
+ *   std_episode_length    c > 0 ? sqrt((double)(c S2 - S1 S1) / (double)(c c)) : 0, the integer
+ *                         expressions in i64 (np.std; exactly 0 when all lengths are equal)
+ *   mean_final_contacts   c > 0 ? C1 / c : 0
+ *   mean_confidence       c > 0 ? (sum of the confidences) / c : 0
+ *   objects               objects with at least one episode of this mode (object o holds records
+ *                         o K .. o K + K - 1 of the level)
+ *   max_object_count      the most episodes of this mode one object has
+ *   worst_object          the first object with that count, -1 when c = 0
+ * failure_levels[row][l] (DXRL_PG_VAL_FAILURE_LEVEL_COLS columns, enum dxrl_pg_val_failure_level_col):
+ *   episodes n, failures F, failure_rate F / n, dominant_mode (the first mode with the largest
+ *   count, -1 when F = 0), dominant_frequency (F > 0 ? that count / F : 0), modes_present (modes
+ *   with c > 0), tie_rows, mean_confidence (F > 0 ? (the six modes' confidence sums added in mode
+ *   order) / F : 0).
+ * failure_transitions i32 [cap][L][7][7] (nullable; written only when `paired` is set, which needs
+ * the episode launch to have run with stream_period = G K): entry [l][from][to] counts the pairs i
+ * whose baseline record i has class `from` and whose record l G K + i has class `to`.  Level 0 is
+ * paired with itself, so its table is diagonal.  Exact.
+ *
+ * With c S2 < 2^62 the i64 expression cannot overflow: ep_length <= max_steps <=
+ * DXRL_SUMMARY_MAX_STEPS asks for G K <= DXRL_PG_VAL_FAILURE_MAX_EPISODES.  The integer sums are
+ * exact in any order.  The confidence sum is a float sum in dxrl_pg_val_row's fixed order: four
+ * consecutive records per thread, lanes by shuffles, waves and workgroup partials in index order.
+ * Two launches whatever L is: reduce (val_grid(G, K) workgroups x L), finish (one workgroup, one
+ * wave per level).  No floating-point atomics; the same inputs give the same bytes.
+ * DXRL_E_INVALID before any launch, outputs untouched: null args or required pointer (the records,
+ * hist_moments, partial, failure_modes, failure_levels), L outside [1, DXRL_PG_VAL_MAX_LEVELS], G or
+ * K < 1, L G K above INT32_MAX, G K above DXRL_PG_VAL_FAILURE_MAX_EPISODES, max_steps outside
+ * [1, DXRL_SUMMARY_MAX_STEPS], timeout_steps < 1, row outside [0, cap), partial_doubles smaller than
+ * dxrl_pg_val_failure_partial_doubles(L, G, K), paired set with a null failure_transitions.
+ * ------------------------------------------------------------------------ */
+#define DXRL_PG_VAL_FAILURE_MAX_EPISODES (1 << 19) /* G K above it -> DXRL_E_INVALID */
+#define DXRL_PG_VAL_FAILURE_CLASSES 7               /* success, then the DXRL_FAILURE_MODES modes */
+#define DXRL_PG_VAL_FAILURE_MODE_COLS 10
+enum dxrl_pg_val_failure_mode_col {
+    DXRL_PG_VAL_FAILURE_COUNT = 0,
+    DXRL_PG_VAL_FAILURE_FREQUENCY,
+    DXRL_PG_VAL_FAILURE_EPISODE_SHARE,
+    DXRL_PG_VAL_FAILURE_MEAN_EPISODE_LENGTH,
+    DXRL_PG_VAL_FAILURE_STD_EPISODE_LENGTH,
+    DXRL_PG_VAL_FAILURE_MEAN_FINAL_CONTACTS,
+    DXRL_PG_VAL_FAILURE_MEAN_CONFIDENCE,
+    DXRL_PG_VAL_FAILURE_OBJECTS,
+    DXRL_PG_VAL_FAILURE_MAX_OBJECT_COUNT,
+    DXRL_PG_VAL_FAILURE_WORST_OBJECT,
+    DXRL_PG_VAL_FAILURE_MODE_NAMED /* == DXRL_PG_VAL_FAILURE_MODE_COLS */
+};
+#define DXRL_PG_VAL_FAILURE_LEVEL_COLS 8
+enum dxrl_pg_val_failure_level_col {
+    DXRL_PG_VAL_FAILURE_LEVEL_EPISODES = 0,
+    DXRL_PG_VAL_FAILURE_LEVEL_FAILURES,
+    DXRL_PG_VAL_FAILURE_LEVEL_FAILURE_RATE,
+    DXRL_PG_VAL_FAILURE_LEVEL_DOMINANT_MODE,
+    DXRL_PG_VAL_FAILURE_LEVEL_DOMINANT_FREQUENCY,
+    DXRL_PG_VAL_FAILURE_LEVEL_MODES_PRESENT,
+    DXRL_PG_VAL_FAILURE_LEVEL_TIE_ROWS,
+    DXRL_PG_VAL_FAILURE_LEVEL_MEAN_CONFIDENCE,
+    DXRL_PG_VAL_FAILURE_LEVEL_NAMED /* == DXRL_PG_VAL_FAILURE_LEVEL_COLS */
+};
+
+typedef struct dxrl_pg_val_failure_args {
+    int64_t num_objects;             /* G                                                    */
+    int64_t episodes_per_object;     /* K                                                    */
+    int64_t row;                     /* table row this call writes, 0 <= row < cap           */
+    int64_t cap;                     /* rows of the tables                                   */
+    int64_t partial_doubles;         /* f64 elements of partial                              */
+    int32_t num_levels;              /* L, 1 .. DXRL_PG_VAL_MAX_LEVELS                       */
+    int32_t paired;                  /* 0 / 1: write failure_transitions                     */
+    int32_t max_steps;               /* the history bound n is clamped to (1 .. DXRL_SUMMARY_MAX_STEPS) */
+    int32_t timeout_steps;           /* the timeout bound of rule 1                          */
+    int32_t success_threshold;       /* rule 6                                               */
+    int32_t reserved;
+    /* device inputs */
+    const int32_t* ep_length;        /* i32 [L G K]                                          */
+    const uint8_t* ep_success;       /* u8  [L G K]                                          */
+    const uint8_t* ep_contacts;      /* u8  [L G K]                                          */
+    const int32_t* hist_moments;     /* i32 [L G K][5] S1, S2, F, L, peak                    */
+    /* device scratch and outputs */
+    double*  partial;                /* f64 [partial_doubles] scratch (its own)              */
+    double*  failure_modes;          /* f64 [cap][L][6][DXRL_PG_VAL_FAILURE_MODE_COLS]       */
+    double*  failure_levels;         /* f64 [cap][L][DXRL_PG_VAL_FAILURE_LEVEL_COLS]         */
+    int32_t* failure_transitions;    /* i32 [cap][L][7][7] (nullable unless paired)          */
+} dxrl_pg_val_failure_args;
+
+/* f64 elements of dxrl_pg_val_failure_row's `partial` scratch for L levels of G objects x K episodes. */
+int dxrl_pg_val_failure_partial_doubles(int32_t num_levels, int64_t num_objects, int64_t episodes_per_object,
+                                        int64_t* out);
+int dxrl_pg_val_failure_row(int32_t device, const dxrl_pg_val_failure_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

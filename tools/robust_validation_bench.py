@@ -25,6 +25,13 @@ runs fit(--paired-iters, validation=the CRN plan) and prints, for the last valid
 and every level, return_diff_std and paired_degradation_stderr from the device's paired table
 beside the same formulas applied on the host to the records of the plan without common random
 numbers (independent episodes per level): the variance reduction the pairing buys.
+
+--failure-modes is another arm of its own (with --profile: the validated fit runs the levels plan
+with common random numbers and failure_modes=True).  On one trainer it alternates, over the
+repeats, plan.run back to back for the CRN levels plan without and with failure_modes (device
+events), then fit(--iters, validate_every=--every) with each of the two plans (host clock and
+device events), and prints the last validation's dominant mode per level.  A commit that has no
+failure_modes option (the parent of the one that added it) runs the arms it has.
 """
 import argparse
 import json
@@ -98,6 +105,68 @@ def paired_arm(a, tr, plan, crn, score, torch):
     return res
 
 
+def failure_arm(a, tr, crn, with_modes, score, torch):
+    from dexterous_rl_manipulation_amd import training_run as run
+    tr.fit(a.warmup)
+    plans = {"crn": crn}
+    if with_modes is not None:
+        plans["crn_failure_modes"] = with_modes
+    arms = {k: (pl, run._ValState(tr, pl.fingerprint, pl.object_names)) for k, pl in plans.items()}
+    for pl, val in arms.values():
+        pl.run(tr, val, 0, 0, 0)
+    torch.cuda.synchronize()
+    alone = {k: [] for k in arms}
+    for _ in range(a.repeats):
+        for name, (pl, val) in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            val.rows = 0  # the tables are scratch here
+            e0.record()
+            for _ in range(10):
+                pl.run(tr, val, 0, 0, 0)
+            e1.record()
+            e1.synchronize()
+            alone[name].append(e0.elapsed_time(e1) / 10)
+    # fit per iteration with the levels validation in both settings: one trainer per plan (a run's
+    # validation table belongs to one plan), alternated
+    from dexterous_rl_manipulation_amd import workloads
+    fits, wall, events = {}, {k: [] for k in plans}, {k: [] for k in plans}
+    for name, pl in plans.items():
+        _, t = workloads.build_pg_workload("easy", tr.dev, envs=a.envs, horizon=a.horizon)
+        kw = {} if name == "crn" else dict(failure_modes=True)
+        fits[name] = (t, t.validation_plan(a.heldout, episodes_per_object=a.episodes, seed=0, device_seed=0,
+                                           noise_levels=crn.noise_levels, common_random_numbers=True, **kw))
+        t.fit(a.warmup, validation=fits[name][1], validate_every=a.every, val_keep_best=score)
+    torch.cuda.synchronize()
+    for _ in range(a.repeats):
+        for name, (t, pl) in fits.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            log = t.fit(a.iters, validation=pl, validate_every=a.every, val_keep_best=score)
+            e1.record()
+            torch.cuda.synchronize()
+            wall[name].append((time.perf_counter() - t0) * 1e3 / a.iters)
+            events[name].append(e0.elapsed_time(e1) / a.iters)
+    res = {"envs": a.envs, "horizon": a.horizon, "iters": a.iters, "validate_every": a.every, "repeats": a.repeats,
+           "objects": a.objects, "episodes_per_object": a.episodes, "levels": len(crn.noise_levels),
+           "validation_episodes": crn.E, "device": torch.cuda.get_device_name(tr.dev)}
+    for name in plans:
+        t, w, e = alone[name], wall[name], events[name]
+        res[f"validation_alone_ms_{name}"] = {"median": statistics.median(t), "min": min(t), "max": max(t), "all": t}
+        res[f"fit_{name}"] = {"wall_ms_per_iteration_median": statistics.median(w), "min": min(w), "max": max(w),
+                              "all": w, "event_ms_per_iteration_median": statistics.median(e)}
+    if with_modes is not None:
+        res["failure_modes_minus_crn_us_per_validation"] = 1e3 * (
+            res["validation_alone_ms_crn_failure_modes"]["median"] - res["validation_alone_ms_crn"]["median"])
+        v = log.validation
+        res["last_row"] = {"dominant_mode": v.statistics()["final_dominant_failure_mode"],
+                           "dominant_frequency": v.statistics()["final_dominant_failure_frequency"],
+                           "failure_rate": v.statistics()["final_failure_rate"],
+                           "lost_into_mode_worst_level": v.failure_transitions[-1, -1, 0].tolist()}
+    return res
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--iters", type=int, default=30)
@@ -112,6 +181,7 @@ def main():
     p.add_argument("--profile", action="store_true")
     p.add_argument("--common-random-numbers", action="store_true")
     p.add_argument("--paired-iters", type=int, default=200)
+    p.add_argument("--failure-modes", action="store_true")
     a = p.parse_args()
     import torch
     from dexterous_rl_manipulation_amd import CurriculumConfig, workloads
@@ -125,15 +195,22 @@ def main():
     plan = tr.validation_plan(heldout, episodes_per_object=a.episodes, seed=0, device_seed=0, noise_levels=levels)
     score = "worst_success_rate"
     crn = None
-    if a.common_random_numbers:
+    if a.common_random_numbers or a.failure_modes:
         crn = tr.validation_plan(heldout, episodes_per_object=a.episodes, seed=0, device_seed=0, noise_levels=levels,
                                  common_random_numbers=True)
+    with_modes = None
+    if a.failure_modes and "failure_modes" in ValidationPlan.__init__.__code__.co_varnames:
+        with_modes = tr.validation_plan(heldout, episodes_per_object=a.episodes, seed=0, device_seed=0,
+                                        noise_levels=levels, common_random_numbers=True, failure_modes=True)
     if a.profile:
-        tr.fit(a.iters, validation=crn or plan, validate_every=a.every, val_keep_best=score)
+        tr.fit(a.iters, validation=with_modes or crn or plan, validate_every=a.every, val_keep_best=score)
         torch.cuda.synchronize()
         return
     if crn is not None:
-        line = json.dumps(paired_arm(a, tr, plan, crn, score, torch))
+        a.heldout = heldout
+        arm = failure_arm(a, tr, crn, with_modes, score, torch) if a.failure_modes else \
+            paired_arm(a, tr, plan, crn, score, torch)
+        line = json.dumps(arm)
         print(line)
         if a.out:
             os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
