@@ -548,8 +548,9 @@ __device__ __forceinline__ bool finger_lane(int s) { return s < kD && s % kJ == 
 // The contact test d_f < size * 1.5 runs on the squared distance (sqrt_below: bit-exact), and
 // dmin = min_f sqrt_rn(x_f) = sqrt_rn(min_f x_f) (the correctly rounded root is monotone), so one
 // root per row, off the mask's dependency chain; kDmin = false (the contacts of a reset state,
-// ME:176) skips it.
-template <bool kDmin = true>
+// ME:176) skips it; kRoot = false hands back the minimum SQUARED distance instead (dmin = xm: the
+// caller's consumer takes the one root, the same correctly rounded sqrt on the same operand).
+template <bool kDmin = true, bool kRoot = true>
 __device__ __forceinline__ uint32_t row_contacts(float jp, const double op[3], double size, int s, int gbit,
                                                  double& dmin, float g3[3]) {
     static_assert(kJ == 3 && kF * kJ <= 16, "finger lanes 3 f of a 16-lane row");
@@ -570,7 +571,7 @@ __device__ __forceinline__ uint32_t row_contacts(float jp, const double op[3], d
         xm = x2 < xm ? x2 : xm;
         xm = x3 < xm ? x3 : xm;
         xm = x4 < xm ? x4 : xm;
-        dmin = sqrt(xm);
+        dmin = kRoot ? sqrt(xm) : xm;
     } else {
         dmin = 0.0;
     }

@@ -328,7 +328,7 @@ struct WsSamplers {
     double lo[256], span[256];
 };
 struct WsReward {      // an env's dense-reward inputs and episode end of one step
-    double dmin;
+    double dmin;       // minimum finger distance; its square where the aux twin takes the root (kXm)
     uint32_t c, prev;  // contacts, previous contacts (0x100: none)
     float nacc[kF];    // per finger: sum of its negative joint positions
     int32_t len;       // episode length after the step
@@ -391,6 +391,15 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
     // (rollout_time A/B, profiles/r04/ab_rollout_wave_priority.log)
     constexpr int kPrio = DXRL_WS_PRIO >= 0 ? DXRL_WS_PRIO : (kNoise ? 1 : 0);
     constexpr bool kObsInP4 = DXRL_WS_OBS_IN_P4 != 0 && !kNoise;
+    // Two moves of work off the wave that sets a phase's length, in the instantiations without
+    // fused noise (per-wave stamps and interleaved A/Bs: DESIGN section 2, profiles/r07/):
+    //   kXm: the env lanes leave the minimum SQUARED finger distance in WsReward and the aux twin,
+    //     the shorter wave of the SIMD in P4, takes the f64 root in front of settle's exp -- the
+    //     same correctly rounded sqrt on the same operand;
+    //   kHeadFirst: the head wave issues its object update after the mu head's MFMA chain, in the
+    //     chain's latency shadow, not in front of it.
+    // With fused noise the aux waves are P4's longer twins already (the root there: +0.4 %).
+    constexpr bool kXm = !kNoise, kHeadFirst = !kNoise;
     if (kPrio != 0 && (__builtin_amdgcn_readfirstlane(wave) >= 4) == (kPrio == 2))
         __builtin_amdgcn_s_setprio(1);
     const int et_tid = tid & 255;  // the env lane this thread is (env wave) or twins (aux wave)
@@ -595,7 +604,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
     // ---- aux: the dense reward (RS:50-187) and the episode bookkeeping of a finished step
     const auto settle = [&](int64_t t_) {
         const WsReward& w = RW[t_ & 1][eg];
-        const double dist = exp(-5.0 * w.dmin);
+        const double dist = exp(-5.0 * (kXm ? sqrt(w.dmin) : w.dmin));  // kXm: w.dmin holds the square
         const double con = count_over_f_f64(__popc(w.c));
         float sum = 0.0f;
 #pragma unroll
@@ -691,7 +700,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
             row_object(opd, op3);
             double dmin;
             float g3[3];
-            const uint32_t c = row_contacts(jp, op3, size, s, gbit, dmin, g3);
+            const uint32_t c = row_contacts<true, !kXm>(jp, op3, size, s, gbit, dmin, g3);
             // the reward's inputs for the aux twin (RS:101-187)
             WsReward& rw = RW[t & 1][eg];
             float nacc = 0.0f;
@@ -768,8 +777,9 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
             p.dyn_noise_tape[m * kActPad + s] = (dyn_noise && s < kAct) ? p.dyn_noise * DR.dzn[et_tid] : 0.0f;
     };
 
-    // diag & 128: s_memtime segment stamps per step (diagnostics only): env waves into
-    // stamps[16 i + k], aux waves into stamps[16 i + 8 + k]
+    // diag & 128: s_memtime segment stamps per step (diagnostics only), one record per wave:
+    // wave w of workgroup g into stamps[(8 g + w) 8 + k], so the longest wave of a phase can be
+    // read off (tools/rollout_stamps.py)
     unsigned long long st_acc[8], st_last = 0;
 #pragma unroll
     for (int q = 0; q < 8; ++q) st_acc[q] = 0;
@@ -810,7 +820,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
         if (mlp) wave_layer16<kH / 32, 2, true, true>(H1, kHsW, w2frag, 32 * wave, H2, kHsW, lane, b2_reg);
         WS_STAMP(2);
         lds_barrier();
-        if (!aux && live && env_on) env_object_step();
+        if (!aux && live && env_on && !(kHeadFirst && mlp && wave == kHeadWave)) env_object_step();
         if (mlp && wave == kHeadWave) {  // mu head: 16 env rows x head rows 0..15 (15 live)
             f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
             // H2 rows and W3 rows (head outputs) from LDS as 16x16x32 fragments: a ring of 4
@@ -832,6 +842,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
+            if (kHeadFirst && live && env_on) env_object_step();  // behind the chain (see kHeadFirst)
 #pragma unroll
             for (int q = 0; q < 4; ++q) MU[(4 * g16 + q) * (kOut + 1) + r16] = acc[q] + b3_reg;
         }
@@ -869,9 +880,9 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
         WS_STAMP(6);
     }
 #undef WS_STAMP
-    if (kDiag && (p.diag & 128) && s == 0 && live) {
+    if (kDiag && (p.diag & 128) && lane == 0) {  // one record per wave: stamps[(8 group + wave) 8 + k]
 #pragma unroll
-        for (int q = 0; q < 8; ++q) p.stamps[16 * i + (aux ? 8 : 0) + q] = st_acc[q];
+        for (int q = 0; q < 8; ++q) p.stamps[((int64_t)blockIdx.x * kWsWaves + wave) * 8 + q] = st_acc[q];
     }
     if (live && aux) {
         if (T > 0 && env_on) settle(T - 1);
@@ -1618,7 +1629,8 @@ int dxrl_pg_rollout(dxrl_env* env, const void* packed, const float* params, cons
     static int64_t stamps_n = 0;
     if ((a->diag_flags & 128) && stamps_n < n) {
         if (stamps) (void)hipFree(stamps);
-        (void)hipMalloc(&stamps, (size_t)n * 16 * sizeof(unsigned long long));
+        // 16 per env (32-env kernel) or 8 per wave of a 16-env workgroup: both fit (n + 15) 16
+        (void)hipMalloc(&stamps, (size_t)(n + 15) * 16 * sizeof(unsigned long long));
         stamps_n = n;
     }
     p.stamps = stamps;
@@ -1639,30 +1651,31 @@ int dxrl_pg_rollout(dxrl_env* env, const void* packed, const float* params, cons
         else if (diag) hipLaunchKernelGGL((k_pg_rollout_ws<false, true>), grid, block, 0, as_stream(stream), p);
         else hipLaunchKernelGGL((k_pg_rollout_ws<false, false>), grid, block, 0, as_stream(stream), p);
         if (int rc = launch_check("k_pg_rollout_ws")) return rc;
-        if (a->diag_flags & 128) {  // diagnostics: mean cycles per env per step segment, env / aux waves
-            std::vector<unsigned long long> h((size_t)n * 16);
+        if (a->diag_flags & 128) {  // diagnostics: mean cycles per step segment of every wave, env / aux means
+            const int64_t groups = (n + kLsEnvs - 1) / kLsEnvs;
+            std::vector<unsigned long long> h((size_t)groups * kWsWaves * 8);
             (void)hipStreamSynchronize(as_stream(stream));
             (void)hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost);
-            for (int w = 0; w < 2; ++w) {
-                fprintf(stderr, "rollout_ws %s cycles/step:", w ? "aux" : "env");
+            double mean[kWsWaves][7];  // over the workgroups in which the wave has a live env
+            for (int wv = 0; wv < kWsWaves; ++wv)
                 for (int k = 0; k < 7; ++k) {
                     double sum = 0;
-                    for (int64_t e = 0; e < n; ++e) sum += (double)h[e * 16 + 8 * w + k];
-                    fprintf(stderr, " s%d=%.0f", k, sum / n / a->horizon);
+                    int64_t cnt = 0;
+                    for (int64_t g = 0; g < groups; ++g)
+                        if (g * kLsEnvs + 4 * (wv & 3) < n) {
+                            sum += (double)h[(size_t)(g * kWsWaves + wv) * 8 + k];
+                            ++cnt;
+                        }
+                    mean[wv][k] = cnt ? sum / cnt / a->horizon : 0.0;
                 }
+            for (int w = 0; w < 2; ++w) {
+                fprintf(stderr, "rollout_ws %s cycles/step:", w ? "aux" : "env");
+                for (int k = 0; k < 7; ++k)
+                    fprintf(stderr, " s%d=%.0f", k, (mean[4 * w][k] + mean[4 * w + 1][k] + mean[4 * w + 2][k] + mean[4 * w + 3][k]) / 4);
                 fprintf(stderr, "\n");
-                for (int wv = 0; wv < 4; ++wv) {  // per wave of the workgroup (envs 4 wv .. 4 wv + 3)
-                    fprintf(stderr, "  wave %d:", 4 * w + wv);
-                    for (int k = 0; k < 7; ++k) {
-                        double sum = 0;
-                        int64_t cnt = 0;
-                        for (int64_t e = 0; e < n; ++e)
-                            if ((e % kLsEnvs) / 4 == wv) {
-                                sum += (double)h[e * 16 + 8 * w + k];
-                                ++cnt;
-                            }
-                        fprintf(stderr, " s%d=%.0f", k, cnt ? sum / cnt / a->horizon : 0.0);
-                    }
+                for (int wv = 4 * w; wv < 4 * w + 4; ++wv) {
+                    fprintf(stderr, "  wave %d:", wv);
+                    for (int k = 0; k < 7; ++k) fprintf(stderr, " s%d=%.0f", k, mean[wv][k]);
                     fprintf(stderr, "\n");
                 }
             }
