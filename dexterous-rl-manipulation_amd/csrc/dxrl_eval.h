@@ -1,6 +1,8 @@
 // dxrl_eval.h -- what the evaluation episode-program kernels share (dxrl_eval.hip: k_eval /
 // k_eval_ls, the reference's three policies; dxrl_eval_mlp.hip: k_eval_mlp, the frozen MLP actor):
-// the launch parameters, the noise stream id and the lane-split geometry.
+// the launch parameters, the noise stream id, the history moments and the lane-split geometry.
+// The lane-split episode program itself (k_eval_ls, k_eval_mlp) and the host side of the two
+// entry points are in dxrl_eval_row.h.
 #pragma once
 #include "dxrl_internal.h"
 

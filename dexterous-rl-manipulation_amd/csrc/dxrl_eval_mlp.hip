@@ -1,8 +1,8 @@
 // dxrl_eval_mlp.hip -- evaluation episode programs of the frozen MLP actor (DXRL_EVAL_POLICY_MLP).
 //
-// k_eval_mlp runs the episode programs of k_eval_ls (dxrl_eval.hip: a row of 16 lanes per env, 16
-// rows per workgroup, rows fed from the caller's work-queue counter; same segments, episodes,
-// reset and noise tapes, records, histories, trajectories, policy_used and status word) with the
+// k_eval_mlp runs the episode programs of k_eval_ls on the same EvalRow (dxrl_eval_row.h: a row of 16
+// lanes per env, 16 rows per workgroup, rows fed from the caller's work-queue counter; same segments,
+// episodes, reset and noise tapes, records, histories, trajectories, policy_used and status word) with the
 // action of every step computed by PGTrainer's actor, obs(45) -> 256 -> 256 -> mu(15), from the
 // observation the evaluation loop hands its policy (evaluator.py:136-141; inside
 // CombinedNoiseWrapper the noisy one, robustness_tests.py:199-207).  The 16 rows of a workgroup
@@ -22,7 +22,7 @@
 // Weights: W1 [256][64] and W3 rows 0..15 stay in LDS for the launch; wave w keeps its 64-column
 // slab of W2 (32 KiB, 128 VGPRs per lane) in registers as k_pg_rollout does; the layer-2 and head
 // biases come from the f32 master.
-#include "dxrl_eval.h"
+#include "dxrl_eval_row.h"
 #include "dxrl_pg.h"
 #include "dxrl_pg_mlp.h"
 #include "dxrl_pg_rollout.h"
@@ -60,11 +60,9 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
     __shared__ int ALIVE[2];
     const dxrl_eval_args& a = p.a;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int s = tid & 15, row = tid >> 4, gbit = 16 * ((tid & 63) >> 4);
+    EvalRow r(a, tid);
+    const int s = r.s, sa = r.sa, row = tid >> 4;
     const int r16 = lane & 15, g16 = lane >> 4;  // 16x16x32 fragment row / k group (row == 4 wave + g16)
-    const int sa = s < kD ? s : 0;
-    const int s2 = s < DXRL_RESET_EXTRA ? s : 0;
-    const bool ntape = a.noise_tape != nullptr;
     // stream period P > 0: the device streams of lane, segment and record i are keyed by i % P
     // (the entry point refuses the tapes then).  Taken once per lane, segment and episode in part A.
     // The three indices are i32 counts, so the entry point launches a period above INT32_MAX,
@@ -108,38 +106,11 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
     const float b3_reg = w.params[kOffW3a + (int64_t)r16 * kHx + kH];
     const float stdv = kMode != kMlpDet ? w.std[sa] : 0.0f;
 
-    // A row's place in its program.  kStep: an episode is running and its observation row is in X;
-    // kDone: the queue is empty.  The others are resolved in part A of the step loop.
-    enum { kNeedLane, kNeedSeg, kNeedEp, kEmit, kEndEp, kFinish, kStep, kDone };
-    int phase = kNeedLane, after = kStep;  // after: the phase that follows kEmit
-    int ln = 0, si = 0, s1 = 0, ep = 0, step = 0;
-    bool ok = true;
-    // policy stream (tape cursor or Philox counter) and noise stream of the current segment
-    int64_t pcur = 0, ncur = 0, navail = 0;
-    uint64_t pctr = 0, nctr = 0, octr = 0;
-    bool pok = true, nok = true;
-    uint32_t pk0 = 0, pk1 = 0, nk0 = 0, nk1 = 0;
-    const double* ptape = nullptr;
-    const double* ntp = nullptr;
-    double dyn_sigma = 0.0, obs_sigma = 0.0;
-    bool obs_noise = false, dyn_noise = false;
-    int first_ep = 0, n_eps = 0, cfg = 0;
-    double lo2 = 0.0, hi2 = 0.0, cst2 = 0.0;
-    bool has2 = true, fric64 = false;
-    // env (lane-split)
-    float jp = 0.0f, jv = 0.0f, ovd = 0.0f;
-    double opd = 0.0, size = 0.0;
-    double fric = 0.0;
-    uint32_t flags = 0;
-    int32_t et = 0;
-    int64_t rec = 0;
-    float *otraj = nullptr, *atraj = nullptr;
-    uint8_t* hist = nullptr;
-    HistAcc hm{0u, 0u};
-    double ret = 0.0;
-    bool te = false;
-    uint32_t nc = 0;
-    int steps = 0;
+    // A row's place in its program is r.phase (EvalPhase).  kStep: an episode is running and its
+    // observation row is in X; kDone: the queue is empty.  The others are resolved in part A of the
+    // step loop, one transition of the row's program per pass.
+    int after = kStep;  // the phase that follows kEmit
+    uint64_t octr = 0;  // observation-noise blocks taken from the segment's Philox stream
     // the pending observation (kEmit): trajectory slot, noise-tape position, "the tape has it"
     float* emit_dst = nullptr;
     int64_t emit_noff = 0;
@@ -165,152 +136,35 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
     // row sets ALIVE and the workgroup leaves.
     for (int par = 0;; par ^= 1) {
         // ---- A: every row ends in kStep (observation row in X, draws available) or kDone
-        while (phase != kDone) {
-            if (phase == kStep) {
-                if (kMode == kMlpTape && pcur + kD > a.policy_stride) {  // the tape ran out
-                    pok = false;
-                    phase = kFinish;
+        while (r.phase != kDone) {
+            if (r.phase == kStep) {
+                if (kMode == kMlpTape && r.pcur + kD > a.policy_stride) {  // the tape ran out
+                    r.pok = false;
+                    r.phase = kFinish;
                     continue;
                 }
                 break;
             }
-            if (phase == kNeedLane) {
-                int L = 0;
-                if (s == 0) L = atomicAdd(queue, 1);
-                ln = (int)row_bcast_u32<0>((uint32_t)L);
-                if (ln >= a.num_lanes) {
-                    phase = kDone;
+            if (r.phase == kNeedLane) {
+                r.take_lane(a, queue, kMode == kMlpTape, kMode == kMlpDevice, keyed);
+                if (r.phase == kDone) {
                     *reinterpret_cast<bf16x4*>(X + row * kEmXp + 4 * s) =
                         bf16x4{(bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f};  // an idle row feeds zeros
                     break;
                 }
-                ok = pok = true;
-                pcur = 0;
-                pctr = 0;
-                if (kMode == kMlpTape) ptape = a.policy_tape + (int64_t)ln * a.policy_stride;
-                if (kMode == kMlpDevice) env_key(a.policy_seed, keyed(ln), pk0, pk1);
-                si = a.lane_segments[ln];
-                s1 = a.lane_segments[ln + 1];
-                phase = kNeedSeg;
-            } else if (phase == kFinish) {  // the lane's end
-                if (!pok) ok = false;
-                if (s == 0) {
-                    if (a.policy_used) a.policy_used[ln] = (int32_t)pcur;
-                    if (!ok && a.status) atomicOr(a.status, 1);
+            } else if (r.phase == kFinish) {
+                r.finish_lane(a);
+            } else if (r.phase == kNeedSeg) {
+                r.begin_segment(curricula, p, keyed);
+                octr = 0;
+            } else if (r.phase == kNeedEp) {
+                r.begin_episode(a, keyed, emit_noff, emit_have);
+                if (r.phase == kStep) {
+                    emit_dst = r.otraj;  // slot 0: the reset observation
+                    after = kStep;
+                    r.phase = kEmit;
                 }
-                phase = kNeedLane;
-            } else if (phase == kNeedSeg) {  // the next segment of the lane (si), or the lane's end
-                if (!ok || si >= s1) {
-                    phase = kFinish;
-                    continue;
-                }
-                const dxrl_eval_segment sg = a.segments[si];
-                const bool noisy = sg.obs_noise_std > 0.0 || sg.dyn_noise_std > 0.0;
-                if (sg.curriculum_row < 0 || sg.curriculum_row >= p.n_curricula || sg.first_episode < 0 ||
-                    (ntape && noisy && sg.noise_offset < 0)) {
-                    ok = false;
-                    phase = kFinish;
-                    continue;
-                }
-                cfg = sg.curriculum_row;
-                const dxrl_curriculum& cu = curricula[cfg];
-                const double* rg = s2 == 0 ? cu.size_range
-                                           : s2 == 1 ? cu.mass_range
-                                                     : s2 == 2 ? cu.friction_range
-                                                               : s2 == 3 ? cu.spawn_x_range
-                                                                         : s2 == 4 ? cu.spawn_y_range : cu.spawn_z_range;
-                lo2 = rg[0];
-                hi2 = rg[1];
-                cst2 = s2 == 0 ? cu.object_size : s2 == 1 ? cu.object_mass : cu.friction_coefficient;
-                has2 = s2 == 0 ? cu.has_size_range != 0
-                               : s2 == 1 ? cu.has_mass_range != 0 : s2 == 2 ? cu.has_friction_range != 0 : true;
-                fric64 = cu.friction_is_f64_scalar != 0;
-                nok = true;
-                if (ntape) {
-                    ntp = a.noise_tape + sg.noise_offset;
-                    navail = sg.noise_count;
-                    ncur = 0;
-                } else {
-                    env_key(a.noise_seed, keyed(si), nk0, nk1);
-                    nctr = 0;
-                    octr = 0;
-                }
-                obs_noise = sg.obs_noise_std > 0.0;
-                dyn_noise = sg.dyn_noise_std > 0.0;
-                dyn_sigma = sg.dyn_noise_std;
-                obs_sigma = sg.obs_noise_std;
-                first_ep = sg.first_episode;
-                n_eps = sg.num_episodes;
-                // DexterousManipulationEnv(curriculum_config=row) (EV:94-98, RT:266-270)
-                jp = jv = 0.0f;
-                opd = s < 3 ? p.obj[s] : 0.0;
-                ovd = 0.0f;
-                flags = p.has_object ? kHasObject : 0u;
-                et = 0;
-                ep = 0;
-                phase = kNeedEp;
-            } else if (phase == kNeedEp) {
-                if (ep >= n_eps) {  // end of the segment
-                    if (!nok) ok = false;
-                    ++si;
-                    phase = kNeedSeg;
-                    continue;
-                }
-                rec = (int64_t)first_ep + ep;
-                if (rec >= a.total_episodes) {
-                    ok = false;
-                    phase = kFinish;
-                    continue;
-                }
-                // env.reset(seed=episode_seed) (EV:127, RT:281) [+ wrapper obs noise, RT:193-197]
-                emit_noff = 0;
-                emit_have = true;
-                if (ntape && obs_noise) {
-                    emit_have = ncur + kObs <= navail;
-                    if (!emit_have) nok = false;
-                    emit_noff = ncur;
-                    ncur += kObs;
-                }
-                double u1, v2;
-                if (a.reset_tape) {
-                    u1 = a.reset_tape[rec * kReset + sa];
-                    v2 = has2 ? a.reset_tape[rec * kReset + kD + s2] : cst2;
-                } else {
-                    uint32_t rk0, rk1;
-                    env_key(a.reset_seed, keyed(rec), rk0, rk1);
-                    u1 = -0.1 + (0.1 - -0.1) * reset_uniform_at(sa, rk0, rk1, 0);
-                    v2 = has2 ? lo2 + (hi2 - lo2) * reset_uniform_at(kD + s2, rk0, rk1, 0) : cst2;
-                }
-                jp = s < kD ? (float)u1 : 0.0f;  // ME:143-145 .astype(float32)
-                jv = 0.0f;
-                size = row_bcast<0>(v2);
-                fric = row_bcast<2>(v2);
-                const double sx = row_bcast<3>(v2), sy = row_bcast<4>(v2), sz = row_bcast<5>(v2);
-                const double spawn = s == 1 ? sy : (s == 2 ? sz : sx);
-                const bool has = (flags & kHasObject) != 0;  // ME:156-161 sticky position
-                if (s < 3) {
-                    opd = (double)(float)(has ? opd : spawn);
-                    ovd = 0.0f;
-                }
-                et = 0;
-                flags = kOpIsF32 | kHasObject | (fric64 ? kFricF64 : 0u);
-                double op3[3], dmin;
-                float g3[3];
-                row_object(opd, op3);
-                flags |= row_contacts<false>(jp, op3, size, s, gbit, dmin, g3);  // ME:176 (no dmin)
-                otraj = a.obs_traj ? a.obs_traj + rec * (int64_t)(a.max_steps + 1) * kObs : nullptr;
-                atraj = a.act_traj ? a.act_traj + rec * (int64_t)a.max_steps * kD : nullptr;
-                hist = a.contact_hist ? a.contact_hist + rec * a.max_steps : nullptr;
-                hm = HistAcc{0u, 0u};
-                ret = 0.0;
-                te = false;
-                nc = 0;
-                steps = 0;
-                step = 0;
-                emit_dst = otraj;  // slot 0: the reset observation
-                after = kStep;
-                phase = kEmit;
-            } else if (phase == kEmit) {
+            } else if (r.phase == kEmit) {
                 // The observation the policy sees next (ME:254-264 [+ wrapper noise, RT:193-207:
                 // obs + f32(0 + s g)]): the row's lanes stage their elements as f32, lanes 0..11 then
                 // take elements 4 s .. 4 s + 3, add the noise (tape: 45 normals at the segment cursor
@@ -318,39 +172,28 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
                 // counter), write the trajectory slot and the bf16 X row (column 45 = 1, 46.. = 0).
                 // LDS hand-off between the lanes of one row (one wave): program order, no barrier.
                 float* ob = OBSF + row * kEmObsP;
-                if (s < kD) {
-                    ob[s] = jp;
-                    ob[kD + s] = jv;
-                }
-                if (s < 3) {
-                    ob[2 * kD + s] = (float)opd;
-                    ob[2 * kD + 7 + s] = ovd;
-                } else if (s < 7) {
-                    ob[2 * kD + s] = s == 3 ? 1.0f : 0.0f;
-                } else if (s < 7 + kF) {
-                    ob[2 * kD + 10 + (s - 7)] = (float)((flags >> (s - 7)) & 1u);
-                }
+                r.write_obs(ob);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 if (s < 12) {
                     const f32x4 v4 = *reinterpret_cast<const f32x4*>(ob + 4 * s);
                     float v[4] = {v4[0], v4[1], v4[2], v4[3]};
-                    if (obs_noise) {
-                        if (ntape) {
+                    if (r.obs_noise) {
+                        if (r.ntape) {
 #pragma unroll
                             for (int q = 0; q < 4; ++q)
                                 if (emit_have && 4 * s + q < kObs)
-                                    v[q] = v[q] + (float)(0.0 + obs_sigma * ntp[emit_noff + 4 * s + q]);
+                                    v[q] = v[q] + (float)(0.0 + r.obs_sigma * r.ntp[emit_noff + 4 * s + q]);
                         } else {
                             const uint64_t c = octr * 12u + (uint64_t)s;
-                            const u32x4 r = philox(
-                                u32x4{(uint32_t)c, (uint32_t)(c >> 32), kStreamEvalNoise, kEvalObsBlock}, nk0, nk1);
+                            const u32x4 u = philox(
+                                u32x4{(uint32_t)c, (uint32_t)(c >> 32), kStreamEvalNoise, kEvalObsBlock}, r.nk0, r.nk1);
                             float n[4];
-                            box_muller(r.x, r.y, n[0], n[1]);
-                            box_muller(r.z, r.w, n[2], n[3]);
+                            box_muller(u.x, u.y, n[0], n[1]);
+                            box_muller(u.z, u.w, n[2], n[3]);
 #pragma unroll
-                            for (int q = 0; q < 4; ++q) v[q] = v[q] + (float)obs_sigma * n[q];
+                            for (int q = 0; q < 4; ++q) v[q] = v[q] + (float)r.obs_sigma * n[q];
                         }
                     }
                     if (emit_dst) {
@@ -367,24 +210,16 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
                     }
                     *reinterpret_cast<bf16x4*>(X + row * kEmXp + 4 * s) = x;
                 }
-                if (obs_noise && !ntape) ++octr;
+                if (r.obs_noise && !r.ntape) ++octr;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                phase = after;
+                r.phase = after;
             } else {  // kEndEp
-                if (s == 0) {
-                    a.ep_return[rec] = ret;
-                    a.ep_length[rec] = steps;
-                    a.ep_success[rec] = (uint8_t)te;  // success = terminated (EV:157, RT:303)
-                    if (a.ep_contacts) a.ep_contacts[rec] = (uint8_t)nc;
-                    if (a.hist_moments) hist_acc_store(hm, a.hist_moments + 5 * rec);
-                }
-                ++ep;
-                phase = kNeedEp;
+                r.end_episode(a);
             }
         }
-        if (phase == kStep && s == 0) ALIVE[par] = 1;
+        if (r.phase == kStep && s == 0) ALIVE[par] = 1;
         lds_barrier();  // B1
         if (ALIVE[par] == 0) break;
         if (tid == 0) ALIVE[par ^ 1] = 0;
@@ -422,122 +257,28 @@ __global__ __launch_bounds__(kEvalThreads, 1) void k_eval_mlp(const dxrl_curricu
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        if (phase != kStep) continue;  // no barrier inside the row step: the next one is B1
+        if (r.phase != kStep) continue;  // no barrier inside the row step: the next one is B1
         // ---- the policy's action: clip(mu [+ std * draw], -1, 1) (lane s: dim s)
         const float mu = MU[row * kEmMuP + sa];
         float act;
         if (kMode == kMlpDet) {
             act = clipf(mu, -1.0f, 1.0f);
         } else if (kMode == kMlpTape) {
-            const double g = ptape[pcur + sa];  // availability checked in part A
-            pcur += kD;
+            const double g = r.ptape[r.pcur + sa];  // availability checked in part A
+            r.pcur += kD;
             act = clipf(mu + (float)(0.0 + (double)stdv * g), -1.0f, 1.0f);
         } else {  // the Philox policy stream, addressed as k_eval_ls addresses SIMPLE's
-            const uint64_t c = pctr + (uint64_t)(sa >> 2);
-            const u32x4 r = philox(u32x4{(uint32_t)c, (uint32_t)(c >> 32), kStreamPolicy, 0u}, pk0, pk1);
-            float n0, n1;
-            const bool hi = (sa & 2) != 0;
-            box_muller(hi ? r.z : r.x, hi ? r.w : r.y, n0, n1);
-            act = clipf(mu + stdv * ((sa & 1) ? n1 : n0), -1.0f, 1.0f);
-            pctr += (kD + 3) / 4;
+            act = clipf(mu + stdv * row_step_normal(r.pctr, kStreamPolicy, r.pk0, r.pk1, sa), -1.0f, 1.0f);
         }
-        if (atraj && s < kD) atraj[step * kD + s] = act;
-        if (dyn_noise) {  // RT:180-187: clip(a + f32(N(0, s)), low, high)
-            float dz = 0.0f;
-            if (ntape) {
-                if (ncur + kD > navail) {
-                    nok = false;
-                } else {
-                    dz = (float)(0.0 + dyn_sigma * ntp[ncur + sa]);
-                    ncur += kD;
-                }
-            } else {
-                const uint64_t c = nctr + (uint64_t)(sa >> 2);
-                const u32x4 r = philox(u32x4{(uint32_t)c, (uint32_t)(c >> 32), kStreamEvalNoise, 0u}, nk0, nk1);
-                float n0, n1;
-                const bool hi = (sa & 2) != 0;
-                box_muller(hi ? r.z : r.x, hi ? r.w : r.y, n0, n1);
-                dz = (float)dyn_sigma * ((sa & 1) ? n1 : n0);
-                nctr += (kD + 3) / 4;
-            }
-            act = clipf(act + dz, -1.0f, 1.0f);
-        }
-        // ---- env_step, lane-split (ME:198-252), as in k_eval_ls
-        if (s < kD) {
-            const float ak = clipf(act, -1.0f, 1.0f);
-            jv = kC09 * jv + kC01 * ak;
-            jp = clipf(jp + jv * kDt, -1.0f, 1.0f);
-        }
-        {
-            const double damp = 1.0 - (fric * 0.1 * 0.01);
-            const float dampf = (float)damp;
-            const bool op32 = (flags & kOpIsF32) != 0, fric_f64 = (flags & kFricF64) != 0;
-            const int ax = s < 3 ? s : 0;
-            const double gz = ax == 2 ? kGz : 0.0, lo = ax == 2 ? 0.0 : -0.2, hi = ax == 2 ? 0.3 : 0.2;
-            float v = fric_f64 ? (float)((double)ovd * damp) : ovd * dampf;
-            v = (float)((double)v + gz);
-            const float inc = v * kDt;
-            double q = op32 ? (double)((float)opd + inc) : opd + (double)inc;
-            q = clipd(q, lo, hi);
-            if ((q <= lo && v < 0.0f) || (q >= hi && v > 0.0f)) v = 0.0f;
-            if (s < 3) {
-                opd = q;
-                ovd = v;
-            }
-        }
-        flags &= ~kOpIsF32;
-        double op3[3], dmin;
-        float g3[3];
-        row_object(opd, op3);
-        const uint32_t c = row_contacts(jp, op3, size, s, gbit, dmin, g3);
-        double r;
-        if (p.dense) {  // RS:50-187
-            const double dist = exp(-5.0 * dmin);
-            const double con = count_over_f_f64(__popc(c));
-            float nacc = 0.0f;
-#pragma unroll
-            for (int j = 0; j < kJ; ++j)
-                if (g3[j] < 0.0f) nacc = nacc + g3[j];
-            float sum = 0.0f;
-            row_neg_sum_fingers(nacc, sum);  // nacc of finger f on lane 3 f
-            const float avg = div_f(sum);
-            const float clo = clipf(div_f(avg), 0.0f, 1.0f);
-            float st = 0.0f;
-            if (flags & kHasPrev) {
-                const uint32_t prev = (flags >> kPrevShift) & 0xFFu;
-                float ch = 0.0f;
-#pragma unroll
-                for (int f = 0; f < kF; ++f) ch = ch + (float)(((c ^ prev) >> f) & 1u);
-                st = clipf(1.0f - count_over_f_f32((uint32_t)ch), 0.0f, 1.0f);
-            }
-            flags = (flags & ~(0xFFu << kPrevShift)) | (c << kPrevShift) | kHasPrev;
-            r = ((p.w.w_dist * dist + p.w.w_con * con) + p.w.w_clo * (double)clo) + p.w.w_st * (double)st;
-        } else {
-            r = (__popc(c) >= 3) ? 1.0 : -0.01;  // RS:226-231
-        }
-        flags = (flags & ~0xFFu) | c;
-        te = __popc(c) >= 3;                        // ME:332-336
-        const bool tr = et >= p.max_episode_steps;  // ME:245 (before the increment)
-        et += 1;
-        emit_noff = 0;
-        emit_have = true;
-        if (ntape && obs_noise) {
-            emit_have = ncur + kObs <= navail;
-            if (!emit_have) nok = false;
-            emit_noff = ncur;
-            ncur += kObs;
-        }
-        ret += r;  // EV:143 / RT:291 episode_reward += reward
-        steps = step + 1;
-        nc = (uint32_t)__popc(c);
-        if (hist && s == 0) hist[step] = (uint8_t)nc;
-        hist_acc_step(hm, nc, step);
-        // the observation this step returns (trajectory slot step + 1, the policy's next input) is
-        // written by the next part A, then the episode goes on or ends there
-        emit_dst = otraj ? otraj + (int64_t)(step + 1) * kObs : nullptr;
-        ++step;
-        after = (te || tr || step >= a.max_steps) ? kEndEp : kStep;
-        phase = kEmit;
+        if (r.atraj && s < kD) r.atraj[r.step * kD + s] = act;
+        // dynamics noise and the env step; the observation this step returns (trajectory slot
+        // step + 1, the policy's next input) is written by the next part A, then the episode goes on
+        // or ends there
+        const bool over = r.step_env(p, r.dynamics_noise(act), emit_noff, emit_have);
+        emit_dst = r.otraj ? r.otraj + (int64_t)(r.step + 1) * kObs : nullptr;
+        ++r.step;
+        after = (over || r.step >= a.max_steps) ? kEndEp : kStep;
+        r.phase = kEmit;
     }
 }
 
@@ -551,38 +292,21 @@ extern "C" int dxrl_evaluate_mlp(dxrl_env* env, const dxrl_eval_args* args, cons
     DXRL_REQUIRE(mlp->packed && (reinterpret_cast<uintptr_t>(mlp->packed) & 15) == 0,
                  "packed must be a 16-byte aligned bf16 weight pack (dxrl_pg_pack_weights)");
     DXRL_REQUIRE(mlp->params, "null params (f32 master: layer-2 / head biases)");
-    DXRL_REQUIRE(a.num_lanes > 0 && a.num_lanes <= env->cfg.num_envs, "num_lanes must be in [1, num_envs]");
-    DXRL_REQUIRE(a.max_steps > 0 && a.total_episodes >= 0, "max_steps must be > 0, total_episodes >= 0");
-    DXRL_REQUIRE(a.lane_segments && a.segments, "null segment table");
-    DXRL_REQUIRE(a.ep_return && a.ep_length && a.ep_success, "null episode record buffers");
-    DXRL_REQUIRE(!a.hist_moments || a.max_steps <= kHistMomentsMaxSteps,
-                 "hist_moments packs its sums for max_steps <= %d, got %d", kHistMomentsMaxSteps, a.max_steps);
+    if (int rc = eval_check_args(env, a, kEvalChkLanes, kEvalChkMoments)) return rc;
     const bool stochastic = mlp->action_std != nullptr, tape = a.policy_tape != nullptr;
     DXRL_REQUIRE(stochastic || !tape, "a policy tape was given in deterministic mode (action_std == NULL takes no draws)");
-    DXRL_REQUIRE(!tape || a.policy_stride >= 0, "bad policy tape stride");
-    DXRL_REQUIRE(a.work_queue, "null work_queue (device i32[1] scratch of this launch)");
+    if (int rc = eval_check_args(env, a, kEvalChkStride, kEvalChkQueue)) return rc;
     DXRL_REQUIRE(a.stream_period >= 0, "stream_period must be >= 0, got %lld", (long long)a.stream_period);
     DXRL_REQUIRE(a.stream_period == 0 || (!a.policy_tape && !a.noise_tape && !a.reset_tape),
                  "stream_period keys the device Philox streams: it cannot be combined with a parity tape");
-    EvalParams p{weights_of(env->cfg),
-                 env->cfg.max_episode_steps,
-                 env->cfg.reward_type == DXRL_REWARD_DENSE,
-                 env->cfg.has_object_position,
-                 env->n_curricula,
-                 {env->cfg.object_position[0], env->cfg.object_position[1], env->cfg.object_position[2]},
-                 a,
-                 nullptr};
+    EvalParams p = eval_params(env, a);
     const EvalMlpWeights w{static_cast<const bf16*>(mlp->packed), mlp->params, mlp->action_std};
     const int dev = env->device;
     DeviceGuard g(dev);
     hipStream_t st = as_stream(stream);
-    if (int rc = hip_check(hipMemsetAsync(a.work_queue, 0, sizeof(int32_t), st), "eval queue reset")) return rc;
     // one workgroup (16 rows) per CU, as k_eval_ls has by default (and as the register budget asks)
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    int64_t blocks = (a.num_lanes + kEvalRows - 1) / kEvalRows;
-    const int64_t resident = cus > 0 ? cus : 256;
-    if (blocks > resident) blocks = resident;
+    int64_t blocks = 0;
+    if (int rc = eval_queue_grid(a, dev, 1, st, blocks)) return rc;
     const dim3 grid((unsigned)blocks), block(kEvalThreads);
     const bool period = a.stream_period > 0 && a.stream_period <= (int64_t)INT32_MAX;  // no tape then (above)
     if (!stochastic && period)

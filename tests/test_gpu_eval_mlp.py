@@ -6,7 +6,8 @@
 3. row / queue independence (lane order, lane count, repeated and concurrent launches);
 4. moments of the device-stream action noise;
 5. the public API (Evaluator / RobustnessTester / PGTrainer.policy / save + load);
-6. argument checks.
+6. argument checks;
+7. k_eval_mlp against k_eval_ls: a constant actor and a frozen SimpleLearner with the same mean.
 """
 import ctypes as C
 import zlib
@@ -22,7 +23,7 @@ from dexterous_rl_manipulation_amd import evaluator as evr
 
 import eval_mlp_reference as E
 import pg_reference as R
-from test_eval_host import cfg_of, oracle_cur
+from test_eval_host import cfg_of, make_policy, oracle_cur
 
 pytestmark = pytest.mark.gpu
 
@@ -397,3 +398,38 @@ def test_argument_checks_refuse_before_any_launch():
     q.add_lane([evr.Segment(0, [1, 2, 3])])
     with pytest.raises(N.NativeError):
         q.run(sto, policy_tapes=np.zeros((1, 15 * 5)))  # 5 steps of draws for 3 episodes of up to 200
+
+
+# ------------------------------------------------------------------ 7. the two episode kernels
+@pytest.mark.parametrize("reward,seed", [("dense", 0), ("sparse", 0), ("dense", 1), ("sparse", 1)])
+def test_constant_actor_equals_frozen_simple_learner(reward, seed):
+    """k_eval_mlp and k_eval_ls run the same episode for the same action.  The actor has zero
+    weights and hidden biases and head bias b3 = m, so H1 = H2 = tanh(0) = 0 and mu = m exactly;
+    its partner is a frozen SimpleLearner with mean_action = m and exploration_noise = 0 on its
+    device stream, whose action is clip(m + 0 * n), the same value.  17 lanes (a row of the first
+    workgroup refills from the queue), 1-3 segments over two curriculum rows, 1-3 episodes each,
+    dynamics noise 0.1 on about half the segments, reset and noise tapes.  Observation noise
+    stays 0: k_eval_ls records the un-noised observation, k_eval_mlp the one its policy sees.
+    Records, histories, moments and the written trajectories are equal bit for bit."""
+    rng = np.random.default_rng(811 + seed)
+    m = rng.uniform(-0.9, 0.9, 15).astype(np.float32)
+    m[[2, 9, 13]] = np.float32([1.4, -1.25, 1.05])  # beyond the clip
+    params = torch.zeros(R.NPARAMS)
+    R.unpack(params)["W3a"][:R.ACT, R.H] = torch.from_numpy(m)
+    configs = [cfg_of("variable"), cfg_of("hard")] if seed == 0 else [cfg_of("easy"), cfg_of("medium")]
+    p = evr.EpisodeProgram(configs, reward, max_episode_steps=10, max_steps=12)
+    for _ in range(17):
+        p.add_lane([evr.Segment(int(rng.integers(0, 2)), [int(x) for x in rng.integers(0, 10**6, rng.integers(1, 4))],
+                                0.0, 0.1 if rng.random() < 0.5 else 0.0, noise_seed=int(rng.integers(0, 10**6)))
+                    for _ in range(int(rng.integers(1, 4)))])
+    simple = make_policy("simple", m)
+    simple.exploration_noise = 0.0
+    kw = dict(trajectories=True, hist_moments=True)
+    a = p.run(evr.policy_program(E.policy_of(params)), **kw)
+    b = p.run(evr.policy_program(simple), **kw)
+    assert_same_records(a, b, used=False)
+    assert np.array_equal(a.hist_moments, b.hist_moments)
+    if np.all(a.policy_used == 0) and np.all(b.policy_used == 0):
+        assert np.array_equal(a.policy_used, b.policy_used)
+    assert a.ep_length.min() >= 1 and np.all(np.abs(a.act_traj) <= 1.0)
+    assert np.array_equal(a.act_traj[0, 0], np.clip(m, -1.0, 1.0))
