@@ -13,6 +13,8 @@
 // copy of any activation is ever written.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "dxrl_internal.h"
 #include "dxrl_gemm.h"
 
@@ -252,7 +254,8 @@ struct WgradArgs {
     float* out;      // [O][ldo] f32 (splits == 1)
     float* partial;  // [splits][O][I] (splits > 1)
     int64_t ldo;     // output row stride (>= I)
-    int diag;        // timing ablation (DXRL_WGRAD_DIAG): 1 = stream only, no fragment reads / MFMAs
+    int diag;        // timing ablation (DXRL_WGRAD_DIAG).  k_wgrad_glds: 1 = stream only (no fragment reads / MFMAs);
+                     // k_wgrad_l1: 1 = no contraction, 2 = no recompute, 3 = stream only, 4 = no partial-slab stores
     const bf16* W1;  // k_wgrad_l1: [256][64] first-layer weights (X is then the observation matrix)
 };
 
@@ -580,8 +583,10 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_glds(WgradArgs w) {
 // conflict-free.  Waves 0..3 issue every LDS-DMA op of a chunk (each: four dH2 pieces of 2 rows,
 // one piece of 8 observation rows); waves 4..7 issue none (below).  Software-pipelined by one chunk: iteration c recomputes
 // H1(c + 1) into one of two H1 buffers while contracting chunk c against the other, one barrier per
-// chunk; the H1(c + 1) products sit between the two k-steps of chunk c in the MFMA pipe, so their
-// tanh issues on the VALU while the second k-step runs on the matrix cores.
+// chunk.  Between two barriers a wave (a 64 x 128 output tile) runs H1(c + 1)'s four products first,
+// then the sixteen contraction MFMAs with the next k-step's fragment reads and H1(c + 1)'s tanh in
+// their gaps (fragments double-buffered in registers), so neither an LDS burst nor the tanh leaves
+// the matrix pipe idle; chunk c + 1's first dH2 fragments are read before the barrier.
 #ifndef DXRL_WL1_RING
 #define DXRL_WL1_RING 4  // chunk slots (4: 166 us, 5: 174 us per 819 k rows, kernel-level A/B)
 #endif
@@ -606,16 +611,22 @@ __device__ __forceinline__ void glds_x4(const void* src, const void* lds_dst) {
 // 4 (r & 3) term keeps the transposed reads conflict-free (as tr_frag_swz); the (r >> 2) & 3 term
 // spreads the 16 rows of one ds_write_b64 lane group over 8 chunk slots (2-way, not 8-way).
 __device__ __forceinline__ int h1_swz(int row) { return (4 * (row & 3)) ^ ((row >> 2) & 3); }
-__device__ __forceinline__ bf16x8 tr_frag_h1(const bf16* tile, int col0, int kk, int lane) {
+// The transposed fragment of an H1 chunk at byte offset tile_off (a multiple of 512) of the LDS
+// block lds0: rows kk + 8 (g >> 1) + q and + 4, columns col0 + 16 (g & 1) + 4 p (col0 a multiple of
+// 32), tr_frag_swz's lanes.  With t = col0 / 32, x = 2 (g & 1) + (p >> 1) and y = 2 (g >> 1) the
+// swizzled chunk (4 t + x) ^ h1_swz(row) is 4 (t ^ q) + (x ^ y) for the low row and 4 (t ^ q) +
+// (x ^ y ^ 1) for the high one, so every tile's address is ONE lane-constant byte offset XOR
+// 2 col0 (low) or 2 col0 ^ 16 (high): one address register for all eight reads of a k-step, where
+// per-tile offsets took eight.
+__device__ __forceinline__ bf16x8 tr_frag_h1(const char* lds0, int tile_off, int col0, int kk, int lane) {
+    typedef __attribute__((address_space(3))) char lds_char;
     const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int col = col0 + 16 * (g & 1) + 4 * p;
-    lds_bf16* base = (lds_bf16*)(tile);
-    const auto at = [&](int row) {
-        return (lds_bf16x4*)(base + row * 256 + (((col >> 3) ^ h1_swz(row)) << 3) + (col & 7));
-    };
-    const int row = kk + 8 * (g >> 1) + q;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(at(row));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(at(row + 4));
+    const int x = 2 * (g & 1) + (p >> 1), y = 2 * (g >> 1);
+    const int lane_off = (8 * (g >> 1) + q) * 512 + 64 * q + 16 * (x ^ y) + 8 * (p & 1);
+    lds_char* base = (lds_char*)lds0;
+    const int at = tile_off + lane_off;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base + (at ^ (2 * col0)) + kk * 512));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base + (at ^ (2 * col0 ^ 16)) + kk * 512 + 2048));
     bf16x8 v;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -658,7 +669,8 @@ struct WgradPair {
 template <bool kDiag>
 __global__ __launch_bounds__(512, 1) void k_wgrad_l1(WgradPair pr) {
     extern __shared__ __attribute__((aligned(16))) char gsm[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // wave index in an SGPR: the tile, slot and LDS-DMA destination arithmetic below stays scalar
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
     const bool second = (int)blockIdx.x >= pr.nb0;
     const WgradArgs& w = second ? pr.n[1] : pr.n[0];
@@ -682,7 +694,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_l1(WgradPair pr) {
         w1f[k] = *(const __attribute__((address_space(1))) bf16x8*)(w.W1 + (32 * wave + r) * 64 + 16 * k + 8 * h);
 #if DXRL_WL1_DMA_HALF
     // the issuing half: wave q = wave mod 4 loads dH2 rows 8 q .. 8 q + 7 and observation rows 8 q ..
-    const bool dma_wave = __builtin_amdgcn_readfirstlane(wave) < 4;
+    const bool dma_wave = wave < 4;
     const auto wait_in = [&](int n) {
         if (dma_wave) wait_chunks_k<5>(n);
         else __builtin_amdgcn_s_waitcnt(0xF70);
@@ -720,78 +732,159 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_l1(WgradPair pr) {
         }
     };
 #endif
+    // Wave tile: output rows 64 (wave >> 1) .. + 63 x columns 128 (wave & 1) .. + 127, i.e. the output
+    // tiles (ot + a, it + b), a < 2, b < 4, in acc[4 a + b]: two dH2 and four H1 fragments per k-step
+    // (12 transposed reads; a 32 x 256 wave tile took 18).  Every tile still sums its chunks and
+    // k-steps in k_wgrad_glds's order from the same fragments, so the bits are unchanged.
+    const int ot = 2 * (wave >> 1), it = 4 * (wave & 1);
+    const auto frag_a = [&](int c, int hh, int a) {
+        return tr_frag_swz((const bf16*)(gsm + (c % kLNB) * kLSlot), 32 * (ot + a), 16 * hh, lane);
+    };
+    const auto frag_b = [&](int c, int hh, int b) {
+        return tr_frag_h1(gsm, kLH1 + (c & 1) * kLK * 512, 32 * (it + b), 16 * hh, lane);
+    };
     // H1[32 samples][hidden 32 wave ..] of chunk c = tanh(obs W1^T): the fused learner's L1, one tile
-    // (products and tanh split so the caller can put MFMA work between them)
-    const auto recompute_mfma = [&](int c, f32x16& ha) {
+    // per wave.  Observation fragment k (B operand), the four products, then per register pair p the
+    // tanh into hv[p] and the four 8-byte stores -- split so the loop can place each part.  The
+    // swizzled chunk index (2 k + h) ^ s is ((h ^ s) ^ 2 k), and (4 wave + g) ^ s is ((4 wave ^ s) ^ g),
+    // so one element index per lane serves all four fragments / stores: the k or g term is an XOR
+    // on bits the rest of the index leaves alone (four address registers less each).
+    const int o_idx = r * 64 + 8 * (h ^ ((r >> 1) & 7));
+    const int s_idx = r * 256 + (((4 * wave) ^ h1_swz(r)) << 3) + 4 * h;
+    const auto frag_o = [&](int c, int k) {
         const bf16* Os = (const bf16*)(gsm + (c % kLNB) * kLSlot + kLYB);
-        bf16x8 b[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) b[k] = *reinterpret_cast<const bf16x8*>(Os + r * 64 + 8 * ((2 * k + h) ^ ((r >> 1) & 7)));
+        return *reinterpret_cast<const bf16x8*>(Os + (o_idx ^ (16 * k)));
+    };
+    const auto recompute_mfma = [&](const bf16x8 (&ob)[4], f32x16& ha) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) ha[q] = 0.0f;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ha = mfma32(w1f[k], b[k], ha);
+        for (int k = 0; k < 4; ++k) ha = mfma32(w1f[k], ob[k], ha);
     };
-    const auto recompute_store = [&](int c, const f32x16& ha) {
+    // The two empty asm statements tie the pair's VALU work to its place in program order (pure
+    // arithmetic is otherwise free to sink past the gap() fences to its use at the stores).
+    const auto tanh_pair = [&](const f32x16& ha, int p, uint32_t (&hv)[8]) {
+        float x = ha[2 * p], y = ha[2 * p + 1];
+        asm volatile("" : "+v"(x), "+v"(y));
+        const f32x2 t = tanh_pre2(f32x2{x, y}, f32x2{0.0f, 0.0f});
+        typedef bf16 bf16x2 __attribute__((ext_vector_type(2)));
+        hv[p] = __builtin_bit_cast(uint32_t, bf16x2{to_bf16(t.x), to_bf16(t.y)});
+        asm volatile("" : "+v"(hv[p]));
+    };
+    const auto h1_store = [&](int c, const uint32_t (&hv)[8]) {
         bf16* H1 = (bf16*)(gsm + kLH1 + (c & 1) * kLK * 512);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int f0 = 32 * wave + 8 * g + 4 * h;
-            bf16x4 v;
-#pragma unroll
-            for (int u = 0; u < 4; u += 2) {
-                const f32x2 t = tanh_pre2(f32x2{ha[4 * g + u], ha[4 * g + u + 1]}, f32x2{0.0f, 0.0f});
-                v[u] = to_bf16(t.x);
-                v[u + 1] = to_bf16(t.y);
-            }
-            *reinterpret_cast<bf16x4*>(H1 + r * 256 + (((f0 >> 3) ^ h1_swz(r)) << 3) + (f0 & 7)) = v;
-        }
-    };
-    // dW2 += dH2(c)^T H1(c), k-step hh (16 samples)
-    const auto contract = [&](int c, int hh) {
-        const bf16* Ys = (const bf16*)(gsm + (c % kLNB) * kLSlot);
-        const bf16* H1 = (const bf16*)(gsm + kLH1 + (c & 1) * kLK * 512);
-        bf16x8 bb[8];
-        const bf16x8 a = tr_frag_swz(Ys, 32 * wave, 16 * hh, lane);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) bb[j] = tr_frag_h1(H1, 32 * j, 16 * hh, lane);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = mfma32(a, bb[j], acc[j]);
+        for (int g = 0; g < 4; ++g) *reinterpret_cast<uint2*>(H1 + (s_idx ^ (8 * g))) = uint2{hv[2 * g], hv[2 * g + 1]};
     };
     constexpr int kLead = kLNB - 1;  // chunks in flight ahead of the one being contracted
+    // The W1 fragments are complete before the first LDS-DMA piece goes out: an explicit vmcnt(0),
+    // and the fragments pass through an empty asm so the compiler's own wait for them lands here too.
+    // Left to their first use it would sit behind pieces the compiler cannot see (inline asm), and
+    // any such wait drains the whole ring.
+    __builtin_amdgcn_s_waitcnt(0xF70);
+    asm volatile("" : "+v"(w1f[0]), "+v"(w1f[1]), "+v"(w1f[2]), "+v"(w1f[3]));
 #pragma unroll
     for (int c = 0; c < kLead; ++c)
         if (c < nch) issue(c);
+    // fragment registers, double-buffered over the two k-steps: fa[hh][a], fb[hh][b]
+    bf16x8 fa[2][2], fb[2][4];
     if (nch > 0) {
         wait_in(min(kLead - 1, nch - 1));  // chunk 0 in
         __builtin_amdgcn_s_barrier();
+        bf16x8 ob[4];
         f32x16 ha;
-        recompute_mfma(0, ha);
-        recompute_store(0, ha);
+        uint32_t hv[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ob[k] = frag_o(0, k);
+        recompute_mfma(ob, ha);
+#pragma unroll
+        for (int p = 0; p < 8; ++p) tanh_pair(ha, p, hv);
+        h1_store(0, hv);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) fa[0][a] = frag_a(0, 0, a);  // chunk 0's dH2 rows are in as well
     }
-    for (int c = 0; c < nch; ++c) {
+    // One chunk: contract chunk c, recompute H1(c + 1) (has_next), one barrier.
+    const auto chunk = [&](int c, auto has_next, auto do_mm, auto do_rc) {
         // chunk c + 1 in (chunks c + 2 .. c + kLead - 1 may still fly); H1(c) complete; chunk c - 1 done
         wait_in(max(0, min(kLead - 2, nch - 2 - c)));
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if (c + kLead < nch) issue(c + kLead);  // into the slot chunk c - 1 released
-        const bool next = c + 1 < nch && !(kDiag && (w.diag & 2)), mm = !(kDiag && (w.diag & 1));
-        if (mm) contract(c, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        constexpr bool kMore = decltype(has_next)::value;
+        constexpr bool next = kMore && decltype(do_rc)::value, mm = decltype(do_mm)::value;
+        bf16x8 ob[4];
         f32x16 ha;
-        if (next) recompute_mfma(c + 1, ha);
-        __builtin_amdgcn_sched_barrier(0);
-        if (mm) contract(c, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (next) recompute_store(c + 1, ha);
+        uint32_t hv[8];
+        // Program order, pinned gap by gap (the compiler may not move anything across gap()): the
+        // reads that had to wait for the barrier (observation rows of chunk c + 1, H1(c) fragments of
+        // k-step 0); the four recompute products with k-step 1's dH2 fragments in their gaps; the
+        // sixteen contraction MFMAs, one H1(c + 1) tanh pair after every even one, k-step 1's H1
+        // fragments after k-step 0's odd ones and the dH2 fragments of chunk c + 1's k-step 0 (landed
+        // since the barrier above) after the last two; the four H1 stores.
+        const auto gap = [] { __builtin_amdgcn_sched_barrier(0); };  // nothing moves across
+        if (next) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ob[k] = frag_o(c + 1, k);
+        }
+        if (mm) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) fb[0][b] = frag_b(c, 0, b);
+        }
+        gap();
+#pragma unroll
+        for (int q = 0; q < 16; ++q) ha[q] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (next) ha = mfma32(w1f[k], ob[k], ha);
+            if (mm && k >= 2) fa[1][k - 2] = frag_a(c, 1, k - 2);
+            gap();
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {  // column tile by column tile: fb[0][b] is free once fb[1][b] is read
+            if (mm) acc[4 * (i & 1) + (i >> 1)] = mfma32(fa[0][i & 1], fb[0][i >> 1], acc[4 * (i & 1) + (i >> 1)]);
+            if (mm && (i & 1)) fb[1][i >> 1] = frag_b(c, 1, i >> 1);
+            if (next && !(i & 1)) tanh_pair(ha, i >> 1, hv);
+            gap();
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (mm) acc[4 * (i & 1) + (i >> 1)] = mfma32(fa[1][i & 1], fb[1][i >> 1], acc[4 * (i & 1) + (i >> 1)]);
+            if (next && !(i & 1)) tanh_pair(ha, 4 + (i >> 1), hv);
+            if (mm && kMore && i >= 6) fa[0][i - 6] = frag_a(c + 1, 0, i - 6);
+            gap();
+        }
+        if (next) h1_store(c + 1, hv);
+    };
+    const auto run = [&](auto do_mm, auto do_rc) {
+        for (int c = 0; c + 1 < nch; ++c) chunk(c, std::true_type{}, do_mm, do_rc);
+        if (nch > 0) chunk(nch - 1, std::false_type{}, do_mm, do_rc);
+    };
+    if constexpr (kDiag) {
+        // each ablation runs its own straight-line copy of the loop: a run-time flag inside the loop
+        // would cut the pinned schedule into pieces (and costs the production kernel time).  Every copy
+        // keeps the stream (LDS-DMA pieces, counted waits, barrier per chunk); what else is left in:
+        switch (w.diag & 3) {
+            // 0: everything (the production loop)
+            case 0: run(std::true_type{}, std::true_type{}); break;
+            // 1, no contraction: the whole H1(c + 1) recompute -- 4 observation reads, 4 products, all 8
+            // tanh pairs (16 v_exp_f32 per chunk), 4 H1 stores; no dH2 / H1 fragment reads, no contraction MFMAs
+            case 1: run(std::false_type{}, std::true_type{}); break;
+            // 2, no recompute: all 24 fragment reads and 16 contraction MFMAs (against a stale H1 buffer
+            // after chunk 0); no observation reads, products, tanh or H1 stores
+            case 2: run(std::true_type{}, std::false_type{}); break;
+            // 3, stream only: neither
+            default: run(std::false_type{}, std::false_type{}); break;
+        }
+    } else {
+        run(std::true_type{}, std::true_type{});
     }
     float* dst = w.partial ? w.partial + (int64_t)bx * 256 * 256 : w.out;
     const int64_t ld = w.partial ? 256 : w.ldo;
     if (kDiag && (w.diag & 4)) return;  // ablation: no partial-slab stores
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int i = 32 * j + (lane & 31);
+    for (int i = 0; i < 8; ++i) {
+        const int col = 32 * (it + (i & 3)) + (lane & 31);
 #pragma unroll
-        for (int q = 0; q < 16; ++q) dst[(int64_t)(32 * wave + acc_row(q, lane)) * ld + i] = acc[j][q];
+        for (int q = 0; q < 16; ++q) dst[(int64_t)(32 * (ot + (i >> 2)) + acc_row(q, lane)) * ld + col] = acc[i][q];
     }
 }
 
