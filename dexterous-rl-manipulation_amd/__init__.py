@@ -12,7 +12,8 @@ Drop-in surfaces (same names as the reference modules):
   failure_statistics.{load_failure_logs,compute_failure_distribution,compute_correlations,generate_failure_report,
                       plot_failure_distribution,plot_failure_correlations,run_failure_study},
   robustness_analysis.{analyze_robustness_results,plot_robustness_results,print_robustness_report,
-                       run_robustness_study}
+                       run_robustness_study},
+  reward_comparison.{run_training_comparison,compare_rewards}
 Batched device API: envs.VecEnv, policies.VecSimpleLearner, training.SimpleLearnerRollout,
 trainer.PGTrainer (iteration, fit, checkpoints; training_run.TrainingLog; `python -m ...train`).
 The compute runs in libdxrl.so (HIP, gfx950; C ABI in include/dxrl.h).  No CPU fallback.
@@ -27,6 +28,6 @@ def __getattr__(name):
     import importlib
     if name in ("envs", "policies", "training", "evaluation", "build", "_native", "trainer",
                 "evaluator", "metrics", "curriculum_ablation", "seed_variance", "failure_analysis", "failure_statistics",
-                "robustness_analysis", "training_run", "workloads"):
+                "robustness_analysis", "training_run", "workloads", "reward_comparison"):
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

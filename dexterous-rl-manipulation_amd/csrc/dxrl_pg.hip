@@ -118,6 +118,8 @@ constexpr int kRolloutWaves = 4, kCpw = kH / kRolloutWaves, kNT = kCpw / 32;
 
 constexpr int kW1s = kIn + 8, kW3s = kH + 8;  // LDS-resident W1 [256][72], W3 [32][264]
 
+// kDense: the env's reward (RS:50-187 dense, RS:228-234 sparse), as in every rollout kernel below
+template <bool kDense = true>
 __global__ __launch_bounds__(64 * kRolloutWaves, 1) void k_pg_rollout(PgRolloutArgs p) {
     __shared__ __attribute__((aligned(16))) bf16 W1s[kH * kW1s];
     __shared__ __attribute__((aligned(16))) bf16 W3s[kOut * kW3s];
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(64 * kRolloutWaves, 1) void k_pg_rollout(PgRolloutA
             }
             bool te = false, tr = false;
             double cp[4], r = 0.0;
-            if (!(p.diag & 2)) r = env_step(e, a, true, p.w, p.max_episode_steps, te, tr, cp);
+            if (!(p.diag & 2)) r = env_step(e, a, kDense, p.w, p.max_episode_steps, te, tr, cp);
             ep_ret += r;
             const bool d = !(p.diag & 2) && (te || tr || e.t >= p.max_steps);
             p.rew[m] = (float)r;
@@ -361,7 +363,10 @@ struct WsReward {      // an env's dense-reward inputs and episode end of one st
 #ifndef DXRL_WS_OBS_IN_P4
 #define DXRL_WS_OBS_IN_P4 1
 #endif
-template <bool kNoise, bool kDiag>
+// kDense = false: the sparse reward (RS:228-234) -- settle needs the contacts only, so the env
+// lanes leave dmin, nacc[] and prev unwritten, and they leave the previous-contact bits of the
+// env's flags alone, as env_step does (only dense_reward touches them).
+template <bool kNoise, bool kDiag, bool kDense = true>
 __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p) {
     constexpr int kRows = 32;
     // the env wave running the mu head: the env lanes idle while it runs (wave 0 instead, beside
@@ -601,24 +606,30 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
             *reinterpret_cast<float4*>(p.obs_noise_tape + (row * n + i) * kObsNoiseLd + 4 * s) = v;
         }
     };
-    // ---- aux: the dense reward (RS:50-187) and the episode bookkeeping of a finished step
+    // ---- aux: the reward (dense RS:50-187, sparse RS:228-234) and the episode bookkeeping of a
+    // finished step
     const auto settle = [&](int64_t t_) {
         const WsReward& w = RW[t_ & 1][eg];
-        const double dist = exp(-5.0 * (kXm ? sqrt(w.dmin) : w.dmin));  // kXm: w.dmin holds the square
-        const double con = count_over_f_f64(__popc(w.c));
-        float sum = 0.0f;
+        double r;
+        if constexpr (kDense) {
+            const double dist = exp(-5.0 * (kXm ? sqrt(w.dmin) : w.dmin));  // kXm: w.dmin holds the square
+            const double con = count_over_f_f64(__popc(w.c));
+            float sum = 0.0f;
 #pragma unroll
-        for (int f = 0; f < kF; ++f) sum = sum + (-w.nacc[f]);
-        const float avg = div_f(sum);
-        const float clo = clipf(div_f(avg), 0.0f, 1.0f);
-        float st = 0.0f;
-        if (w.prev != 0x100u) {
-            float ch = 0.0f;
+            for (int f = 0; f < kF; ++f) sum = sum + (-w.nacc[f]);
+            const float avg = div_f(sum);
+            const float clo = clipf(div_f(avg), 0.0f, 1.0f);
+            float st = 0.0f;
+            if (w.prev != 0x100u) {
+                float ch = 0.0f;
 #pragma unroll
-            for (int f = 0; f < kF; ++f) ch = ch + (float)(((w.c ^ w.prev) >> f) & 1u);
-            st = clipf(1.0f - count_over_f_f32((uint32_t)ch), 0.0f, 1.0f);
+                for (int f = 0; f < kF; ++f) ch = ch + (float)(((w.c ^ w.prev) >> f) & 1u);
+                st = clipf(1.0f - count_over_f_f32((uint32_t)ch), 0.0f, 1.0f);
+            }
+            r = ((p.w.w_dist * dist + p.w.w_con * con) + p.w.w_clo * (double)clo) + p.w.w_st * (double)st;
+        } else {
+            r = __popc(w.c) >= 3 ? 1.0 : -0.01;  // RS:228-234
         }
-        const double r = ((p.w.w_dist * dist + p.w.w_con * con) + p.w.w_clo * (double)clo) + p.w.w_st * (double)st;
         ep_ret += r;
         if (s == 0) p.rew[t_ * n + i] = (float)r;
         if (w.done) {
@@ -700,20 +711,24 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
             row_object(opd, op3);
             double dmin;
             float g3[3];
-            const uint32_t c = row_contacts<true, !kXm>(jp, op3, size, s, gbit, dmin, g3);
-            // the reward's inputs for the aux twin (RS:101-187)
+            const uint32_t c = row_contacts<kDense, !kXm>(jp, op3, size, s, gbit, dmin, g3);
+            // the reward's inputs for the aux twin (RS:101-187; sparse: the contacts)
             WsReward& rw = RW[t & 1][eg];
-            float nacc = 0.0f;
+            if constexpr (kDense) {
+                float nacc = 0.0f;
 #pragma unroll
-            for (int j = 0; j < kJ; ++j)
-                if (g3[j] < 0.0f) nacc = nacc + g3[j];
-            if (finger_lane(s)) rw.nacc[s / kJ] = nacc;  // finger f on lane 3 f
-            if (s == 0) {
-                rw.dmin = dmin;
-                rw.c = c;
-                rw.prev = (flags & kHasPrev) ? ((flags >> kPrevShift) & 0xFFu) : 0x100u;
+                for (int j = 0; j < kJ; ++j)
+                    if (g3[j] < 0.0f) nacc = nacc + g3[j];
+                if (finger_lane(s)) rw.nacc[s / kJ] = nacc;  // finger f on lane 3 f
+                if (s == 0) {
+                    rw.dmin = dmin;
+                    rw.c = c;
+                    rw.prev = (flags & kHasPrev) ? ((flags >> kPrevShift) & 0xFFu) : 0x100u;
+                }
+                flags = (flags & ~(0xFFu << kPrevShift)) | (c << kPrevShift) | kHasPrev;
+            } else {
+                if (s == 0) rw.c = c;
             }
-            flags = (flags & ~(0xFFu << kPrevShift)) | (c << kPrevShift) | kHasPrev;
             flags = (flags & ~0xFFu) | c;
             te = __popc(c) >= 3;
             tr = et >= p.max_episode_steps;
@@ -1570,7 +1585,6 @@ int dxrl_pg_rollout(dxrl_env* env, const void* packed, const float* params, cons
     DXRL_REQUIRE(a->obs_rm && a->act && a->logp && a->rew && a->done && a->ep_return && a->ep_count &&
                      a->ep_sum_return && a->ep_sum_length && a->ep_successes,
                  "null tape / episode buffer");
-    DXRL_REQUIRE(env->cfg.reward_type == DXRL_REWARD_DENSE, "the policy-gradient rollout uses the dense reward");
     DXRL_REQUIRE(a->record_cap == 0 || (a->rec_return && a->rec_length && a->rec_success && a->rec_end_step),
                  "record_cap > 0 needs all four record buffers");
     DXRL_REQUIRE(!a->ep_code || (a->max_steps < 16384 && env->cfg.max_episode_steps < 16383),
@@ -1619,9 +1633,12 @@ int dxrl_pg_rollout(dxrl_env* env, const void* packed, const float* params, cons
     DXRL_REQUIRE((reinterpret_cast<uintptr_t>(a->h2_tape) & 15) == 0, "pg_rollout: h2_tape must be 16-byte aligned");
     DXRL_REQUIRE(!a->h2_tape || rollout_kernel(n, a->diag_flags, a->obs_fm != nullptr) != 0,
                  "h2_tape is written by the 16- and 32-env rollout kernels only (dxrl_pg_rollout_kernel)");
+    // the reward follows the env's config: every kernel has a dense and a sparse instantiation
+    const bool dense = env->cfg.reward_type == DXRL_REWARD_DENSE;
     if (a->obs_fm || (a->diag_flags & 16)) {  // feature-major tape / A-B reference: the 64-env kernel
-        hipLaunchKernelGGL(k_pg_rollout, dim3((unsigned)((n + kTile - 1) / kTile)), dim3(64 * kRolloutWaves), 0,
-                           as_stream(stream), p);
+        const dim3 grid((unsigned)((n + kTile - 1) / kTile)), block(64 * kRolloutWaves);
+        if (dense) hipLaunchKernelGGL(k_pg_rollout<true>, grid, block, 0, as_stream(stream), p);
+        else hipLaunchKernelGGL(k_pg_rollout<false>, grid, block, 0, as_stream(stream), p);
         return launch_check("k_pg_rollout");
     }
     DXRL_REQUIRE(!(a->diag_flags & (32 | 64)), "diag_flags 32 / 64 named the retired k_pg_rollout_ls");
@@ -1639,17 +1656,23 @@ int dxrl_pg_rollout(dxrl_env* env, const void* packed, const float* params, cons
         const bool noise = a->obs_noise_std > 0.0 || a->dyn_noise_std > 0.0 || a->dyn_noise_tape || a->obs_noise_tape;
         const bool diag = (a->diag_flags & ~(1024 | 2048)) != 0 || a->applied_act || a->dyn_noise_tape ||
                           a->obs_noise_tape;
-        return launch_pg_rollout_e8(p, n, noise, diag, as_stream(stream));
+        return launch_pg_rollout_e8(p, n, noise, diag, dense, as_stream(stream));
     }
     {  // the 16-env warp-specialised kernel
         const bool noise = a->obs_noise_std > 0.0 || a->dyn_noise_std > 0.0 || a->dyn_noise_tape || a->obs_noise_tape;
         const bool diag = (a->diag_flags & ~(1024 | 2048)) != 0 || a->applied_act || a->dyn_noise_tape ||
                           a->obs_noise_tape;
         const dim3 grid((unsigned)((n + kLsEnvs - 1) / kLsEnvs)), block(kWsThreads);
-        if (noise && diag) hipLaunchKernelGGL((k_pg_rollout_ws<true, true>), grid, block, 0, as_stream(stream), p);
-        else if (noise) hipLaunchKernelGGL((k_pg_rollout_ws<true, false>), grid, block, 0, as_stream(stream), p);
-        else if (diag) hipLaunchKernelGGL((k_pg_rollout_ws<false, true>), grid, block, 0, as_stream(stream), p);
-        else hipLaunchKernelGGL((k_pg_rollout_ws<false, false>), grid, block, 0, as_stream(stream), p);
+        hipStream_t st = as_stream(stream);
+        if (!dense) {
+            if (noise && diag) hipLaunchKernelGGL((k_pg_rollout_ws<true, true, false>), grid, block, 0, st, p);
+            else if (noise) hipLaunchKernelGGL((k_pg_rollout_ws<true, false, false>), grid, block, 0, st, p);
+            else if (diag) hipLaunchKernelGGL((k_pg_rollout_ws<false, true, false>), grid, block, 0, st, p);
+            else hipLaunchKernelGGL((k_pg_rollout_ws<false, false, false>), grid, block, 0, st, p);
+        } else if (noise && diag) hipLaunchKernelGGL((k_pg_rollout_ws<true, true>), grid, block, 0, st, p);
+        else if (noise) hipLaunchKernelGGL((k_pg_rollout_ws<true, false>), grid, block, 0, st, p);
+        else if (diag) hipLaunchKernelGGL((k_pg_rollout_ws<false, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((k_pg_rollout_ws<false, false>), grid, block, 0, st, p);
         if (int rc = launch_check("k_pg_rollout_ws")) return rc;
         if (a->diag_flags & 128) {  // diagnostics: mean cycles per step segment of every wave, env / aux means
             const int64_t groups = (n + kLsEnvs - 1) / kLsEnvs;

@@ -66,6 +66,6 @@ __device__ __forceinline__ int swz16(int r, int col) { return ((((col >> 3) ^ r)
 // The 32-env rollout (dxrl_pg_rollout8.hip): one workgroup of 8 waves per 32 envs, each env on 8
 // lanes.  Same tapes, records and env state as k_pg_rollout_ws bit for bit.
 constexpr int kE8Envs = 32;
-int launch_pg_rollout_e8(const PgRolloutArgs& p, int64_t n, bool noise, bool diag, hipStream_t st);
+int launch_pg_rollout_e8(const PgRolloutArgs& p, int64_t n, bool noise, bool diag, bool dense, hipStream_t st);
 
 }  // namespace dxrl

@@ -153,7 +153,9 @@ struct __attribute__((aligned(16))) E8Reward {  // an env's reward / log pi inpu
     unsigned long long rctr;  // reset counter after the step (the next step's reset draws use it)
 };
 
-template <bool kNoise, bool kDiag>
+// kDense = false: the sparse reward (RS:228-234), as in k_pg_rollout_ws -- the settle reads the
+// contacts only; dmin, nacc[] and prev stay unwritten and the flags' previous-contact bits untouched
+template <bool kNoise, bool kDiag, bool kDense = true>
 __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p) {
     constexpr int kHeadWave0 = 2;  // env waves 2, 3: the mu head of row tiles 0, 1
     constexpr int kW1sW = kIn + 16, kW3sW = kH + 16, kXsW = kIn + 16, kHsW = kH;
@@ -359,24 +361,30 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
             }
         }
     };
-    // ---- aux: the dense reward (RS:50-187) and the episode bookkeeping of a finished step
+    // ---- aux: the reward (dense RS:50-187, sparse RS:228-234) and the episode bookkeeping of a
+    // finished step
     const auto settle = [&](int64_t t_) {
         const E8Reward& w = RW[t_ & 1][eg];
-        const double dist = exp(-5.0 * w.dmin);
-        const double con = count_over_f_f64(__popc(w.c));
-        float sum = 0.0f;
+        double r;
+        if constexpr (kDense) {
+            const double dist = exp(-5.0 * w.dmin);
+            const double con = count_over_f_f64(__popc(w.c));
+            float sum = 0.0f;
 #pragma unroll
-        for (int f = 0; f < kF; ++f) sum = sum + (-w.nacc[f]);
-        const float avg = div_f(sum);
-        const float clo = clipf(div_f(avg), 0.0f, 1.0f);
-        float st = 0.0f;
-        if (w.prev != 0x100u) {
-            float ch = 0.0f;
+            for (int f = 0; f < kF; ++f) sum = sum + (-w.nacc[f]);
+            const float avg = div_f(sum);
+            const float clo = clipf(div_f(avg), 0.0f, 1.0f);
+            float st = 0.0f;
+            if (w.prev != 0x100u) {
+                float ch = 0.0f;
 #pragma unroll
-            for (int f = 0; f < kF; ++f) ch = ch + (float)(((w.c ^ w.prev) >> f) & 1u);
-            st = clipf(1.0f - count_over_f_f32((uint32_t)ch), 0.0f, 1.0f);
+                for (int f = 0; f < kF; ++f) ch = ch + (float)(((w.c ^ w.prev) >> f) & 1u);
+                st = clipf(1.0f - count_over_f_f32((uint32_t)ch), 0.0f, 1.0f);
+            }
+            r = ((p.w.w_dist * dist + p.w.w_con * con) + p.w.w_clo * (double)clo) + p.w.w_st * (double)st;
+        } else {
+            r = __popc(w.c) >= 3 ? 1.0 : -0.01;  // RS:228-234
         }
-        const double r = ((p.w.w_dist * dist + p.w.w_con * con) + p.w.w_clo * (double)clo) + p.w.w_st * (double)st;
         ep_ret += r;
         if (s == 0) p.rew[t_ * n + i] = (float)r;
         if (w.done) {
@@ -475,26 +483,30 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
             double x;
             const uint32_t c = contacts8(jp, opd, size, finger, gbit, x);
             E8Reward& rw = RW[t & 1][eg];
-            if (finger) {  // the reward's inputs for the aux twin (RS:101-187)
-                float nacc = 0.0f;
+            if constexpr (kDense) {
+                if (finger) {  // the reward's inputs for the aux twin (RS:101-187)
+                    float nacc = 0.0f;
 #pragma unroll
-                for (int j = 0; j < kJ; ++j)
-                    if (jp[j] < 0.0f) nacc = nacc + jp[j];
-                rw.nacc[s] = nacc;
+                    for (int j = 0; j < kJ; ++j)
+                        if (jp[j] < 0.0f) nacc = nacc + jp[j];
+                    rw.nacc[s] = nacc;
+                }
+                // dmin = min_f sqrt_rn(x_f) = sqrt_rn(min_f x_f) (the rounded root is monotone)
+                double xm = bcast8<0>(x);
+                const double x1 = bcast8<1>(x), x2 = bcast8<2>(x), x3 = bcast8<3>(x), x4 = bcast8<4>(x);
+                xm = x1 < xm ? x1 : xm;
+                xm = x2 < xm ? x2 : xm;
+                xm = x3 < xm ? x3 : xm;
+                xm = x4 < xm ? x4 : xm;
+                if (s == 0) {
+                    rw.dmin = sqrt(xm);
+                    rw.c = c;
+                    rw.prev = (flags & kHasPrev) ? ((flags >> kPrevShift) & 0xFFu) : 0x100u;
+                }
+                flags = (flags & ~(0xFFu << kPrevShift)) | (c << kPrevShift) | kHasPrev;
+            } else {
+                if (s == 0) rw.c = c;  // the sparse reward's one input
             }
-            // dmin = min_f sqrt_rn(x_f) = sqrt_rn(min_f x_f) (the rounded root is monotone)
-            double xm = bcast8<0>(x);
-            const double x1 = bcast8<1>(x), x2 = bcast8<2>(x), x3 = bcast8<3>(x), x4 = bcast8<4>(x);
-            xm = x1 < xm ? x1 : xm;
-            xm = x2 < xm ? x2 : xm;
-            xm = x3 < xm ? x3 : xm;
-            xm = x4 < xm ? x4 : xm;
-            if (s == 0) {
-                rw.dmin = sqrt(xm);
-                rw.c = c;
-                rw.prev = (flags & kHasPrev) ? ((flags >> kPrevShift) & 0xFFu) : 0x100u;
-            }
-            flags = (flags & ~(0xFFu << kPrevShift)) | (c << kPrevShift) | kHasPrev;
             flags = (flags & ~0xFFu) | c;
             te = __popc(c) >= 3;
             tr = et >= p.max_episode_steps;
@@ -701,9 +713,14 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
 
 }  // namespace
 
-int launch_pg_rollout_e8(const PgRolloutArgs& p, int64_t n, bool noise, bool diag, hipStream_t st) {
+int launch_pg_rollout_e8(const PgRolloutArgs& p, int64_t n, bool noise, bool diag, bool dense, hipStream_t st) {
     const dim3 grid((unsigned)((n + kE8Envs - 1) / kE8Envs)), block(kE8Threads);
-    if (noise && diag) hipLaunchKernelGGL((k_pg_rollout_e8<true, true>), grid, block, 0, st, p);
+    if (!dense) {
+        if (noise && diag) hipLaunchKernelGGL((k_pg_rollout_e8<true, true, false>), grid, block, 0, st, p);
+        else if (noise) hipLaunchKernelGGL((k_pg_rollout_e8<true, false, false>), grid, block, 0, st, p);
+        else if (diag) hipLaunchKernelGGL((k_pg_rollout_e8<false, true, false>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((k_pg_rollout_e8<false, false, false>), grid, block, 0, st, p);
+    } else if (noise && diag) hipLaunchKernelGGL((k_pg_rollout_e8<true, true>), grid, block, 0, st, p);
     else if (noise) hipLaunchKernelGGL((k_pg_rollout_e8<true, false>), grid, block, 0, st, p);
     else if (diag) hipLaunchKernelGGL((k_pg_rollout_e8<false, true>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((k_pg_rollout_e8<false, false>), grid, block, 0, st, p);

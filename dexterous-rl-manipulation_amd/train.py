@@ -1,6 +1,9 @@
 """``python -m dexterous_rl_manipulation_amd.train``: one training run of the MLP actor-critic.
 
   --config-name NAME   a workload of workloads.py (easy, default, hard_heldout, variable_noise)
+  --reward-type R      dense (default) or sparse: the reward of a --config-name run (an
+                       ExperimentConfig file names its own in training.reward_type); a --resume
+                       run names the reward type its checkpoint was written with
   --config FILE        an ExperimentConfig JSON: its training section gives the episode limit and the
                        seed, its curriculum_scheduler section the attached CurriculumScheduler
   --iterations N --out DIR [--resume CKPT] [--keep-best COL] [--converge COL W THR]
@@ -35,6 +38,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     g = p.add_mutually_exclusive_group()
     g.add_argument("--config-name", choices=sorted(WORKLOADS), default=None, help="workload name (default: easy)")
     g.add_argument("--config", metavar="FILE", default=None, help="ExperimentConfig JSON")
+    p.add_argument("--reward-type", choices=("dense", "sparse"), default=None,
+                   help="reward of a --config-name run (default: dense)")
     p.add_argument("--iterations", type=int, required=True)
     p.add_argument("--out", metavar="DIR", required=True)
     p.add_argument("--resume", metavar="CKPT", default=None, help="continue the run of a checkpoint.npz")
@@ -109,6 +114,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--val-classify-max-steps needs --val-failure-modes")
     if a.val_classify_max_steps is not None and a.val_classify_max_steps < 1:
         p.error("--val-classify-max-steps must be >= 1")
+    if a.reward_type is not None and a.config is not None:
+        p.error("--reward-type goes with --config-name: an ExperimentConfig file names its own reward_type")
+    if a.reward_type is None:
+        a.reward_type = "dense"
     if a.config_name is None and a.config is None:
         a.config_name = "easy"
     return a
@@ -126,9 +135,9 @@ def _build(a, fresh: bool):
         if a.seed is not None:
             kw["seed"] = a.seed
         if fresh:
-            return workloads.build_pg_workload(a.config_name, a.device, envs=a.envs, **kw)
+            return workloads.build_pg_workload(a.config_name, a.device, envs=a.envs, reward_type=a.reward_type, **kw)
         env = VecEnv(a.envs or w["envs"], curriculum_config=CurriculumConfig.named(w["curriculum"]),
-                     reward_type="dense", seed=workloads.ENV_SEED, device=a.device)
+                     reward_type=a.reward_type, seed=workloads.ENV_SEED, device=a.device)
         return env, None
     ex = experiments.load_config(a.config)
     sc = ex.curriculum_scheduler

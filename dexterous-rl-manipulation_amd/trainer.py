@@ -151,8 +151,6 @@ class _null:
 
 class PGTrainer:
     def __init__(self, env: VecEnv, cfg: TrainerConfig = TrainerConfig(), process_group=None, world_size: int = 1):
-        if env.reward_type != "dense":
-            raise ValueError("the policy-gradient trainer uses the dense reward")
         p_, b_ = C.c_int64(), C.c_int64()
         N.call("dxrl_pg_sizes", C.byref(p_), C.byref(b_))
         assert (p_.value, b_.value) == (NPARAMS, NBF), "csrc/dxrl_pg.h and trainer.py disagree"

@@ -37,13 +37,14 @@ ENV_SEED = 20240601
 
 def build_pg_workload(name: str, device, *, rank: int = 0, world: int = 1, process_group=None, envs=None,
                       horizon: int = 200, curriculum=None, seed: int = 7, scheduler_history: str = "window",
-                      **trainer_kw):
-    """(VecEnv, PGTrainer) for one rank of workload `name`; the env is reset."""
+                      reward_type: str = "dense", **trainer_kw):
+    """(VecEnv, PGTrainer) for one rank of workload `name`; the env is reset.  reward_type: the
+    env's reward ("dense", the workloads' own, or "sparse": reward_comparison.py's other arm)."""
     from .trainer import PGTrainer, TrainerConfig
     w = WORKLOADS[name]
     n = envs or w["envs"]
     cur = curriculum or w["curriculum"]
-    env = VecEnv(n, curriculum_config=CurriculumConfig.named(cur), reward_type="dense", seed=ENV_SEED,
+    env = VecEnv(n, curriculum_config=CurriculumConfig.named(cur), reward_type=reward_type, seed=ENV_SEED,
                  device=device, global_env_offset=rank * n)
     if w.get("heldout"):
         from .evaluation import HeldOutObjectSet

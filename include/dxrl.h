@@ -380,7 +380,10 @@ typedef struct dxrl_pg_rollout_args {
 } dxrl_pg_rollout_args;
 
 /* Fused policy + env rollout: T steps of actor MLP (bf16 MFMA) -> Gaussian
- * sample -> [dynamics noise] -> env step -> tape, auto-reset (device RNG). */
+ * sample -> [dynamics noise] -> env step -> tape, auto-reset (device RNG).
+ * The reward follows the env's config (reward_type): the dense shaped reward, or the sparse one of
+ * rewards/reward_shaping.py:228-234 (1.0 on a step with >= 3 contacts, -0.01 otherwise), which
+ * leaves the env's previous-contact bits alone, as dxrl_env_step does. */
 int dxrl_pg_rollout(dxrl_env* env, const void* packed, const float* params, const dxrl_pg_rollout_args* args,
                     void* stream);
 /* Which kernel dxrl_pg_rollout runs for this env and diag_flags (without a feature-major tape):
