@@ -587,10 +587,8 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_glds(WgradArgs w) {
 // then the sixteen contraction MFMAs with the next k-step's fragment reads and H1(c + 1)'s tanh in
 // their gaps (fragments double-buffered in registers), so neither an LDS burst nor the tanh leaves
 // the matrix pipe idle; chunk c + 1's first dH2 fragments are read before the barrier.
-#ifndef DXRL_WL1_RING
-#define DXRL_WL1_RING 4  // chunk slots (4: 166 us, 5: 174 us per 819 k rows, kernel-level A/B)
-#endif
-constexpr int kLK = 32, kLNB = DXRL_WL1_RING;
+constexpr int kLK = 32;
+constexpr int kLNB = 4;  // chunk slots (4: 166 us, 5: 174 us per 819 k rows, kernel-level A/B)
 constexpr int kLYB = kLK * 512, kLXB = kLK * 128, kLSlot = kLYB + kLXB;
 constexpr int kLH1 = kLNB * kLSlot;          // two recomputed H1 chunks [32][256] (h1_swz rows)
 constexpr int kLLds = kLH1 + 2 * kLK * 512;  // 112 KiB at 4 slots
@@ -636,14 +634,11 @@ __device__ __forceinline__ bf16x8 tr_frag_h1(const char* lds0, int tile_off, int
     return v;
 }
 
-// Which waves issue a chunk's LDS-DMA pieces.  1 (default): waves 0..3 five each (four dH2, one
-// observation piece), waves 4..7 none; 0: every wave three (two dH2 pieces, one half-wave
-// observation piece).  The first-dispatched half waits at the chunk barrier for its SIMD partners,
-// so the pieces' issue cost (~0.4 k cycles per wave and chunk) moves into that slack: 182 -> 171
-// us per 819 k rows (kernel-level A/B; the second half issuing them: 180 us)
-#ifndef DXRL_WL1_DMA_HALF
-#define DXRL_WL1_DMA_HALF 1
-#endif
+// Which waves issue a chunk's LDS-DMA pieces: waves 0..3 five each (four dH2, one observation
+// piece), waves 4..7 none.  The first-dispatched half waits at the chunk barrier for its SIMD
+// partners, so the pieces' issue cost (~0.4 k cycles per wave and chunk) moves into that slack:
+// 182 -> 171 us per 819 k rows against every wave issuing three pieces (two dH2, one half-wave
+// observation piece; kernel-level A/B; the second half issuing them: 180 us)
 // s_waitcnt vmcnt(k n) (n = 0..4 chunks of k LDS-DMA ops each still in flight)
 // (gfx9 vmcnt: 6 bits, the low four at [3:0] and the high two at [15:14])
 constexpr int vmcnt_imm(int v) { return 0xF70 | (v & 15) | ((v >> 4) << 14); }
@@ -656,7 +651,6 @@ __device__ __forceinline__ void wait_chunks_k(int n) {
     else if (n == 1) __builtin_amdgcn_s_waitcnt(vmcnt_imm(k));
     else __builtin_amdgcn_s_waitcnt(0xF70);
 }
-__device__ __forceinline__ void wait_chunks(int n) { wait_chunks_k<3>(n); }
 
 // kDiag: the DXRL_WGRAD_DIAG ablations compiled in (a run-time branch in the chunk loop costs the
 // production kernel measurable time)
@@ -692,7 +686,6 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_l1(WgradPair pr) {
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         w1f[k] = *(const __attribute__((address_space(1))) bf16x8*)(w.W1 + (32 * wave + r) * 64 + 16 * k + 8 * h);
-#if DXRL_WL1_DMA_HALF
     // the issuing half: wave q = wave mod 4 loads dH2 rows 8 q .. 8 q + 7 and observation rows 8 q ..
     const bool dma_wave = wave < 4;
     const auto wait_in = [&](int n) {
@@ -715,23 +708,6 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_l1(WgradPair pr) {
             glds_x4(X + (m0 + row) * ldx + 8 * pc, slot + kLYB + 1024 * q);
         }
     };
-#else
-    const auto wait_in = [](int n) { wait_chunks(n); };
-    const auto issue = [&](int c) {
-        char* slot = gsm + (c % kLNB) * kLSlot;
-        const int64_t m0 = ((int64_t)bx + (int64_t)c * gx) * kLK;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {  // dH2 rows 4 wave + 2 i, + 1
-            const int prow = 4 * wave + 2 * i;
-            const int rr = prow + (lane >> 5), gchunk = (lane & 31) ^ (4 * (rr & 3));
-            glds_x4(Y + (m0 + rr) * ldy + 8 * gchunk, slot + prow * 512);
-        }
-        if (lane < 32) {  // observation rows 4 wave .. + 3
-            const int row = 4 * wave + (lane >> 3), pc = (lane & 7) ^ ((row >> 1) & 7);
-            glds_x4(X + (m0 + row) * ldx + 8 * pc, slot + kLYB + 512 * wave);
-        }
-    };
-#endif
     // Wave tile: output rows 64 (wave >> 1) .. + 63 x columns 128 (wave & 1) .. + 127, i.e. the output
     // tiles (ot + a, it + b), a < 2, b < 4, in acc[4 a + b]: two dH2 and four H1 fragments per k-step
     // (12 transposed reads; a 32 x 256 wave tile took 18).  Every tile still sums its chunks and
@@ -1088,8 +1064,7 @@ int launch_wgrad(const bf16* Y, int64_t ldy, int O, const bf16* X, int64_t ldx, 
     splits = (int)((M + chunk - 1) / chunk);
     DXRL_REQUIRE(splits == 1 || partial, "wgrad: split-K needs a partial slab");
     WgradArgs w{Y, ldy, X, ldx, O, I, M, chunk, out, splits > 1 ? partial : nullptr, ldo, 0};
-    if (O == kFO && I == kFI && M % kGK == 0 && ldy >= kFO && ldx >= kFI &&
-        getenv("DXRL_WGRAD_REGSTAGE") == nullptr) {  // LDS-DMA stream (A/B: DXRL_WGRAD_REGSTAGE=1)
+    if (O == kFO && I == kFI && M % kGK == 0 && ldy >= kFO && ldx >= kFI) {  // LDS-DMA stream
         static bool attr = [] {
             return hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_glds),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kGNB * kGChunkB) == hipSuccess;

@@ -71,26 +71,8 @@ __device__ __forceinline__ bf16x8 tr_frag(const bf16* tile, int col0, int kk, in
     return v;
 }
 
-// The same for the 16x16x32 operand: lane l gets T[kk + 8 (l >> 4) + j][col0 + (l & 15)], j = 0..7
-// (operand row "feature col0 + (l & 15)" over the 32 k values kk..kk+31).
-template <int kPitch>
-__device__ __forceinline__ bf16x8 tr_frag16(const bf16* tile, int col0, int kk, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int row = kk + 8 * g + q;
-    const int col = col0 + 4 * p;
-    lds_bf16* base = (lds_bf16*)(tile);
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base + row * kPitch + col));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base + (row + 4) * kPitch + col));
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        v[j] = lo[j];
-        v[4 + j] = hi[j];
-    }
-    return v;
-}
-
-// tr_frag16 with the k slots of each 8-sample group in even / odd order: lane l gets
+// The same for the 16x16x32 operand (operand row "feature col0 + (l & 15)" over the 32 k values
+// kk..kk+31), with the k slots of each 8-sample group in even / odd order: lane l gets
 // T[kk + 8 (l >> 4) + e(j)][col0 + (l & 15)], e = (0, 2, 4, 6, 1, 3, 5, 7) -- the first
 // ds_read_b64_tr_b16 reads rows kk + 8 g + 2 q, the second rows kk + 8 g + 2 q + 1.  A weight
 // gradient sums over the samples, so any permutation of the k slots shared by both operands gives

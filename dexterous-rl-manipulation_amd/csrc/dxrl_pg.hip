@@ -353,16 +353,6 @@ struct WsReward {      // an env's dense-reward inputs and episode end of one st
 // kNoise: configs with fused noise (or the noise parity tapes); kDiag: diag_flags / parity tapes
 // set.  The production instantiations compile out every runtime check of the other's features
 // (branches and SGPRs inside the step loop: -8 % rollout time for <false, false>).
-#ifndef DXRL_WS_PRIO
-#define DXRL_WS_PRIO -1  // -1: by instantiation (env waves first with fused noise)
-#endif
-// Observation row t + 1 written at the end of step t's P4 instead of in step t + 1's P0 (no P0
-// phase, no barrier for it) -- in the instantiations without fused noise only: there the rollout
-// runs 1 % faster; with fused noise the aux waves' P0 draw stays and the env lanes' longer P4
-// (the row's noise add) made it 7 % slower (profiles/r05/ab_ws_obs_in_p4.log)
-#ifndef DXRL_WS_OBS_IN_P4
-#define DXRL_WS_OBS_IN_P4 1
-#endif
 // kDense = false: the sparse reward (RS:228-234) -- settle needs the contacts only, so the env
 // lanes leave dmin, nacc[] and prev unwritten, and they leave the previous-contact bits of the
 // env's flags alone, as env_step does (only dense_reward touches them).
@@ -394,8 +384,12 @@ __global__ __launch_bounds__(kWsThreads, 1) void k_pg_rollout_ws(PgRolloutArgs p
     // run a Philox round beside the observation row): noise configs -2.2 % rollout, the others
     // +1 % (so they keep equal priorities); aux first or per-phase priorities lose 5-10 %
     // (rollout_time A/B, profiles/r04/ab_rollout_wave_priority.log)
-    constexpr int kPrio = DXRL_WS_PRIO >= 0 ? DXRL_WS_PRIO : (kNoise ? 1 : 0);
-    constexpr bool kObsInP4 = DXRL_WS_OBS_IN_P4 != 0 && !kNoise;
+    constexpr int kPrio = kNoise ? 1 : 0;
+    // Observation row t + 1 written at the end of step t's P4 instead of in step t + 1's P0 (no P0
+    // phase, no barrier for it) -- in the instantiations without fused noise only: there the rollout
+    // runs 1 % faster; with fused noise the aux waves' P0 draw stays and the env lanes' longer P4
+    // (the row's noise add) made it 7 % slower (profiles/r05/ab_ws_obs_in_p4.log)
+    constexpr bool kObsInP4 = !kNoise;
     // Two moves of work off the wave that sets a phase's length, in the instantiations without
     // fused noise (per-wave stamps and interleaved A/Bs: DESIGN section 2, profiles/r07/):
     //   kXm: the env lanes leave the minimum SQUARED finger distance in WsReward and the aux twin,
@@ -1016,9 +1010,6 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ r
 // profiles/r05/ab_gae_phases.log).
 // k_gae (64 single-wave workgroups, the whole step on the chain, a memory latency per 32-step
 // chunk) remains for horizons whose staging exceeds the LDS.
-#ifndef DXRL_GAE_XCD
-#define DXRL_GAE_XCD 1
-#endif
 // ablation bits for phase timing (A/B builds only; results are wrong when set): 1 no recurrence,
 // 2 no moments / merge, 4 no stores of adv / ret
 #ifndef DXRL_GAE_DIAG
@@ -1051,7 +1042,7 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
     float* Ae = Vs + (int64_t)T * kGlEnvs;         // [16][P] A_t (env-major; the padded steps' A past T)
     __shared__ Moments red[kGlThreads];
     const int tid = threadIdx.x;
-    const int64_t grp = DXRL_GAE_XCD ? xcd_contiguous(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+    const int64_t grp = xcd_contiguous(blockIdx.x, gridDim.x);
     const int64_t e0 = grp * kGlEnvs;
     const int64_t cnt = (int64_t)T * kGlEnvs;
     const float gl = gamma * lam;

@@ -44,16 +44,27 @@ constexpr int kXp = kIn + 8;             // 72:  X rows (conflict-free b128 row 
 constexpr int kHp = kH + 8;              // 264: H1 / H2 rows
 constexpr int kDp = kOut + 8;            // 40:  dout rows
 
-// LDS image of one kTR-sample tile: X [kTR][kXp], H1 / H2 [kTR][kHp], dout [kTR][kDp] (bf16).
-// kTR = 128: 160 KiB, one workgroup per CU; kTR = 64: 80 KiB, two workgroups per CU.
-template <int kTR>
+// Tile geometry: 128-sample tiles run by one 8-wave workgroup per CU, two waves per SIMD (64-sample
+// tiles on two 4-wave workgroups per CU were measured and removed: DESIGN section 9).  Wave w owns
+// the 32-wide hidden feature tile w of every layer; a tile is four 32-sample MFMA tiles.
+constexpr int kFW = 8, kTR = 128;
+constexpr int kMT = kTR / 32;            // 32-sample MFMA tiles of a tile
+constexpr int kFThreads = 64 * kFW;
+// 32-wide feature tiles per wave: one.  The per-layer loops over a wave's feature tiles (j < kNT,
+// #pragma unroll 1) run once and stay: written as straight-line blocks the same phases compile
+// to a different instruction order.
+constexpr int kNT = kH / 32 / kFW;
+static_assert(kNT == 1, "one 32-wide feature tile per wave");
+
+// LDS image of one kTR-sample tile: X [kTR][kXp], H1 / H2 [kTR][kHp], dout [kTR][kDp] (bf16):
+// 160 KiB, one workgroup per CU.
 struct TileLds {
     static constexpr int kOffX = 0;
     static constexpr int kOffH1 = kOffX + kTR * kXp;
     static constexpr int kOffH2 = kOffH1 + kTR * kHp;
     static constexpr int kOffD = kOffH2 + kTR * kHp;
     static constexpr int kElems = kOffD + kTR * kDp;
-    static_assert(kElems * 2 * (128 / kTR) == 163840, "one CU's 160 KiB of LDS per 128 samples");
+    static_assert(kElems * 2 == 163840, "one CU's 160 KiB of LDS");
 };
 
 // per-workgroup gradient partial slab (f32)
@@ -127,8 +138,8 @@ struct NoHook {
 struct NoKHook {
     __device__ void operator()(int) const {}
 };
-// The first kD weight fragments of a fwd_tiles call, issuable ahead of the call (before the
-// barrier in front of its phase, so their L2 latency overlaps the barrier wait).
+// The first kD weight fragments of a fwd_run / fwd_pipe call, issuable ahead of the call (before
+// the barrier in front of its phase, so their L2 latency overlaps the barrier wait).
 template <int KS>
 struct WPre {
     // weight prefetch distance (k-steps; 12 or 16, all of W2 issued ahead of the barrier in front
@@ -146,9 +157,10 @@ __device__ __forceinline__ void w_prefetch(WPre<KS>& w, const bf16* W, int kst, 
 #pragma unroll
     for (int k = 0; k < WPre<KS>::kD; ++k) w.wf[k] = w.wp[64 * k];
 }
-template <int KS, int kLda, int MT, typename Hook = NoHook>
-__device__ __forceinline__ void fwd_run(WPre<KS>& w, const bf16* A, f32x16 (&acc)[MT], int lane, Hook hook = Hook{},
-                                        bool no_mfma = false) {
+// acc[mt] (features 32 ft0.. x samples 32 mt..) = W[32 ft0 + r][:] . A[32 mt + r][:] over KS
+// k-steps (k-major); weight fragments stream from L2 kD k-steps ahead, each feeds MT MFMAs.
+template <int KS, int kLda, int MT>
+__device__ __forceinline__ void fwd_run(WPre<KS>& w, const bf16* A, f32x16 (&acc)[MT], int lane) {
     const int r = lane & 31, h = lane >> 5;
     constexpr int kD = WPre<KS>::kD;
 #pragma unroll
@@ -167,26 +179,13 @@ __device__ __forceinline__ void fwd_run(WPre<KS>& w, const bf16* A, f32x16 (&acc
         }
         const bf16x8 a = w.wf[k % kD];
         if (k + kD < KS) w.wf[k % kD] = w.wp[64 * (k + kD)];
-        // loads the caller wants behind the last weight fragment (vmcnt retires in issue order:
-        // issued earlier they would hold every weight wait of this call)
-        if (k + kD == KS) hook();
         // keep the prefetches above issued ahead of this k-step's MFMAs (the scheduler would
         // otherwise sink every load next to its use and expose its full latency)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-            if (!no_mfma) acc[mt] = mfma32(a, bq[k & 1][mt], acc[mt]);
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma32(a, bq[k & 1][mt], acc[mt]);
         __builtin_amdgcn_sched_barrier(0);
     }
-}
-// acc[mt] (features 32 ft0.. x samples 32 mt..) = W[32 ft0 + r][:] . A[32 mt + r][:] over KS
-// k-steps; weight fragments stream from L2 kD k-steps ahead, each feeds MT MFMAs.
-template <int KS, int kLda, int MT, typename Hook = NoHook>
-__device__ __forceinline__ void fwd_tiles(const bf16* __restrict__ W, int kst, int ft0, const bf16* A,
-                                          f32x16 (&acc)[MT], int lane, Hook hook = Hook{}, bool no_mfma = false) {
-    WPre<KS> w;
-    w_prefetch(w, W, kst, ft0, lane);
-    fwd_run<KS, kLda, MT>(w, A, acc, lane, hook, no_mfma);
 }
 
 // Sample-tile-major variant with the epilogue software-pipelined under the MFMAs: all KS weight
@@ -254,13 +253,15 @@ __device__ __forceinline__ void fwd_pipe(WPre<KS>& w, const bf16* A, int lane, E
     fwd_pipe_w<KS, kLda, MT>(wf, A, lane, epi, no_mfma, khook, thook);
 }
 
-// fwd_pipe epilogues.  EpiTanh: tanh(acc + bias) -> bf16 H rows (store_hidden, pair by pair);
-// EpiGate: acc * (1 - Y^2) -> bf16 in place of Y (gate_in_place), Y read one pair group ahead.
+// fwd_pipe epilogues.  EpiTanh: tanh(acc + bias) -> bf16 row-major H rows, pair by pair (4
+// consecutive features per 8-byte store); EpiGate: acc * (1 - Y^2) -> bf16 in place of Y, Y read
+// one pair group ahead.
 struct EpiTanh {
     bf16* H;
     int f0;        // 32 ft + 4 h
     int r;
-    const float* bk;  // 16 pre-scaled biases (registers) or null
+    // the lane's 16 pre-scaled biases tanh_bias(b[32 ft + 8 g + 4 h + u]) at [4 g + u] (registers), or null
+    const float* bk;
     bf16x4 v;
     __device__ void prime(int) {}
     __device__ __forceinline__ void operator()(const f32x16& acc, int mt, int p) {
@@ -308,35 +309,6 @@ struct EpiGate {
     }
 };
 
-// tanh(acc + bias) -> bf16 row-major activation tile (4 consecutive features per 8-byte store)
-// (bk: the lane's 16 pre-scaled biases tanh_bias(b[32 ft + 8 g + 4 h + u]) at [4 g + u], or null)
-template <int MT>
-__device__ __forceinline__ void store_hidden(const f32x16 (&acc)[MT], int ft, const float* bk, bf16* H, int lane) {
-    const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int f0 = 32 * ft + 8 * g + 4 * h;
-            float b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (bk) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) b[u] = bk[4 * g + u];
-            }
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                bf16x4 v;
-#pragma unroll
-                for (int u = 0; u < 4; u += 2) {
-                    const f32x2 t = tanh_pre2(f32x2{acc[mt][4 * g + u], acc[mt][4 * g + u + 1]},
-                                              f32x2{b[u], b[u + 1]});
-                    v[u] = to_bf16(t.x);
-                    v[u + 1] = to_bf16(t.y);
-                }
-                *reinterpret_cast<bf16x4*>(H + (32 * mt + r) * kHp + f0) = v;
-            }
-        }
-}
-
-// Y[m][f] <- bf16(acc[f][m] * (1 - Y[m][f]^2)) for this wave's features (tanh' gate, in place)
 // Y[m][f] <- bf16(acc[f][m] * (1 - Y[m][f]^2)) for this wave's features (tanh' gate, in place).
 // gate_load reads all 4 x MT Y pieces first (the caller issues it ahead of the MFMAs that make acc,
 // so one LDS latency hides under them; read one by one right before use, the compiler's schedule
@@ -374,17 +346,16 @@ __device__ __forceinline__ void gate_store(const f32x16 (&acc)[MT], const bf16x4
 }
 
 // A [kTR][kH] bf16 tile of LDS (pitch kHp) -> rows m0.. of an HBM matrix (leading dimension ld),
-// nthr threads from thread index t0 (16-byte chunks, rows past `rows` skipped)
-template <int kThreads, int kTR>
-__device__ __forceinline__ void copy_tile_out_n(const bf16* T, bf16* out, int64_t ld, int64_t m0, int64_t rows,
-                                                int t, int diag) {
-    constexpr int kChunks = kTR * (kH / 8);
-    static_assert(kChunks % kThreads == 0, "whole chunks per thread");
+// by the whole workgroup (thread t; 16-byte chunks, rows past `rows` skipped)
+constexpr int kCopyU = kTR * (kH / 8) / kFThreads;  // 16-byte chunks per thread, [kTR][kH] tile
+__device__ __forceinline__ void copy_tile_out(const bf16* T, bf16* out, int64_t ld, int64_t m0, int64_t rows, int t,
+                                              int diag) {
+    static_assert(kTR * (kH / 8) % kFThreads == 0, "whole chunks per thread");
     if (diag & 1) return;
     asm volatile("" : "+v"(t));  // per-call addresses (hoisted out of the tile loop they would spill)
 #pragma unroll
-    for (int u = 0; u < kChunks / kThreads; ++u) {
-        const int c = t + kThreads * u, row = c >> 5, col = 8 * (c & 31);
+    for (int u = 0; u < kCopyU; ++u) {
+        const int c = t + kFThreads * u, row = c >> 5, col = 8 * (c & 31);
         const int64_t m = m0 + row;
         const bf16x8 v = *reinterpret_cast<const bf16x8*>(T + row * kHp + col);
         if (m < rows) *(__attribute__((address_space(1))) bf16x8*)(out + m * ld + col) = v;
@@ -404,126 +375,57 @@ __device__ __forceinline__ T* opaque(T* ptr) {
     return ptr;
 }
 
-// A/B switches: DXRL_L2_PIPE layer 2 as fwd_pipe (tanh epilogue under the next sample tile's
-// MFMAs) instead of the k-major chain + store_hidden; DXRL_FUSED_PRIO s_setprio 1 for waves 4..7
-#ifndef DXRL_L2_PIPE
-#define DXRL_L2_PIPE 1
-#endif
-#ifndef DXRL_DH2_IN_DH1
-#define DXRL_DH2_IN_DH1 1
-#endif
-// The critic's value head on 16x16x32 tiles run by all eight waves (16 samples each, only head row
-// 0 nonzero) instead of 32x32x16 tiles on four waves (32 samples each, 31 dead head rows, four
-// waves idle): critic train 384 -> 375 us, critic values 215 -> 209 us (kernel-level A/B)
-#ifndef DXRL_CRITIC_HEAD16
-#define DXRL_CRITIC_HEAD16 1
-#endif
-// The actor's head on 16x16x32 tiles run by all eight waves (16 samples each, head rows 0..15; a
-// sample's 16 log-density terms gathered by shuffles and summed in action order as before):
-// actor train 427.6 -> 423.3 us (kernel-level A/B), 249 -> 231 VGPRs
-#ifndef DXRL_ACTOR_HEAD16
-#define DXRL_ACTOR_HEAD16 1
-#endif
-#ifndef DXRL_HEAD_PF
-#define DXRL_HEAD_PF 1
-#endif
-#ifndef DXRL_FWD_RESIDENT_W
-#define DXRL_FWD_RESIDENT_W 1
-#endif
-#ifndef DXRL_TRAIN_RESIDENT_HEAD
-#define DXRL_TRAIN_RESIDENT_HEAD 1
-#endif
-// the train passes' layer-2 biases and (DXRL_TRAIN_RESIDENT_HEAD) the heads' constants in
-// registers for the launch: actor 400 -> 384 us, critic 377 -> 363 us (kernel-level A/B,
-// profiles/r04/ab_kernels_train_resident_consts.log); W1's 16 registers as well: no change
-#ifndef DXRL_TRAIN_RESIDENT_B2
-#define DXRL_TRAIN_RESIDENT_B2 1
-#endif
-#ifndef DXRL_FUSED_PRIO
-#define DXRL_FUSED_PRIO 1
-#endif
-
-// forward-only pass with resident weights: the next tile's X fetched at the start of the tile
-#ifndef DXRL_FWD_EARLY_X
-#define DXRL_FWD_EARLY_X 1
-#endif
-// dW1 without the barrier after dH1: a wave's dW1 reads only its own dH1 columns (and X), so the
-// MFMAs of the first three 32-sample blocks issue beside dH1's last epilogue (VALU only) and the
-// db2 column sums' second stage moves behind the end-of-tile barrier
-#ifndef DXRL_DW1_TAIL
-#define DXRL_DW1_TAIL 1
-#endif
-
 // stamps (DXRL_FUSED_DIAG=8) of the kH2 passes: a diagnostic build only
 #ifndef DXRL_H2_STAMPS
 #define DXRL_H2_STAMPS 0
 #endif
 
-// dW3 / dW1 operands through tr_frag16_eo (even / odd sample order inside each 8-sample group:
-// the transposed reads conflict-free) instead of tr_frag16 (2-way)
-#ifndef DXRL_TR_EO
-#define DXRL_TR_EO 1
-#endif
-template <int kPitch>
-__device__ __forceinline__ bf16x8 wg_frag(const bf16* tile, int col0, int kk, int lane) {
-    if constexpr (DXRL_TR_EO) return tr_frag16_eo<kPitch>(tile, col0, kk, lane);
-    else return tr_frag16<kPitch>(tile, col0, kk, lane);
-}
-
-// kFW waves per workgroup: 4 (one per SIMD, 512 registers each) or 8 (two per SIMD)
 // kTrain: forward + heads + backward; otherwise the forward-only critic-value pass, which keeps
-// no launch-long accumulators and so fits two waves per SIMD.
-// kNet: 0 actor, 1 critic, -1 read from the arguments; kDiag: the DXRL_FUSED_DIAG ablations /
-// stamps compiled in (production instantiations do not test them at run time: fewer branches and
-// SGPRs in the tile loop)
-// kH2 (train, production geometry): the tile's layer-2 activations come from HBM (p.h2_in,
-// written by the rollout for the actor / by k_pg_values for the critic with the same weights,
-// bit for bit this pass's own L2) by LDS-DMA into the H2 slot while layer 1 runs, instead of
-// being recomputed: no L2 phase (round 6).
-template <int kFW, int kTR, bool kTrain, int kNet, bool kDiag, bool kH2 = false>
-__global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedArgs p) {
-    static_assert(!kH2 || (kTrain && kFW == 8 && kTR == 128 && (!kDiag || DXRL_H2_STAMPS)), "kH2: production train instantiations");
+// no launch-long accumulators.
+// kNet: 0 actor (train only), 1 critic; kDiag: the DXRL_FUSED_DIAG ablations / stamps compiled in
+// (production instantiations do not test them at run time: fewer branches and SGPRs in the tile
+// loop)
+// kH2 (train): the tile's layer-2 activations come from HBM (p.h2_in, written by the rollout for
+// the actor / by k_pg_values for the critic with the same weights, bit for bit this pass's own
+// L2) by LDS-DMA into the H2 slot while layer 1 runs, instead of being recomputed: no L2 phase
+// (round 6).
+// The heads run on 16x16x32 tiles by all eight waves, 16 samples each (32x32x16 tiles on four
+// waves, 32 samples each, left four waves idle):
+//   critic: only head row 0 nonzero (the 32-row tile had 31 dead head rows): critic train
+//     384 -> 375 us, critic values 215 -> 209 us (kernel-level A/B);
+//   actor: head rows 0..15, a sample's 16 log-density terms gathered by shuffles and summed in
+//     action order as before: actor train 427.6 -> 423.3 us (kernel-level A/B), 249 -> 231 VGPRs.
+template <bool kTrain, int kNet, bool kDiag, bool kH2 = false>
+__global__ __launch_bounds__(kFThreads, 1) void k_pg_fused(FusedArgs p) {
+    static_assert(kNet == 1 || (kNet == 0 && kTrain), "critic (train / values) or actor (train)");
+    static_assert(!kH2 || (kTrain && (!kDiag || DXRL_H2_STAMPS)), "kH2: production train instantiations");
     const int diag = kDiag ? p.diag : 0;
-    const bool actor = kNet < 0 ? p.net == 0 : kNet == 0;  // kNet -1: the net read at run time
-    using L = TileLds<kTR>;
+    constexpr bool actor = kNet == 0;
+    using L = TileLds;
     constexpr int kOffX = L::kOffX, kOffH1 = L::kOffH1, kOffH2 = L::kOffH2, kOffD = L::kOffD;
-    constexpr int kHW = kTR / 32;  // waves running the heads (one 32-sample tile each)
-    // critic, 8 waves x 128 samples: every wave runs a 16-sample value head (DXRL_CRITIC_HEAD16)
-    constexpr bool kCH16 = DXRL_CRITIC_HEAD16 && kNet == 1 && kFW == 8 && kTR == 128;
-    constexpr bool kAH16 = DXRL_ACTOR_HEAD16 && kNet == 0 && kTrain && kFW == 8 && kTR == 128;
-    constexpr bool kH16 = kCH16 || kAH16;
-    constexpr int kMT = kTR / 32;  // 32-sample MFMA tiles of a tile
-    constexpr int kFThreads = 64 * kFW;
-    constexpr int kNT = kH / 32 / kFW;  // 32-wide feature tiles per wave
-    [[maybe_unused]] constexpr int kCopyU = kTR * (kH / 8) / kFThreads;  // 16-byte chunks per thread, [kTR][kH] tile
-    static_assert(kHW <= kFW, "one 32-sample head tile per wave");
     __shared__ __attribute__((aligned(16))) bf16 lds[L::kElems];
     bf16* X = lds + kOffX;
     bf16* H1 = lds + kOffH1;
     bf16* H2 = lds + kOffH2;
     bf16* D = lds + kOffD;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#if DXRL_FUSED_PRIO
     // the second-dispatched half of the waves loses VALU arbitration to its SIMD partner
     if (__builtin_amdgcn_readfirstlane(wave) >= kFW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
-    const int ft0 = kNT * wave;  // this wave's first 32-wide feature tile
+    const int ft0 = wave;  // this wave's 32-wide feature tile
     const int64_t ntiles = (p.rows + kTR - 1) / kTR;
 
-    // launch-long accumulators: dW3 columns of this wave's tiles, dW1 rows of this wave's tiles
+    // launch-long accumulators: dW3 columns of this wave's tile, dW1 rows of this wave's tile
     // (16x16x32 tiles: only head rows 0..15 and input columns 0..47 can be nonzero -- 15 mu rows /
     // one value row, 45 observation features + the bias column -- so 8 + 24 registers, not 16 + 32)
-    f32x4 acc3[kNT][2], acc1[kNT][2][3];
+    f32x4 acc3[2], acc1[2][3];
 #pragma unroll
-    for (int j = 0; j < kNT; ++j)
+    for (int q = 0; q < 4; ++q) {
+        acc3[0][q] = acc3[1][q] = 0.0f;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            acc3[j][0][q] = acc3[j][1][q] = 0.0f;
+        for (int ri = 0; ri < 2; ++ri)
 #pragma unroll
-            for (int ri = 0; ri < 2; ++ri)
-#pragma unroll
-                for (int ci = 0; ci < 3; ++ci) acc1[j][ri][ci][q] = 0.0f;
-        }
+            for (int ci = 0; ci < 3; ++ci) acc1[ri][ci][q] = 0.0f;
+    }
     float dls[8], db3[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) dls[j] = db3[j] = 0.0f;
@@ -571,13 +473,11 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
     // forward-only pass (critic values): this wave's W1 / W2 fragments stay in registers for the
     // whole launch (80 VGPRs; the train instantiations have no room for them) instead of streaming
     // 160 KB of weight fragments from L2 per tile and workgroup
-    constexpr bool kResW = !kTrain && kNT == 1 && DXRL_FWD_RESIDENT_W && DXRL_L2_PIPE;
-    constexpr bool kEarlyX = kResW && DXRL_FWD_EARLY_X;
+    constexpr bool kResW = !kTrain;
     // kH2: W1 resident too, so layer 1 issues no global loads -- the LDS-DMA pieces in flight
     // beside it are invisible to the compiler, and a vmcnt wait for a weight fragment issued
     // before them would wait for them as well
     constexpr bool kResW1 = kResW || kH2;
-    constexpr bool kDw1Tail = kTrain && kNT == 1 && kMT == 4 && DXRL_DW1_TAIL && DXRL_DH2_IN_DH1;
     bf16x8 w1res[kResW1 ? kIn / 16 : 1], w2res[kResW ? kH / 16 : 1];
     if constexpr (kResW1) {
         const gbf16x8* p1 = (const gbf16x8*)p.W1 + (int64_t)ft0 * (kIn / 16) * 64 + lane;
@@ -590,17 +490,18 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
 #pragma unroll
         for (int k = 0; k < kH / 16; ++k) w2res[k] = p2[64 * k];
     }
-    // ... and so do the layer-2 biases of its feature tile and (16-row critic head) the value row
-    // (the train passes too: the biases fit beside their accumulators, W2 / W2T do not)
-    constexpr bool kResB = kNT == 1 && (kResW || (kTrain && DXRL_TRAIN_RESIDENT_B2));
-    float bkres[kResB ? 16 : 1];
-    constexpr bool kResH = kCH16 && (kResW || (kTrain && DXRL_TRAIN_RESIDENT_HEAD));
-    bf16x8 w3res[kResH ? 8 : 1];
+    // ... and so do the layer-2 biases of its feature tile and the heads' constants, in every pass
+    // (the biases fit beside the train passes' accumulators, W2 / W2T do not): train actor 400 ->
+    // 384 us, critic 377 -> 363 us (kernel-level A/B, profiles/r04/
+    // ab_kernels_train_resident_consts.log); W1's 16 registers as well: no change
+    float bkres[16];
+    // critic: the value row's 8 A fragments (head row lane & 15 -- only row 0 is loaded -- over
+    // k 32 ks + 8 (lane >> 4) ..) and the value bias
+    bf16x8 w3res[actor ? 1 : 8];
     float b3res = 0.0f;
     // the actor head's per-lane constants (head rows 4 (lane >> 4) .. + 3): log sigma and mu bias
-    constexpr bool kResA = kAH16 && DXRL_TRAIN_RESIDENT_HEAD;
-    float ahls[kResA ? 4 : 1], ahb3[kResA ? 4 : 1];
-    if constexpr (kResA) {
+    float ahls[actor ? 4 : 1], ahb3[actor ? 4 : 1];
+    if constexpr (actor) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int o = 4 * (lane >> 4) + i;
@@ -608,19 +509,17 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
             ahb3[i] = ((gf32*)p.b3)[(int64_t)o * kHx];
         }
     }
-    if constexpr (kResB) {
+    {
         const int h0 = (threadIdx.x & 63) >> 5;
 #pragma unroll
         for (int q = 0; q < 16; ++q)
             bkres[q] = tanh_bias(((gf32*)p.b2)[(int64_t)(32 * ft0 + 8 * (q >> 2) + 4 * h0 + (q & 3)) * kHx]);
     }
-    if constexpr (kResH) {
-        {
+    if constexpr (!actor) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k)
-                w3res[k] = (lane & 15) == 0 ? *(const gbf16x8*)(p.W3rm + 32 * k + 8 * (lane >> 4)) : zero8();
-            b3res = ((gf32*)p.b3)[0];
-        }
+        for (int k = 0; k < 8; ++k)
+            w3res[k] = (lane & 15) == 0 ? *(const gbf16x8*)(p.W3rm + 32 * k + 8 * (lane >> 4)) : zero8();
+        b3res = ((gf32*)p.b3)[0];
     }
     int64_t tile = blockIdx.x;
     if (tile < ntiles) fetch_x(tile);
@@ -636,16 +535,21 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
         (void)h;
         const bf16 *W1 = opaque(p.W1), *W2 = opaque(p.W2), *W3 = opaque(p.W3), *W2T = opaque(p.W2T),
                    *W3T = opaque(p.W3T);
+        // (W3, b2, b3, log sigma are read before the tile loop -- the heads' constants and the biases
+        // are resident -- and no longer through these; the four pins stay because without them the
+        // kernel-argument loads and the scalar register allocation of every instantiation change.
+        // They can go with the next change to this kernel's schedule.)
         const float *b2 = opaque(p.b2), *b3 = opaque(p.b3), *logstd = opaque(p.logstd);
+        (void)W3, (void)b2, (void)b3, (void)logstd;
 #pragma unroll
         for (int u = 0; u < kXU; ++u) {
             const int c = tid + kFThreads * u, row = c >> 3, col = 8 * (c & 7);
             *reinterpret_cast<bf16x8*>(X + row * kXp + col) = xr[u];
         }
-        // resident-weight forward pass: no weight fragment loads in the tile loop, so nothing
-        // waits behind the next tile's X -- it goes out now and lands under this tile's layers
-        // (fetched after the head it was a full HBM latency at the next tile's start)
-        if constexpr (kEarlyX) {
+        // forward-only pass (resident weights): no weight fragment loads in the tile loop, so
+        // nothing waits behind the next tile's X -- it goes out now and lands under this tile's
+        // layers (fetched after the head it was a full HBM latency at the next tile's start)
+        if constexpr (!kTrain) {
             if (tile + gridDim.x < ntiles) fetch_x(tile + gridDim.x);
         }
         // the first W1 fragments go out before the barrier (their L2 latency overlaps its wait;
@@ -698,11 +602,10 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
         // (the next tile's X is fetched late in this one: vmcnt retires in issue order, so an
         // HBM load issued here would make every weight-fragment wait below wait for it too)
 
-        // ---- L1, L2 (wave w: hidden features 64w .. 64w + 63, all 128 samples)
+        // ---- L1, L2 (wave w: hidden features 32w .. 32w + 31, all 128 samples)
 #pragma unroll 1
         for (int j = 0; j < kNT; ++j) {
             // bias = W1 column 45 (X column 45 = 1)
-            if (j > 0) w_prefetch(pw1, W1, kIn / 16, ft0 + j, lane);
             EpiTanh e1{H1, 32 * (ft0 + j) + 4 * h, r, nullptr};
             if constexpr (kH2) fwd_pipe<kIn / 16, kXp, kMT>(pw1, X, lane, e1, NoHook{}, false, h2_dma_k);
             else fwd_pipe<kIn / 16, kXp, kMT>(pw1, X, lane, e1);
@@ -714,115 +617,46 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
         if constexpr (!kH2) __syncthreads();  // (kH2: no L2, so H1 is next read after the head barrier)
         STAMP(3);
         // head inputs (HBM), issued halfway through L2 so their latency hides behind its second half
-        const int ml = 32 * wave + r;
-        const int64_t m = m0 + ml;
-        const bool valid = m < p.rows;
-        float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+        float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f);
         // hv: the head's per-sample target -- old log pi (actor) or return (critic); one variable,
         // not two assigned on the two net branches (the compiler merged those stores into one
         // through a selected pointer and kept both in scratch memory)
         float hv = 0.0f, adv = 0.0f;
-        float bk[16];
-        int bft = ft0;  // feature tile whose biases bk holds
         auto head_inputs = [&]() {
-            // the bias loads first: store_hidden waits for them, and must not wait for the HBM loads
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                if constexpr (kResB) bk[q] = bkres[q];
-                else bk[q] = tanh_bias(((gf32*)b2)[(int64_t)(32 * bft + 8 * (q >> 2) + 4 * h + (q & 3)) * kHx]);
-            }
-            if constexpr (kCH16) {
-                if (kTrain) {
-                    const int64_t m16 = m0 + 16 * wave + (lane & 15);
-                    hv = p.ret[m16 < p.rows ? m16 : p.rows - 1];
-                }
-                return;
-            }
-            if constexpr (kAH16) {  // sample 16 w + (lane & 15), actions 4 (lane >> 4) .. + 3
-                const int64_t m16 = m0 + 16 * wave + (lane & 15), mc = m16 < p.rows ? m16 : p.rows - 1;
+            const int64_t m16 = m0 + 16 * wave + (lane & 15), mc = m16 < p.rows ? m16 : p.rows - 1;
+            if constexpr (!actor) {
+                hv = p.ret[mc];
+            } else {  // sample 16 w + (lane & 15), actions 4 (lane >> 4) .. + 3
                 hv = p.logp_old[mc];
                 a0 = *reinterpret_cast<const float4*>(p.act + mc * kActPad + 4 * (lane >> 4));
                 adv = p.adv[mc];
-                return;
-            }
-            if (!kTrain || __builtin_amdgcn_readfirstlane(wave) >= kHW) return;
-            const int64_t mc = valid ? m : p.rows - 1;  // clamped: unconditional loads, no branch
-            hv = (actor ? p.logp_old : p.ret)[mc];
-            if (actor) {
-                a0 = *reinterpret_cast<const float4*>(p.act + mc * kActPad + 4 * h);
-                a1 = *reinterpret_cast<const float4*>(p.act + mc * kActPad + 8 + 4 * h);
-                adv = p.adv[mc];
             }
         };
+        // layer 2 as fwd_pipe: the tanh epilogue of a sample tile under the next one's MFMAs
 #pragma unroll 1
         for (int j = 0; j < (kH2 ? 0 : kNT); ++j) {
-            bft = ft0 + j;
-            const auto l2_hook = [&]() {
-                if (j == kNT - 1) head_inputs();
-                else {
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        bk[q] = tanh_bias(((gf32*)b2)[(int64_t)(32 * bft + 8 * (q >> 2) + 4 * h + (q & 3)) * kHx]);
-                }
-            };
-            if (j > 0) w_prefetch(pw2, W2, kH / 16, ft0 + j, lane);
-            // (fwd_pipe measured 1 % slower here than the k-major chain + store_hidden)
-#if DXRL_L2_PIPE
-            EpiTanh e2{H2, 32 * (ft0 + j) + 4 * h, r, bk};
-            if constexpr (kResW) {  // biases and head inputs resident: nothing to load
-                EpiTanh e2r{H2, 32 * (ft0 + j) + 4 * h, r, bkres};
-                fwd_pipe_w<kH / 16, kHp, kMT>(w2res, H1, lane, e2r, (diag & 32) != 0);
+            EpiTanh e2{H2, 32 * (ft0 + j) + 4 * h, r, bkres};
+            if constexpr (kResW) {  // weights resident, no head inputs: nothing to load
+                fwd_pipe_w<kH / 16, kHp, kMT>(w2res, H1, lane, e2, (diag & 32) != 0);
             } else {
+                const auto l2_hook = [&]() {  // behind the last weight fragment of the wave's last tile
+                    if (j == kNT - 1) head_inputs();
+                };
                 fwd_pipe<kH / 16, kHp, kMT>(pw2, H1, lane, e2, l2_hook, (diag & 32) != 0);
             }
-#else
-            f32x16 acc[kMT];
-            fwd_run<kH / 16, kHp, kMT>(pw2, H1, acc, lane, l2_hook, (diag & 32) != 0);
-            if (!(diag & 16)) store_hidden(acc, ft0 + j, bk, H2, lane);
-#endif
         }
-        // forward mode: the head waves' W3 fragments, all 16 k-steps, go out before the barrier
-        // (their L2 latency overlaps its wait instead of opening the head phase twice).  Train
-        // mode keeps two batches of 8 issued in the head: 16 in flight there spill (the
-        // launch-long gradient accumulators are live)
-        constexpr int kW3K = kH / 16;
-        // (critic train mode, DXRL_HEAD_PF: the first half of the fragments and the head's biases go
-        // out here too, so the head opens without an L2 round trip; across the barrier the actor's
-        // extra registers spill, so its head keeps its loads)
-        constexpr bool kHeadPf = kTrain && DXRL_HEAD_PF && kNet == 1;
-        constexpr int kW3P = kTrain ? (kHeadPf ? kW3K / 2 : 1) : kW3K;
-        bf16x8 w3p[kW3P];
-        float b3p[8];
-        const gbf16x8* w3row = (const gbf16x8*)W3 + lane;  // fragment stream, feature tile 0
-        // 16-row critic head: the 8 A fragments (head row lane & 15 -- only row 0, the value row,
-        // is loaded -- over k 32 ks + 8 (lane >> 4) ..) and the value bias, on every wave
-        bf16x8 w3h[kH16 ? 8 : 1];
+        // the head's A fragments and bias, on every wave: the critic's resident value row; the
+        // actor's head rows lane & 15 (0..14 the means, 15 zero), loaded ahead of the head barrier
+        bf16x8 w3h[8];
         float b3h = 0.0f;
-        if constexpr (kAH16) {  // head rows lane & 15 (0..14 the means, 15 zero)
+        if constexpr (actor) {
             const bf16* W3rm = opaque(p.W3rm) + (lane & 15) * kHx + 8 * (lane >> 4);
 #pragma unroll
             for (int k = 0; k < 8; ++k) w3h[k] = *(const gbf16x8*)(W3rm + 32 * k);
-        }
-        if constexpr (kResH) {
+        } else {
 #pragma unroll
             for (int k = 0; k < 8; ++k) w3h[k] = w3res[k];
             b3h = b3res;
-        } else if constexpr (kCH16) {
-            const bf16* W3rm = opaque(p.W3rm);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                w3h[k] = (lane & 15) == 0 ? *(const gbf16x8*)(W3rm + 32 * k + 8 * (lane >> 4)) : zero8();
-            b3h = ((gf32*)b3)[0];
-        }
-        if (!kH16 && (!kTrain || kHeadPf)) {
-            if (wave < kHW) {
-#pragma unroll
-                for (int k = 0; k < kW3P; ++k) w3p[k] = w3row[64 * k];
-                if (kTrain) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) b3p[q] = ((gf32*)b3)[(int64_t)((q & 3) + 8 * (q >> 2) + 4 * h) * kHx];
-                }
-            }
         }
         if constexpr (kH2) {
             hv = hv2;
@@ -837,14 +671,8 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
         __syncthreads();
         STAMP(5);
 
-        // ---- head: wave w < kHW owns samples 32w .. 32w + 31 (lane: sample r, head rows of half h)
-        // H1 tile -> HBM (B operand of the dW2 GEMM) by the waves that have no head tile; their
-        // stores then retire while the head runs instead of holding the head's load waits
-        if constexpr (kTrain && kFW > kHW && !kH16) {
-            if (wave >= kHW && p.h1_out)
-                copy_tile_out_n<64 * (kFW - kHW), kTR>(H1, p.h1_out, kHx, m0, p.rows, tid - 64 * kHW, diag);
-        }
-        if constexpr (kCH16) {
+        // ---- head: wave w owns samples 16w .. 16w + 15
+        if constexpr (!actor) {
             // wave w: samples 16 w .. 16 w + 15; V of sample 16 w + l in lane l < 16 (row 0, reg 0)
             const int s16 = 16 * wave + (lane & 15);
             const bf16* hb = H2 + s16 * kHp + 8 * (lane >> 4);
@@ -868,7 +696,7 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
                 if (lane < 16) dv[0] = to_bf16(d0);
                 *reinterpret_cast<bf16x8*>(D + s16 * kDp + 8 * (lane >> 4)) = dv;
             }
-        } else if constexpr (kAH16) {
+        } else {
             // wave w: samples 16 w .. + 15; lane l holds head rows o = 4 (l >> 4) + i of sample l & 15
             const int s16 = 16 * wave + (lane & 15), g4 = lane >> 4;
             const bf16* hb = H2 + s16 * kHp + 8 * g4;
@@ -882,11 +710,9 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int o = 4 * g4 + i;
-                if constexpr (kResA) lsv[i] = ahls[i];
-                else lsv[i] = o < kAct ? ((gf32*)logstd)[o] : 0.0f;
+                lsv[i] = ahls[i];
                 iv2[i] = __expf(-2.0f * lsv[i]);
-                if constexpr (kResA) mu[i] = a16[i] + ahb3[i];
-                else mu[i] = a16[i] + ((gf32*)b3)[(int64_t)o * kHx];
+                mu[i] = a16[i] + ahb3[i];
                 const float z = (a[i] - mu[i]) * __expf(-lsv[i]);
                 t[i] = o < kAct ? -0.5f * z * z - lsv[i] - 0.5f * kLog2PiF : 0.0f;
                 d[i] = 0.0f;
@@ -934,164 +760,32 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
             }
             *reinterpret_cast<bf16x4*>(D + s16 * kDp + 4 * g4) = dv;        // head rows 4 g4 .. + 3
             *reinterpret_cast<bf16x4*>(D + s16 * kDp + 16 + 4 * g4) = zv;   // rows 16 .. 31: zero
-        } else if (wave < kHW) {
-            f32x16 acc;
-            zero_acc(acc);
-            if constexpr (!kTrain) {
-#pragma unroll
-                for (int k = 0; k < kW3K; ++k) {
-                    const bf16x8 b = *reinterpret_cast<const bf16x8*>(H2 + (32 * wave + r) * kHp + 16 * k + 8 * h);
-                    acc = mfma32(w3p[k], b, acc);
-                }
-            } else {
-                constexpr int kB = kW3K / 2;  // fragments per batch (32 registers in flight)
-                bf16x8 w3f[kB];
-                if constexpr (kHeadPf) {
-                    // second batch in flight under the first (prefetched) batch's MFMAs
-#pragma unroll
-                    for (int k = 0; k < kB; ++k) w3f[k] = w3row[64 * (k + kB)];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < kB; ++k) {
-                        const bf16x8 b = *reinterpret_cast<const bf16x8*>(H2 + (32 * wave + r) * kHp + 16 * k + 8 * h);
-                        acc = mfma32(w3p[k], b, acc);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < kB; ++k) w3f[k] = w3row[64 * k];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < kB; ++k) {
-                        const bf16x8 b = *reinterpret_cast<const bf16x8*>(H2 + (32 * wave + r) * kHp + 16 * k + 8 * h);
-                        acc = mfma32(w3f[k], b, acc);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < kB; ++k) w3f[k] = w3row[64 * (k + kB)];
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int k = 0; k < kB; ++k) {
-                    const bf16x8 b = *reinterpret_cast<const bf16x8*>(H2 + (32 * wave + r) * kHp + 16 * (k + kB) + 8 * h);
-                    acc = mfma32(w3f[k], b, acc);
-                }
-            }
-            float d[8], b3v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                d[q] = 0.0f;
-                // head row o of register q
-                b3v[q] = kHeadPf ? b3p[q] : ((gf32*)b3)[(int64_t)((q & 3) + 8 * (q >> 2) + 4 * h) * kHx];
-            }
-            if (actor) {
-                if (kTrain) {
-                    float mu[8], a[8], lsv[8], iv2[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int o = (q & 3) + 8 * (q >> 2) + 4 * h;
-                        lsv[q] = o < kAct ? ((gf32*)logstd)[o] : 0.0f;
-                        iv2[q] = __expf(-2.0f * lsv[q]);
-                    }
-                    a[0] = a0.x; a[1] = a0.y; a[2] = a0.z; a[3] = a0.w;
-                    a[4] = a1.x; a[5] = a1.y; a[6] = a1.z; a[7] = a1.w;
-                    // log pi(a|s): the 15 terms summed in action order (as the rollout sampled
-                    // them), so the first update's ratios are exactly 1
-                    float t[8], u[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int o = (q & 3) + 8 * (q >> 2) + 4 * h;
-                        mu[q] = acc[q] + b3v[q];
-                        const float z = (a[q] - mu[q]) * __expf(-lsv[q]);
-                        t[q] = o < kAct ? -0.5f * z * z - lsv[q] - 0.5f * kLog2PiF : 0.0f;
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) u[q] = __shfl_xor(t[q], 32);
-                    float lp = 0.0f;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) lp += h ? u[q] : t[q];      // o = 0..3
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) lp += h ? t[q] : u[q];      // o = 4..7
-#pragma unroll
-                    for (int q = 4; q < 8; ++q) lp += h ? u[q] : t[q];      // o = 8..11
-#pragma unroll
-                    for (int q = 4; q < 7; ++q) lp += h ? t[q] : u[q];      // o = 12..14
-                    const float lo = hv;
-                    const float ratio = __expf(lp - lo);
-                    const float A = (float)(((double)adv - adv_mean) * adv_inv);
-                    const float s1 = ratio * A;
-                    const float rc = fminf(fmaxf(ratio, 1.0f - p.clip_eps), 1.0f + p.clip_eps);
-                    const float s2 = rc * A;
-                    float g = 0.0f;
-                    if (s1 <= s2 || ratio == rc) g = -A * ratio;  // d(-min(s1, s2)) / d logp
-                    g *= p.sc;
-                    if (valid) {
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) {
-                            const int o = (q & 3) + 8 * (q >> 2) + 4 * h;
-                            if (o < kAct) {
-                                const float dd = a[q] - mu[q];
-                                d[q] = from_bf16(to_bf16(g * dd * iv2[q]));  // dlogp/dmu = (a - mu) / sigma^2
-                                dls[q] += g * (dd * dd * iv2[q] - 1.0f);       // dlogp/dlogstd
-                                db3[q] += d[q];
-                            }
-                        }
-                        if (h == 0) {
-                            lsum[0] += -fminf(s1, s2);
-                            lsum[2] += fabsf(ratio - 1.0f) > p.clip_eps ? 1.0f : 0.0f;
-                            lsum[3] += lo - lp;
-                        }
-                    }
-                }
-            } else {
-                const float v = acc[0] + b3v[0];  // lanes h == 0 hold head row 0
-                if (!kTrain) {
-                    if (valid && h == 0) p.v_out[m] = v;
-                } else if (valid && h == 0) {
-                    const float e = v - hv;  // hv: the return
-                    d[0] = from_bf16(to_bf16(p.vf2 * e * p.sc));
-                    db3[0] += d[0];
-                    lsum[1] += e * e;
-                }
-            }
-            if (kTrain) {
-#pragma unroll
-                for (int g2 = 0; g2 < 4; ++g2) {  // head rows 8 g2 + 4 h .. + 3
-                    bf16x4 v;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) v[u] = g2 < 2 ? to_bf16(d[4 * g2 + u]) : (bf16)0.0f;
-                    *reinterpret_cast<bf16x4*>(D + ml * kDp + 8 * g2 + 4 * h) = v;
-                }
-            }
         }
         STAMP(6);
         if (!kTrain) {
             // (h2_out: H2 for the critic's train pass, as k_pg_values writes it)
-            if (p.h2_out) copy_tile_out_n<kFThreads, kTR>(H2, p.h2_out, kHp, m0, p.rows, tid, diag);
-            if (!kEarlyX && tile + gridDim.x < ntiles) fetch_x(tile + gridDim.x);
+            if (p.h2_out) copy_tile_out(H2, p.h2_out, kHp, m0, p.rows, tid, diag);
             __syncthreads();  // X / H1 / H2 are rewritten by the next tile
             STAMP(7);
             continue;
         }
-        if constexpr (kFW == kHW || kH16) {
-            if (p.h1_out) copy_tile_out_n<kFThreads, kTR>(H1, p.h1_out, kHx, m0, p.rows, tid, diag);
-        }
+        // H1 tile -> HBM (B operand of the dW2 GEMM) where the contraction does not recompute it
+        if (p.h1_out) copy_tile_out(H1, p.h1_out, kHx, m0, p.rows, tid, diag);
         WPre<1> pw3t;  // dH2's one W3T fragment, ahead of the barrier
         w_prefetch(pw3t, W3T, kOut / 16, ft0, lane);
         STAMP(7);
         __syncthreads();
         STAMP(8);
 
-        // ---- dW3 += dout^T H2 (wave w: H2 columns of its tiles), then dH2 in place of H2
+        // ---- dW3 += dout^T H2 (wave w: H2 columns of its tile), then dH2 in place of H2
+        // (dW3 / dW1 operands through tr_frag16_eo -- even / odd sample order inside each 8-sample
+        // group: the transposed reads conflict-free, where consecutive samples' are 2-way)
 #pragma unroll
         for (int kk = 0; kk < kTR; kk += 32) {
-            const bf16x8 a = wg_frag<kDp>(D, 0, kk, lane);
+            const bf16x8 a = tr_frag16_eo<kDp>(D, 0, kk, lane);
 #pragma unroll
-            for (int j = 0; j < kNT; ++j)
-#pragma unroll
-                for (int ci = 0; ci < 2; ++ci)
-                    if (!(diag & 4))
-                        acc3[j][ci] = mfma16(a, wg_frag<kHp>(H2, 32 * (ft0 + j) + 16 * ci, kk, lane), acc3[j][ci]);
+            for (int ci = 0; ci < 2; ++ci)
+                if (!(diag & 4)) acc3[ci] = mfma16(a, tr_frag16_eo<kHp>(H2, 32 * ft0 + 16 * ci, kk, lane), acc3[ci]);
         }
 #pragma unroll 1
         for (int j = 0; j < kNT; ++j) {
@@ -1099,8 +793,7 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
             bf16x4 ys[4][kMT];
             gate_load(ys, ft0 + j, H2, lane);
             // dH2^T = W3^T dout^T over head rows 0..15 (dout rows 16..31 are zero)
-            if (j == 0) fwd_run<1, kDp, kMT>(pw3t, D, acc, lane);
-            else fwd_tiles<1, kDp, kMT>(W3T, kOut / 16, ft0 + j, D, acc, lane);
+            fwd_run<1, kDp, kMT>(pw3t, D, acc, lane);
             gate_store(acc, ys, ft0 + j, H2, lane);
         }
         WPre<kH / 16> pw2t;  // dH1's first W2T fragments, ahead of the barrier
@@ -1110,7 +803,8 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
         STAMP(10);
 
         // ---- db2 column sums of dH2, stage 1: wave w sums rows w * kTR / kFW.. for the 4 columns
-        //      4 lane..; the per-wave sums go to the (dead) dout region, stage 2 follows in dW1.
+        //      4 lane..; the per-wave sums go to the (dead) dout region, stage 2 follows the
+        //      end-of-tile barrier.
         //      dH1 = (dH2 W2) * (1 - H1^2)  (wave w: L2 inputs of its tiles, rows = samples)
         {
             constexpr int kRows = kTR / kFW;
@@ -1135,11 +829,9 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
 #pragma unroll 1
         for (int j = 0; j < kNT; ++j) {
             // dH1^T = W2^T dH2^T, gated in place of H1
-            if (j > 0) w_prefetch(pw2t, W2T, kH / 16, ft0 + j, lane);
             EpiGate eg{H1, 32 * (ft0 + j) + 4 * h, r};
-#if DXRL_DH2_IN_DH1
             // dH2 tile -> HBM (Y of the dW2 GEMM) in this phase's shadow: one 16-byte chunk per
-            // thread every 8th step (the stores go out after every weight fragment, so no
+            // thread every kEvery-th step (the stores go out after every weight fragment, so no
             // fragment wait queues behind them; H2 holds dH2 read-only here)
             // The chunks go out from the second sample tile on (k-step 16 + kEvery i): a store
             // issued among the first tile's k-steps, while W2T fragments still stream in, made
@@ -1149,42 +841,35 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
             // flight, the B-operand prefetch included).
             bf16x8 cv;
             const auto copy_k = [&](int sidx) {
-                // (64-sample tiles: too few steps after the first tile; they start at step 3)
-                constexpr int kSteps = kMT * (kH / 16);
-                constexpr int kFirst = (kSteps - kH / 16) / kCopyU >= 4 ? kH / 16 : 2;
-                constexpr int kEvery = (kSteps - kFirst) / kCopyU, kAhead = kEvery >= 4 ? 3 : kEvery - 1;
-                static_assert(kAhead >= 1 && kFirst >= kAhead && kFirst + kEvery * kCopyU <= kSteps, "copy schedule");
+                constexpr int kSteps = kMT * (kH / 16), kFirst = kH / 16;
+                constexpr int kEvery = (kSteps - kFirst) / kCopyU, kAhead = 3;
+                static_assert(kEvery > kAhead && kFirst >= kAhead && kFirst + kEvery * kCopyU <= kSteps, "copy schedule");
                 if (diag & 1 || sidx < kFirst - kAhead) return;
                 const int i = (sidx - (kFirst - kAhead)) / kEvery, ph = (sidx - (kFirst - kAhead)) % kEvery;
                 const int c = tid_l + kFThreads * i, row = c >> 5, col = 8 * (c & 31);
                 if (ph == 0 && i < kCopyU) cv = *reinterpret_cast<const bf16x8*>(H2 + row * kHp + col);
                 if (ph == kAhead && i < kCopyU && m0 + row < p.rows) store_dh2(p.dh2_out + (m0 + row) * kH + col, cv);
             };
-            if constexpr (kDw1Tail) {
-                // dW1 of sample blocks 0..2 (gated during the tile loop) beside the tail epilogue
-                // of block 3; block 3's dW1 follows it (same MFMAs, same kk order as below)
-                const auto dw1_tail = [&](int q) {
-                    if (q != 1 && q != 3 && q != 5) return;
-                    const int kk = 32 * (q >> 1);
-                    if (kk == 0 && tile + gridDim.x < ntiles) fetch_x(tile + gridDim.x);
-                    bf16x8 b[3];
+            // dW1 += dH1^T X without a barrier after dH1: a wave's dW1 reads only its own dH1 columns
+            // (and X), so the MFMAs of sample blocks 0..2 (gated during the tile loop) issue beside
+            // the tail epilogue of block 3 (VALU only); block 3's dW1 follows it (same MFMAs, same
+            // kk order), and the db2 column sums' second stage moves behind the end-of-tile barrier
+            const auto dw1_tail = [&](int q) {
+                if (q != 1 && q != 3 && q != 5) return;
+                const int kk = 32 * (q >> 1);
+                if (kk == 0 && tile + gridDim.x < ntiles) fetch_x(tile + gridDim.x);
+                bf16x8 b[3];
 #pragma unroll
-                    for (int ci = 0; ci < 3; ++ci) b[ci] = wg_frag<kXp>(X, 16 * ci, kk, lane);
+                for (int ci = 0; ci < 3; ++ci) b[ci] = tr_frag16_eo<kXp>(X, 16 * ci, kk, lane);
 #pragma unroll
-                    for (int ri = 0; ri < 2; ++ri) {
-                        const bf16x8 a = wg_frag<kHp>(H1, 32 * ft0 + 16 * ri, kk, lane);
+                for (int ri = 0; ri < 2; ++ri) {
+                    const bf16x8 a = tr_frag16_eo<kHp>(H1, 32 * ft0 + 16 * ri, kk, lane);
 #pragma unroll
-                        for (int ci = 0; ci < 3; ++ci)
-                            if (!(diag & 4)) acc1[0][ri][ci] = mfma16(a, b[ci], acc1[0][ri][ci]);
-                    }
-                };
-                fwd_pipe<kH / 16, kHp, kMT>(pw2t, H2, lane, eg, NoHook{}, false, copy_k, dw1_tail);
-            } else {
-                fwd_pipe<kH / 16, kHp, kMT>(pw2t, H2, lane, eg, NoHook{}, false, copy_k);
-            }
-#else
-            fwd_pipe<kH / 16, kHp, kMT>(pw2t, H2, lane, eg);
-#endif
+                    for (int ci = 0; ci < 3; ++ci)
+                        if (!(diag & 4)) acc1[ri][ci] = mfma16(a, b[ci], acc1[ri][ci]);
+                }
+            };
+            fwd_pipe<kH / 16, kHp, kMT>(pw2t, H2, lane, eg, NoHook{}, false, copy_k, dw1_tail);
         }
         STAMP(11);
         const auto db2_stage2 = [&]() {
@@ -1194,39 +879,25 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
                 for (int w = 0; w < kFW; ++w) db2 += cs[w * kH + tid_l];
             }
         };
-        if constexpr (!kDw1Tail) {
-            __syncthreads();
-            STAMP(12);
-            // ---- dW1 += dH1^T X (wave w: hidden rows of its tiles, input columns 0..63); LDS only,
-            //      so the next tile's X loads go out now
-            if (tile + gridDim.x < ntiles) fetch_x(tile + gridDim.x);
-#if !DXRL_DH2_IN_DH1
-            // dH2 tile -> HBM (Y of the dW2 GEMM; H2 holds dH2 until the next tile's L2)
-            copy_tile_out_n<kFThreads, kTR>(H2, p.dh2_out, kH, m0, p.rows, tid, diag);
-#endif
-            db2_stage2();
-        }
 #pragma unroll
-        for (int kk = kDw1Tail ? 96 : 0; kk < kTR; kk += 32) {
+        for (int kk = kTR - 32; kk < kTR; kk += 32) {  // dW1 of sample block 3
             bf16x8 b[3];
 #pragma unroll
-            for (int ci = 0; ci < 3; ++ci) b[ci] = wg_frag<kXp>(X, 16 * ci, kk, lane);
+            for (int ci = 0; ci < 3; ++ci) b[ci] = tr_frag16_eo<kXp>(X, 16 * ci, kk, lane);
 #pragma unroll
-            for (int j = 0; j < kNT; ++j)
+            for (int ri = 0; ri < 2; ++ri) {
+                const bf16x8 a = tr_frag16_eo<kHp>(H1, 32 * ft0 + 16 * ri, kk, lane);
 #pragma unroll
-                for (int ri = 0; ri < 2; ++ri) {
-                    const bf16x8 a = wg_frag<kHp>(H1, 32 * (ft0 + j) + 16 * ri, kk, lane);
-#pragma unroll
-                    for (int ci = 0; ci < 3; ++ci)
-                        if (!(diag & 4)) acc1[j][ri][ci] = mfma16(a, b[ci], acc1[j][ri][ci]);
-                }
+                for (int ci = 0; ci < 3; ++ci)
+                    if (!(diag & 4)) acc1[ri][ci] = mfma16(a, b[ci], acc1[ri][ci]);
+            }
         }
         STAMP(13);
         __syncthreads();
         STAMP(14);
-        // (kDw1Tail: the dout region holding the row-group sums is not written again before the
-        // next tile's head, two barriers on)
-        if constexpr (kDw1Tail) db2_stage2();
+        // (the dout region holding the row-group sums is not written again before the next tile's
+        // head, two barriers on)
+        db2_stage2();
     }
     if ((diag & 8) && lane == 0) {
 #pragma unroll
@@ -1240,22 +911,20 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
     {
         const int c16 = lane & 15, g16 = lane >> 4;
 #pragma unroll
-        for (int j = 0; j < kNT; ++j)
+        for (int i = 0; i < 4; ++i) {
+            const int o = 4 * g16 + i;  // head row (rows 16..31 stay zero: k_fused_scatter)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int o = 4 * g16 + i;  // head row (rows 16..31 stay zero: k_fused_scatter)
+            for (int ci = 0; ci < 2; ++ci) part[kPartW3 + o * kPW3C + 32 * ft0 + 16 * ci + c16] = acc3[ci][i];
 #pragma unroll
-                for (int ci = 0; ci < 2; ++ci) part[kPartW3 + o * kPW3C + 32 * (ft0 + j) + 16 * ci + c16] = acc3[j][ci][i];
+            for (int ri = 0; ri < 2; ++ri) {
+                float* row = part + kPartW1 + (32 * ft0 + 16 * ri + o) * kPW1C;
 #pragma unroll
-                for (int ri = 0; ri < 2; ++ri) {
-                    float* row = part + kPartW1 + (32 * (ft0 + j) + 16 * ri + o) * kPW1C;
-#pragma unroll
-                    for (int ci = 0; ci < 3; ++ci) row[16 * ci + c16] = acc1[j][ri][ci][i];
-                }
+                for (int ci = 0; ci < 3; ++ci) row[16 * ci + c16] = acc1[ri][ci][i];
             }
+        }
     }
     if (tid < kH) part[kPartB2 + tid] = db2;
-    if constexpr (kCH16) {
+    if constexpr (!actor) {
         // value-head bias gradient and value loss: lanes 0..15 of every wave, summed in
         // (wave, lane) order
         float* red = reinterpret_cast<float*>(lds);
@@ -1279,9 +948,7 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
             p.loss[(int64_t)blockIdx.x * 4 + 1] = s;
             for (int r = blockIdx.x + gridDim.x; r < p.loss_rows; r += gridDim.x) p.loss[(int64_t)r * 4 + 1] = 0.0;
         }
-        return;
-    }
-    if constexpr (kAH16) {
+    } else {
         // head rows o = 4 g + i of lanes 16 g .. 16 g + 15 of every wave, summed in (wave, lane)
         // order; the loss terms over every lane in thread order
         float* red = reinterpret_cast<float*>(lds);              // [512][8]: dls[0..3], db3[0..3]
@@ -1315,47 +982,10 @@ __global__ __launch_bounds__(64 * kFW, kTR == 64 ? 2 : 1) void k_pg_fused(FusedA
                 double s = 0.0;
                 for (int t = 0; t < kFThreads; ++t) s += lred[t * 4 + k];
                 p.loss[(int64_t)blockIdx.x * 4 + k] = s;
+                // rows of workgroups this launch does not have (fewer tiles than the caller's grid):
+                // zeroed, so a sum over all rows never picks up an earlier, larger pass
                 for (int r = blockIdx.x + gridDim.x; r < p.loss_rows; r += gridDim.x) p.loss[(int64_t)r * 4 + k] = 0.0;
             }
-        }
-        return;
-    }
-    float* red = reinterpret_cast<float*>(lds);              // [head lanes][16]
-    double* lred = reinterpret_cast<double*>(lds + kOffH1);  // [head lanes][4]
-    if (wave < kHW) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            red[tid * 16 + q] = dls[q];
-            red[tid * 16 + 8 + q] = db3[q];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) lred[tid * 4 + k] = (double)lsum[k];
-    }
-    __syncthreads();
-    if (tid < 32) {  // head row o: lanes with h = (o >> 2) & 1, register q = (o & 3) + 4 (o >> 3)
-        const int o = tid, hh = (o >> 2) & 1, q = (o & 3) + 4 * (o >> 3);
-        float sl = 0.0f, sb = 0.0f;
-        if (o < 16) {
-            for (int w = 0; w < kHW; ++w)
-                for (int rr = 0; rr < 32; ++rr) {
-                    const int t = 64 * w + 32 * hh + rr;
-                    sl += red[t * 16 + q];
-                    sb += red[t * 16 + 8 + q];
-                }
-        }
-        if (o < 16) {
-            part[kPartW3 + o * kPW3C + kH] = sb;  // bias column of the head
-            part[kPartLs + o] = sl;
-        }
-    } else if (tid < 36) {
-        const int k = tid - 32;
-        double s = 0.0;
-        for (int t = 0; t < 64 * kHW; ++t) s += lred[t * 4 + k];
-        if (actor == (k != 1)) {
-            p.loss[(int64_t)blockIdx.x * 4 + k] = s;
-            // rows of workgroups this launch does not have (fewer tiles than the caller's grid):
-            // zeroed, so a sum over all rows never picks up an earlier, larger pass
-            for (int r = blockIdx.x + gridDim.x; r < p.loss_rows; r += gridDim.x) p.loss[(int64_t)r * 4 + k] = 0.0;
         }
     }
 }
@@ -1407,7 +1037,7 @@ __device__ __forceinline__ double sumsq4(float a, float b, float c, float d) {
 }
 
 // Critic values (the forward-only pass) as its own kernel, pipelined across tiles: the layer-by-layer
-// instantiation k_pg_fused<8, 128, false, 1> closes four barriers per tile (X stored, L1 -> L2,
+// instantiation k_pg_fused<false, 1> closes four barriers per tile (X stored, L1 -> L2,
 // L2 -> head, end of tile).  Here the next tile's X is stored while L2 runs (X is free once L1 is
 // done) and the next tile's L1 runs beside this tile's value head (H1 is free once L2 is done, H2
 // is not written again until the next L2): two barriers per tile.  Rows: every workgroup runs the
@@ -1418,12 +1048,6 @@ __device__ __forceinline__ double sumsq4(float a, float b, float c, float d) {
 // same fwd_pipe_w chains, epilogues and 16x16x32 head as the layer-by-layer pass, and a row's V
 // depends only on its own observation row, so V is bit for bit that pass's V
 // (test_values_kernel_equals_layer_by_layer_pass).
-#ifndef DXRL_FWD_VALUES
-#define DXRL_FWD_VALUES 1
-#endif
-#ifndef DXRL_VALUES_HEAD_SPLIT
-#define DXRL_VALUES_HEAD_SPLIT 1
-#endif
 template <int KS, int kLda, typename Epi>
 __device__ __forceinline__ void fwd_pipe_w_mt(int mt, const bf16x8 (&wf)[KS], const bf16* A, int lane, Epi& epi) {
     switch (mt) {  // workgroup-uniform
@@ -1434,16 +1058,14 @@ __device__ __forceinline__ void fwd_pipe_w_mt(int mt, const bf16x8 (&wf)[KS], co
     }
 }
 __global__ __launch_bounds__(512, 1) void k_pg_values(FusedArgs p) {
-    using L = TileLds<128>;
+    using L = TileLds;
     constexpr int kXU = 128 * (kIn / 8) / 512;
     __shared__ __attribute__((aligned(16))) bf16 lds[L::kElems];
     bf16* X = lds + L::kOffX;
     bf16* H1 = lds + L::kOffH1;
     bf16* H2 = lds + L::kOffH2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-#if DXRL_FUSED_PRIO
-    if (__builtin_amdgcn_readfirstlane(wave) >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
+    if (__builtin_amdgcn_readfirstlane(wave) >= 4) __builtin_amdgcn_s_setprio(1);  // as k_pg_fused
     // this workgroup's tiles: k < full -> rows (b + k G) 128 .. + 127; k == full -> its share of the rest
     const int64_t G = gridDim.x, b = blockIdx.x;
     const int64_t full = p.rows / 128 / G, main_rows = full * G * 128, rem = p.rows - main_rows;
@@ -1536,8 +1158,8 @@ __global__ __launch_bounds__(512, 1) void k_pg_values(FusedArgs p) {
             break;
         }
         // L1(k + 1) beside the heads: the two waves of a SIMD in opposite orders, so one's head MFMAs
-        // run beside the other's L1 epilogue (DXRL_VALUES_HEAD_SPLIT; 0: head first on every wave)
-        if (DXRL_VALUES_HEAD_SPLIT && __builtin_amdgcn_readfirstlane(wave) >= 4) {
+        // run beside the other's L1 epilogue
+        if (__builtin_amdgcn_readfirstlane(wave) >= 4) {
             fwd_pipe_w_mt<kIn / 16, kXp>(mts(k + 1), w1, X, lane, e1);
             head();
         } else {
@@ -1660,7 +1282,7 @@ extern "C" {
 
 int dxrl_pg_fused_sizes(int32_t* tile_rows, int64_t* partial_floats_per_block) {
     DXRL_REQUIRE(tile_rows && partial_floats_per_block, "null outputs");
-    *tile_rows = 128;  // the largest tile; launches use up to two workgroups per CU (grid <= 2 CUs)
+    *tile_rows = kTR;
     *partial_floats_per_block = kPartSize;
     return DXRL_OK;
 }
@@ -1867,22 +1489,15 @@ int fused_kernel(const dxrl_pg_fused_args* a, hipStream_t st, int* grid_out) {
     f.part = a->partial;
     f.loss = a->loss_partial;
     f.loss_rows = a->grid;
-    // tile geometry: 128-sample tiles, one 8-wave workgroup per CU (160 KiB LDS), or 64-sample
-    // tiles, two 4-wave workgroups per CU (80 KiB each) -- DXRL_FUSED_TILE=64|128 (A/B)
-    static const int tile = [] {
-        const char* v = getenv("DXRL_FUSED_TILE");
-        return v && atoi(v) == 64 ? 64 : 128;
-    }();
+    // one workgroup per CU (160 KiB LDS), persistent over the 128-sample tiles
     static const int cus = [] {
         int n = 0, device = 0;
         (void)hipGetDevice(&device);  // the caller's DeviceGuard made it current
         return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0 ? n
                                                                                                             : 256;
     }();
-    const int waves = tile == 64 ? 4 : 8;  // the instantiations launched below (128-sample tiles: 8 waves)
-    const int64_t ntiles = (a->rows + tile - 1) / tile;
-    const int64_t cap = (int64_t)cus * (tile == 64 ? 2 : 1);
-    int64_t g64 = a->grid < cap ? a->grid : cap;
+    const int64_t ntiles = (a->rows + kTR - 1) / kTR;
+    int64_t g64 = a->grid < cus ? a->grid : cus;
     if (ntiles < g64) g64 = ntiles;
     const int grid = (int)g64;
     static const int diag = [] {
@@ -1894,36 +1509,33 @@ int fused_kernel(const dxrl_pg_fused_args* a, hipStream_t st, int* grid_out) {
     if ((diag & 8) && !stamps) (void)hipMalloc(&stamps, (size_t)65536 * 8 * 16 * 8);
     f.stamps = stamps;
     const bool dg = diag != 0;
-    if (tile == 64) {  // A/B geometry: the diagnostic instantiations only
-        if (!train) hipLaunchKernelGGL((k_pg_fused<4, 64, false, 1, true>), dim3(grid), dim3(256), 0, st, f);
-        else if (!c) hipLaunchKernelGGL((k_pg_fused<4, 64, true, 0, true>), dim3(grid), dim3(256), 0, st, f);
-        else hipLaunchKernelGGL((k_pg_fused<4, 64, true, 1, true>), dim3(grid), dim3(256), 0, st, f);
-    } else if (!train) {
+    if (!train) {
         // A/B and the bit-identity test: the layer-by-layer instantiation (DXRL_FWD_LAYERED=1, read per call)
         const char* lv = getenv("DXRL_FWD_LAYERED");
         const bool layered = lv && atoi(lv) != 0;
-        if (dg) hipLaunchKernelGGL((k_pg_fused<8, 128, false, 1, true>), dim3(grid), dim3(512), 0, st, f);
-        else if (DXRL_FWD_VALUES && !layered) hipLaunchKernelGGL(k_pg_values, dim3(grid), dim3(512), 0, st, f);
-        else hipLaunchKernelGGL((k_pg_fused<8, 128, false, 1, false>), dim3(grid), dim3(512), 0, st, f);
+        if (dg) hipLaunchKernelGGL((k_pg_fused<false, 1, true>), dim3(grid), dim3(512), 0, st, f);
+        else if (!layered) hipLaunchKernelGGL(k_pg_values, dim3(grid), dim3(512), 0, st, f);
+        else hipLaunchKernelGGL((k_pg_fused<false, 1, false>), dim3(grid), dim3(512), 0, st, f);
     } else if (!c) {
         // (h2_in: the layer-2 activations from the rollout; the diagnostic instantiations recompute
         // them -- the same bits either way)
-        if (dg && DXRL_H2_STAMPS && f.h2_in) hipLaunchKernelGGL((k_pg_fused<8, 128, true, 0, true, DXRL_H2_STAMPS != 0>), dim3(grid), dim3(512), 0, st, f);
-        else if (dg) hipLaunchKernelGGL((k_pg_fused<8, 128, true, 0, true>), dim3(grid), dim3(512), 0, st, f);
-        else if (f.h2_in) hipLaunchKernelGGL((k_pg_fused<8, 128, true, 0, false, true>), dim3(grid), dim3(512), 0, st, f);
-        else hipLaunchKernelGGL((k_pg_fused<8, 128, true, 0, false>), dim3(grid), dim3(512), 0, st, f);
+        if (dg && DXRL_H2_STAMPS && f.h2_in) hipLaunchKernelGGL((k_pg_fused<true, 0, true, DXRL_H2_STAMPS != 0>), dim3(grid), dim3(512), 0, st, f);
+        else if (dg) hipLaunchKernelGGL((k_pg_fused<true, 0, true>), dim3(grid), dim3(512), 0, st, f);
+        else if (f.h2_in) hipLaunchKernelGGL((k_pg_fused<true, 0, false, true>), dim3(grid), dim3(512), 0, st, f);
+        else hipLaunchKernelGGL((k_pg_fused<true, 0, false>), dim3(grid), dim3(512), 0, st, f);
     } else {
-        if (dg && DXRL_H2_STAMPS && f.h2_in) hipLaunchKernelGGL((k_pg_fused<8, 128, true, 1, true, DXRL_H2_STAMPS != 0>), dim3(grid), dim3(512), 0, st, f);
-        else if (dg) hipLaunchKernelGGL((k_pg_fused<8, 128, true, 1, true>), dim3(grid), dim3(512), 0, st, f);
-        else if (f.h2_in) hipLaunchKernelGGL((k_pg_fused<8, 128, true, 1, false, true>), dim3(grid), dim3(512), 0, st, f);
-        else hipLaunchKernelGGL((k_pg_fused<8, 128, true, 1, false>), dim3(grid), dim3(512), 0, st, f);
+        if (dg && DXRL_H2_STAMPS && f.h2_in) hipLaunchKernelGGL((k_pg_fused<true, 1, true, DXRL_H2_STAMPS != 0>), dim3(grid), dim3(512), 0, st, f);
+        else if (dg) hipLaunchKernelGGL((k_pg_fused<true, 1, true>), dim3(grid), dim3(512), 0, st, f);
+        else if (f.h2_in) hipLaunchKernelGGL((k_pg_fused<true, 1, false, true>), dim3(grid), dim3(512), 0, st, f);
+        else hipLaunchKernelGGL((k_pg_fused<true, 1, false>), dim3(grid), dim3(512), 0, st, f);
     }
     if (int rc = launch_check("k_pg_fused")) return rc;
     if (diag & 8) {  // print the mean cycles per segment per wave (diagnostic builds only)
+        constexpr int waves = kFW;
         std::vector<unsigned long long> h((size_t)grid * waves * 16);
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost);
-        fprintf(stderr, "fused net=%d train=%d tile=%d waves=%d cycles/wave:", a->net, (int)train, tile, waves);
+        fprintf(stderr, "fused net=%d train=%d tile=%d waves=%d cycles/wave:", a->net, (int)train, kTR, waves);
         // (first half of the waves / second half: the two waves sharing a SIMD are w and w + waves / 2)
         for (int k = 0; k < 16; ++k) {
             double sum[2] = {0, 0};
