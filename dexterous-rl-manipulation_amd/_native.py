@@ -217,6 +217,12 @@ PG_LOG_COLUMNS = ("iteration", "env_steps", "episodes", "mean_return", "mean_len
 PG_LOG_NAMED = len(PG_LOG_COLUMNS)  # DXRL_PG_LOG_NAMED
 PG_LOG_COLS = 24                    # DXRL_PG_LOG_COLS
 PG_LOG_IS_BEST = PG_LOG_COLUMNS.index("is_best")
+# enum dxrl_pg_log_rank_col: the named entries of a rank record (dxrl_pg_log_rank_pack), in order
+PG_LOG_RANK_COLUMNS = ("samples", "reward_sum", "value_sum", "done_count", "target_mean", "target_m2",
+                       "residual_mean", "residual_m2", "episodes", "length_sum", "successes", "return_sum",
+                       "policy_loss_sum", "value_se_sum", "clip_sum", "kl_sum", "loss_rows")
+PG_LOG_RANK_NAMED = len(PG_LOG_RANK_COLUMNS)  # DXRL_PG_LOG_RANK_NAMED
+PG_LOG_RANK_DOUBLES = 20                      # DXRL_PG_LOG_RANK_DOUBLES
 
 
 class PgLogHeader(C.Structure):
@@ -376,6 +382,8 @@ _SIGS = {
     "dxrl_study_summarize": (C.c_int, [_I32, C.POINTER(StudySummaryArgs), _P]),
     "dxrl_pg_log_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_log_row": (C.c_int, [_I32, C.POINTER(PgLogArgs), _P]),
+    "dxrl_pg_log_rank_pack": (C.c_int, [_I32, C.POINTER(PgLogArgs), _P, _P]),
+    "dxrl_pg_log_row_world": (C.c_int, [_I32, C.POINTER(PgLogArgs), _P, _I32, _P, _P]),
     "dxrl_pg_val_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_val_row": (C.c_int, [_I32, C.POINTER(PgValArgs), _P]),
     "dxrl_pg_val_levels_partial_doubles": (C.c_int, [_I32, _I64, _I64, C.POINTER(_I64)]),

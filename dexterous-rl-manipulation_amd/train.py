@@ -16,10 +16,20 @@
                        first-three x first-three combinations; at most 16 levels).  --val-keep-best may
                        then name a score over the levels: worst_success_rate, mean_success_rate,
                        mean_noisy_success_rate, worst_mean_return
+  --gpus N [--backend nccl|gloo]
+                       a sharded run, one rank per GPU: --envs is the global count, split equally; every
+                       rank trains its shard (global env ids rank * n ..) with fit(merge_ranks=True), so
+                       all ranks hold the same log.  Without WORLD_SIZE in the environment the ranks are
+                       started as a child process (python -m torch.distributed.run on 127.0.0.1) before any
+                       GPU work here; under torchrun the ranks are used as given.  Rank 0 writes the log and
+                       the policies and prints the statistics; every rank writes DIR/checkpoint.rank{r}.npz,
+                       and --resume DIR reads each rank's own file.  --backend gloo (rank r on GPU r mod the
+                       visible count; ranks may share a GPU) is a harness check only
 
 Writes DIR/training_log.json (TrainingLog, with the validation curve), DIR/best_policy.npz
 (MLPActorPolicy, when some iteration qualified as best), DIR/best_val_policy.npz (the actor of the
-best validation) and DIR/checkpoint.npz (PGTrainer.load_checkpoint / --resume).
+best validation) and DIR/checkpoint.npz (PGTrainer.load_checkpoint / --resume; with --gpus N one
+DIR/checkpoint.rank{r}.npz per rank).
 """
 from __future__ import annotations
 
@@ -42,7 +52,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                    help="reward of a --config-name run (default: dense)")
     p.add_argument("--iterations", type=int, required=True)
     p.add_argument("--out", metavar="DIR", required=True)
-    p.add_argument("--resume", metavar="CKPT", default=None, help="continue the run of a checkpoint.npz")
+    p.add_argument("--resume", metavar="CKPT", default=None,
+                   help="continue the run of a checkpoint.npz (with --gpus N: of a directory's checkpoint.rank{r}.npz)")
     p.add_argument("--keep-best", metavar="COL", default="mean_return", choices=list(_SCORE_COLUMNS) + ["none"])
     p.add_argument("--min-episodes", type=int, default=1)
     p.add_argument("--converge", nargs=3, metavar=("COL", "W", "THR"), default=None)
@@ -71,7 +82,18 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--minibatches", type=int, default=1)
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--device", default=None)
+    p.add_argument("--gpus", type=int, default=1, metavar="N", help="ranks of a sharded run, one per GPU")
+    p.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
+                   help="process group of a --gpus N run: nccl (RCCL, one rank per GPU) or gloo (harness check)")
     a = p.parse_args(argv)
+    if a.gpus < 1:
+        p.error("--gpus must be >= 1")
+    if a.gpus > 1:
+        if a.device is not None:
+            p.error("--device goes with one rank: a --gpus N run puts rank r on GPU r")
+        total = a.envs or (WORKLOADS[a.config_name or "easy"]["envs"] if a.config is None else 4096)
+        if total % a.gpus:
+            p.error(f"--envs {total} does not split equally over --gpus {a.gpus}")
     if a.iterations < 0:
         p.error("--iterations must be >= 0")
     if a.converge is not None:
@@ -123,8 +145,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     return a
 
 
-def _build(a, fresh: bool):
-    """(env, trainer or None): the run's env, and with `fresh` its new trainer."""
+def _build(a, fresh: bool, rank: int = 0, world: int = 1, group=None):
+    """(env, trainer or None): the run's env, and with `fresh` its new trainer.  With world > 1
+    this rank's shard: --envs / world envs at global env offset rank * n."""
     from . import experiments, workloads
     from .envs import VecEnv
     from .experiments import CurriculumConfig
@@ -132,22 +155,25 @@ def _build(a, fresh: bool):
     kw = dict(horizon=a.horizon, epochs=a.epochs, minibatches=a.minibatches, max_steps=a.max_steps)
     if a.config is None:
         w = workloads.WORKLOADS[a.config_name]
+        n = (a.envs or w["envs"]) // world
         if a.seed is not None:
             kw["seed"] = a.seed
         if fresh:
-            return workloads.build_pg_workload(a.config_name, a.device, envs=a.envs, reward_type=a.reward_type, **kw)
-        env = VecEnv(a.envs or w["envs"], curriculum_config=CurriculumConfig.named(w["curriculum"]),
-                     reward_type=a.reward_type, seed=workloads.ENV_SEED, device=a.device)
+            return workloads.build_pg_workload(a.config_name, a.device, rank=rank, world=world, process_group=group,
+                                               envs=n, reward_type=a.reward_type, **kw)
+        env = VecEnv(n, curriculum_config=CurriculumConfig.named(w["curriculum"]),
+                     reward_type=a.reward_type, seed=workloads.ENV_SEED, device=a.device, global_env_offset=rank * n)
         return env, None
     ex = experiments.load_config(a.config)
     sc = ex.curriculum_scheduler
     seed = ex.training.seed if a.seed is None else a.seed
-    env = VecEnv(a.envs or 4096, curriculum_config=CurriculumConfig.named(sc.initial_difficulty),
+    n = (a.envs or 4096) // world
+    env = VecEnv(n, curriculum_config=CurriculumConfig.named(sc.initial_difficulty),
                  reward_type=ex.training.reward_type, max_episode_steps=ex.training.max_episode_steps, seed=seed,
-                 device=a.device)
+                 device=a.device, global_env_offset=rank * n)
     if not fresh:
         return env, None
-    tr = PGTrainer(env, TrainerConfig(seed=seed, **kw))
+    tr = PGTrainer(env, TrainerConfig(seed=seed, **kw), process_group=group, world_size=world)
     tr.attach_curriculum(experiments.CurriculumScheduler(
         CurriculumConfig.named(sc.initial_difficulty), CurriculumConfig.named(sc.target_difficulty),
         sc.success_rate_threshold, sc.min_episodes_before_progression, sc.window_size, sc.progression_steps,
@@ -156,14 +182,66 @@ def _build(a, fresh: bool):
     return env, tr
 
 
+DIST_TIMEOUT_S = 300  # bound of the process group's rendezvous and of every collective
+
+
+def launch_ranks(a, argv: List[str]) -> int:
+    """`train --gpus N` without torchrun: start N ranks (torch.distributed.run, rendezvous on
+    127.0.0.1) as a child process and return its exit code.  Called before this process does any
+    GPU work (device_count() initialises nothing on ROCm)."""
+    import socket
+    import subprocess
+    import torch
+    have = torch.cuda.device_count()
+    if have < (1 if a.backend == "gloo" else a.gpus):
+        print(f"train: --gpus {a.gpus} needs {a.gpus} visible GPUs, found {have}", file=sys.stderr)
+        return 2
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    env = dict(os.environ)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # where the import shim lives
+    env["PYTHONPATH"] = root + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
+           "--master-addr=127.0.0.1", f"--master-port={port}", "-m", "dexterous_rl_manipulation_amd.train"] + argv
+    return subprocess.call(cmd, env=env)
+
+
+def join_ranks(a):
+    """(world, rank, process group) of this rank of a --gpus N run (RANK / LOCAL_RANK / WORLD_SIZE
+    as torchrun sets them); sets a.device to the rank's GPU."""
+    import datetime
+    import torch
+    import torch.distributed as dist
+    world, rank = int(os.environ["WORLD_SIZE"]), int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != a.gpus:
+        raise SystemExit(f"train: --gpus {a.gpus} but WORLD_SIZE={world}")
+    if a.backend == "gloo":
+        local %= max(1, torch.cuda.device_count())
+    torch.cuda.set_device(local)
+    a.device = f"cuda:{local}"
+    kw = {"device_id": torch.device("cuda", local)} if a.backend == "nccl" else {}
+    dist.init_process_group(a.backend, rank=rank, world_size=world,
+                            timeout=datetime.timedelta(seconds=DIST_TIMEOUT_S), **kw)
+    return world, rank, dist.group.WORLD
+
+
 def main(argv: Optional[List[str]] = None) -> int:
+    argv = list(sys.argv[1:] if argv is None else argv)
     a = parse_args(argv)
+    if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        return launch_ranks(a, argv)
     from .trainer import PGTrainer
+    world, rank, group = join_ranks(a) if a.gpus > 1 else (1, 0, None)
+    sharded = world > 1
     os.makedirs(a.out, exist_ok=True)
-    env, tr = _build(a, fresh=a.resume is None)
+    env, tr = _build(a, a.resume is None, rank, world, group)
     base_config = env.curriculum_configs[0]  # the run's curriculum config, the same on a resume
     if a.resume is not None:
-        tr = PGTrainer.load_checkpoint(a.resume, env)
+        ckpt = os.path.join(a.resume, f"checkpoint.rank{rank}.npz") if sharded else a.resume
+        tr = PGTrainer.load_checkpoint(ckpt, env, process_group=group, world_size=world)
     kw = {}
     if a.validate_every:
         from .evaluation import HeldOutObjectSet
@@ -174,14 +252,20 @@ def main(argv: Optional[List[str]] = None) -> int:
         kw = dict(validation=plan, validate_every=a.validate_every, val_keep_best=a.val_keep_best,
                   patience=a.patience, stop_on_patience=bool(a.patience and a.poll_every))
     log = tr.fit(a.iterations, keep_best=a.keep_best, min_episodes=a.min_episodes, converge=a.converge,
-                 stop_on_converge=a.stop_on_converge, poll_every=a.poll_every, **kw)
-    log.save(os.path.join(a.out, "training_log.json"))
-    if log.best_row is not None:
-        tr.best_policy().save(os.path.join(a.out, "best_policy.npz"))
-    if log.validation is not None and log.validation.best_row is not None:
-        tr.best_policy(which="validation").save(os.path.join(a.out, "best_val_policy.npz"))
-    tr.save_checkpoint(os.path.join(a.out, "checkpoint.npz"))
-    print(json.dumps(log.statistics()))
+                 stop_on_converge=a.stop_on_converge, poll_every=a.poll_every, merge_ranks=sharded, **kw)
+    if rank == 0:  # every rank holds the same log and best parameters
+        log.save(os.path.join(a.out, "training_log.json"))
+        if log.best_row is not None:
+            tr.best_policy().save(os.path.join(a.out, "best_policy.npz"))
+        if log.validation is not None and log.validation.best_row is not None:
+            tr.best_policy(which="validation").save(os.path.join(a.out, "best_val_policy.npz"))
+    tr.save_checkpoint(os.path.join(a.out, f"checkpoint.rank{rank}.npz" if sharded else "checkpoint.npz"))
+    if rank == 0:
+        print(json.dumps(log.statistics()))
+    if sharded:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
     return 0
 
 

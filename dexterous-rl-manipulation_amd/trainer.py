@@ -779,14 +779,16 @@ class PGTrainer:
     def fit(self, iterations: int, keep_best: Optional[str] = "mean_return", min_episodes: int = 1, converge=None,
             stop_on_converge: bool = False, poll_every: int = 0, validation=None, validate_every: int = 1,
             val_keep_best: Optional[str] = "success_rate", min_delta: float = 0.0, patience: int = 0,
-            stop_on_patience: bool = False):
+            stop_on_patience: bool = False, merge_ranks: bool = False):
         """`iterations` x (iteration() + one device log row), with `validation` (a validation_plan)
-        a held-out validation row every validate_every iterations; returns the run's TrainingLog."""
+        a held-out validation row every validate_every iterations; returns the run's TrainingLog.
+        merge_ranks: the run of a sharded trainer -- every row is finished from all ranks' records
+        (one all-gather per row) and is identical on all ranks; all ranks pass the same arguments."""
         from . import training_run
         return training_run.fit(self, iterations, keep_best=keep_best, min_episodes=min_episodes, converge=converge,
                                 stop_on_converge=stop_on_converge, poll_every=poll_every, validation=validation,
                                 validate_every=validate_every, val_keep_best=val_keep_best, min_delta=min_delta,
-                                patience=patience, stop_on_patience=stop_on_patience)
+                                patience=patience, stop_on_patience=stop_on_patience, merge_ranks=merge_ranks)
 
     def validation_plan(self, heldout_set, episodes_per_object: int = 5, seed: int = 0, device_seed: int = 0,
                         max_steps: Optional[int] = None, deterministic: bool = True, solve_threshold: float = 1.0,
@@ -817,9 +819,9 @@ class PGTrainer:
         training_run.save_checkpoint(self, path)
 
     @classmethod
-    def load_checkpoint(cls, path, env: VecEnv) -> "PGTrainer":
+    def load_checkpoint(cls, path, env: VecEnv, process_group=None, world_size: int = 1) -> "PGTrainer":
         from . import training_run
-        return training_run.load_checkpoint(cls, path, env)
+        return training_run.load_checkpoint(cls, path, env, process_group=process_group, world_size=world_size)
 
     # ------------------------------------------------------------------ stats
     def episode_stats(self) -> Dict[str, float]:

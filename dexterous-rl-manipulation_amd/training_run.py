@@ -32,6 +32,11 @@ the episode launch also accumulates the five history words of every episode, and
 ``dxrl_pg_val_failure_row`` (csrc/dxrl_pg_val_failure.hip) classifies every episode with the failure
 taxonomy and adds, per level, a table of the modes, a row of totals and -- with common random
 numbers -- the class transitions against the baseline.
+
+``fit(merge_ranks=True)`` is the run of a sharded (collective) trainer: per logged iteration
+``dxrl_pg_log_rank_pack`` reduces the rank's tape to one record, the records are all-gathered, and
+``dxrl_pg_log_row_world`` finishes the row from all of them, so every rank holds the same table,
+header and best parameters; ``log.ranks`` keeps the records, and each rank checkpoints its own file.
 """
 from __future__ import annotations
 
@@ -53,6 +58,8 @@ CHECKPOINT_FORMAT = "dxrl-pg-checkpoint-v1"
 LOG_FORMAT = "dxrl-training-log-v1"
 _SCORE_COLUMNS = COLUMNS[:N.PG_LOG_IS_BEST]  # columns a score / convergence rule may read
 _HEADER_BYTES = C.sizeof(N.PgLogHeader)
+RANK_COLUMNS = N.PG_LOG_RANK_COLUMNS    # the named entries of a rank record (fit(merge_ranks=True))
+RANK_DOUBLES = N.PG_LOG_RANK_DOUBLES
 _MIN_CAP = 256
 VAL_COLUMNS = N.PG_VAL_COLUMNS
 VAL_COLS = N.PG_VAL_COLS
@@ -98,11 +105,19 @@ class TrainingLog:
     ``best_iteration``: the ``iteration`` value of the row keep-best chose (None: no row
     qualified).  ``convergence_iteration``: the ``iteration`` value of row
     ``converged_row - W + 1``, the first row of the first window whose mean exceeded the
-    threshold (reward_comparison.py:121-124), or None."""
+    threshold (reward_comparison.py:121-124), or None.
+
+    ``ranks``: f64 [rows][world][RANK_DOUBLES], the ranks' records every row was finished from
+    (``rank_column(name)`` -> [rows][world], names in RANK_COLUMNS), for a run logged with
+    ``fit(merge_ranks=True)``; None otherwise."""
 
     def __init__(self, table=None, header: Optional[Dict[str, Any]] = None, window: Optional[int] = None,
-                 settings: Optional[Dict[str, Any]] = None, _pending=None, validation: "Optional[ValidationLog]" = None):
+                 settings: Optional[Dict[str, Any]] = None, _pending=None, validation: "Optional[ValidationLog]" = None,
+                 ranks=None):
         self._pending = _pending
+        self._ranks = None if ranks is None else np.array(ranks, dtype=np.float64)
+        if self._ranks is not None and (self._ranks.ndim != 3 or self._ranks.shape[2] != RANK_DOUBLES):
+            raise ValueError(f"ranks must be [rows][world][{RANK_DOUBLES}], got shape {self._ranks.shape}")
         self._table = None if table is None else np.array(table, dtype=np.float64).reshape(-1, COLS)
         self._header = dict(header) if header is not None else None
         self.window = window
@@ -112,10 +127,12 @@ class TrainingLog:
     # -- lazy fill (fit enqueued the copy; the first read waits for it)
     def _resolve(self):
         if self._pending is not None:
-            event, host_table, host_header, rows = self._pending
+            event, host_table, host_header, rows, host_ranks = self._pending
             event.synchronize()
             self._table = host_table[:rows].numpy().copy()
             self._header = header_dict(host_header.numpy())
+            if host_ranks is not None:
+                self._ranks = host_ranks[:rows].numpy().copy()
             self._pending = None
 
     @property
@@ -127,6 +144,20 @@ class TrainingLog:
     def header(self) -> Dict[str, Any]:
         self._resolve()
         return self._header
+
+    @property
+    def ranks(self) -> Optional[np.ndarray]:
+        """f64 [rows][world][RANK_DOUBLES], or None for a run logged without merge_ranks."""
+        self._resolve()
+        return self._ranks
+
+    def rank_column(self, name: str) -> np.ndarray:
+        """[rows][world]: one entry of the ranks' records."""
+        if self.ranks is None:
+            raise ValueError("this log has no per-rank records (fit(..., merge_ranks=True))")
+        if name not in RANK_COLUMNS:
+            raise ValueError(f"a rank column is one of {list(RANK_COLUMNS)}, got {name!r}")
+        return self.ranks[:, :, RANK_COLUMNS.index(name)]
 
     @property
     def columns(self) -> Dict[str, np.ndarray]:
@@ -186,6 +217,9 @@ class TrainingLog:
                "rows": [[_enc(x) for x in row[:len(COLUMNS)]] for row in self.table.tolist()]}
         if self.validation is not None:  # a log without validation serialises as it always did
             out["validation"] = self.validation.to_dict()
+        if self.ranks is not None:  # likewise: a run without merge_ranks serialises as it always did
+            out["rank_columns"] = list(RANK_COLUMNS)
+            out["ranks"] = [[[_enc(x) for x in rec] for rec in row] for row in self.ranks.tolist()]
         return out
 
     @classmethod
@@ -196,8 +230,14 @@ class TrainingLog:
         for r, row in enumerate(d["rows"]):
             table[r, :len(COLUMNS)] = [_dec(x) for x in row]
         val = ValidationLog.from_dict(d["validation"]) if d.get("validation") is not None else None
+        ranks = None
+        if d.get("ranks") is not None:  # absent in runs without merge_ranks and in older files
+            if list(d.get("rank_columns", [])) != list(RANK_COLUMNS):
+                raise ValueError("not a training log with this build's rank columns")
+            ranks = np.array([[[_dec(x) for x in rec] for rec in row] for row in d["ranks"]], dtype=np.float64)
+            ranks = ranks.reshape(len(d["rows"]), -1, RANK_DOUBLES)
         return cls(table, {k: _dec(v) for k, v in d["header"].items()}, d.get("window"), d.get("settings"),
-                   validation=val)
+                   validation=val, ranks=ranks)
 
     def save(self, path):
         with open(path, "w") as f:
@@ -953,7 +993,26 @@ class _RunState:
         self.event = torch.cuda.Event()
         self.last_log = None  # weak reference to the last TrainingLog handed out
         self.val: Optional[_ValState] = None  # the validation tables (fit(validation=plan))
+        # fit(merge_ranks=True): this rank's record, the gathered records and the per-rank log
+        self.merged = False
+        self.record = self.records_all = self.rank_log = self.host_rank_log = None
         self.reserve(tr, cap)
+
+    def merge_ranks(self, tr):
+        """Make this run a rank-merged one (before its first row)."""
+        if self.merged:
+            return
+        self.merged = True
+        self.record = torch.zeros(RANK_DOUBLES, dtype=torch.float64, device=tr.dev)
+        self.records_all = torch.zeros(tr.world, RANK_DOUBLES, dtype=torch.float64, device=tr.dev)
+        self._rank_tables(tr, self.cap)
+
+    def _rank_tables(self, tr, cap: int):
+        rank_log = torch.zeros(cap, tr.world, RANK_DOUBLES, dtype=torch.float64, device=tr.dev)
+        if self.rank_log is not None and self.rows:
+            rank_log[:self.rows].copy_(self.rank_log[:self.rows])
+        self.rank_log = rank_log
+        self.host_rank_log = torch.zeros(cap, tr.world, RANK_DOUBLES, dtype=torch.float64).pin_memory()
 
     def reserve(self, tr, cap: int):
         """Room for `cap` rows: the table is allocated once per run and only regrown (device
@@ -966,6 +1025,8 @@ class _RunState:
             table[:self.rows].copy_(self.table[:self.rows])
         self.table, self.cap = table, cap
         self.host_table = torch.zeros(cap, COLS, dtype=torch.float64).pin_memory()
+        if self.merged:
+            self._rank_tables(tr, cap)
 
 
 def run_state(tr, cap: int = 0) -> _RunState:
@@ -978,12 +1039,14 @@ def run_state(tr, cap: int = 0) -> _RunState:
 
 
 def log_iteration(tr, st: _RunState, score_col: int, min_episodes: int, conv_col: int, window: int,
-                  threshold: float):
-    """One dxrl_pg_log_row call for the iteration that just ran (enqueued, no sync)."""
+                  threshold: float, merge_ranks: bool = False):
+    """One dxrl_pg_log_row call for the iteration that just ran (enqueued, no sync).  With
+    merge_ranks: dxrl_pg_log_rank_pack, one all-gather of the ranks' records on the compute
+    stream, and dxrl_pg_log_row_world on the gathered records."""
     p = N.ptr
     a = N.PgLogArgs()
     a.num_envs, a.horizon, a.row, a.cap = tr.n, tr.T, st.rows, st.cap
-    st.env_steps += tr.M
+    st.env_steps += tr.global_M if merge_ranks else tr.M
     a.iteration, a.env_steps = tr.iteration_index - 1, st.env_steps
     loss = tr.fused_loss if tr.cfg.fused else tr.loss_partial
     a.loss_blocks, a.loss_rows = loss.shape[0], (tr._loss_rows if tr.cfg.fused else tr.M)
@@ -994,14 +1057,22 @@ def log_iteration(tr, st: _RunState, score_col: int, min_episodes: int, conv_col
     a.stats, a.loss_partial, a.gnorm2 = p(tr.stats), p(loss), p(tr.gnorm2)
     a.params, a.best_params = p(tr.params), p(st.best_params)
     a.partial, a.log, a.header = p(st.partial), p(st.table), p(st.header)
-    N.call("dxrl_pg_log_row", tr.dev.index, C.byref(a), tr._s())
+    if merge_ranks:
+        from .distributed import all_gather_into_
+        with torch.cuda.device(tr.dev):
+            N.call("dxrl_pg_log_rank_pack", tr.dev.index, C.byref(a), p(st.record), tr._s())
+            all_gather_into_(st.records_all, st.record, tr.world, tr.pg if tr.collective else None)
+            N.call("dxrl_pg_log_row_world", tr.dev.index, C.byref(a), p(st.records_all), tr.world, p(st.rank_log),
+                   tr._s())
+    else:
+        N.call("dxrl_pg_log_row", tr.dev.index, C.byref(a), tr._s())
     st.rows += 1
 
 
 def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episodes: int = 1, converge=None,
         stop_on_converge: bool = False, poll_every: int = 0, validation: Optional[ValidationPlan] = None,
         validate_every: int = 1, val_keep_best: Optional[str] = "success_rate", min_delta: float = 0.0,
-        patience: int = 0, stop_on_patience: bool = False) -> TrainingLog:
+        patience: int = 0, stop_on_patience: bool = False, merge_ranks: bool = False) -> TrainingLog:
     """Run `iterations` training iterations, logging each on the device.
 
     keep_best: the score column ("mean_return", "success_rate", any column before is_best, or
@@ -1030,10 +1101,23 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
     built with common_random_numbers=True also logs ``paired`` / ``object_lost``
     (``dxrl_pg_val_paired_row``); keep-best and patience do not read them.  A plan built with
     failure_modes=True also logs ``failure_modes`` / ``failure_levels`` / ``failure_transitions``
-    (``dxrl_pg_val_failure_row``); keep-best and patience do not read those either."""
-    if tr.collective:
-        raise ValueError("fit() runs on one rank: a collective trainer (world > 1 or a process group) would need "
-                         "the ranks' log sums merged between the reduce and the finish stage, which is not built")
+    (``dxrl_pg_val_failure_row``); keep-best and patience do not read those either.
+
+    merge_ranks: the run of a sharded (collective) trainer.  Every rank reduces its own tape to a
+    record (``dxrl_pg_log_rank_pack``), the records are all-gathered -- one collective per logged
+    iteration, on the compute stream -- and every rank finishes the row from the same gathered
+    bytes (``dxrl_pg_log_row_world``), over the global sample count; env_steps advances by the
+    global sample count.  Tables, headers, keep-best decisions and best parameters are therefore
+    bit-identical on all ranks, so the polls of stop_on_converge / stop_on_patience decide the same
+    on every rank and need no further collective: all ranks must call fit with the same arguments.
+    Every rank runs the whole validation plan against its own (identical) weights.
+    ``log.ranks`` keeps the ranks' records of every row.  On a trainer without a process group it
+    takes the same path at world 1 with no collective and writes dxrl_pg_log_row's bytes.  A run
+    is merged or not from its first row on."""
+    if tr.collective and not merge_ranks:
+        raise ValueError("fit() runs on one rank: on a collective trainer (world > 1 or a process group) pass "
+                         "merge_ranks=True, which merges the ranks' log sums on the device between the reduce and "
+                         "the finish stage")
     iterations = int(iterations)
     if iterations < 0 or int(poll_every) < 0:
         raise ValueError("iterations and poll_every must be >= 0")
@@ -1055,6 +1139,12 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
     if stop_on_patience and (validation is None or patience < 1):
         raise ValueError("stop_on_patience needs validation=plan and patience >= 1")
     st = run_state(tr)
+    merge_ranks = bool(merge_ranks)
+    if st.rows and st.merged != merge_ranks:
+        raise ValueError(f"this run's {st.rows} rows were logged with merge_ranks={st.merged}: a run keeps the "
+                         "setting of its first row")
+    if merge_ranks:
+        st.merge_ranks(tr)
     val = val_state(tr, st, validation) if validation is not None else None
     st.reserve(tr, st.rows + iterations)
     if converge is not None:
@@ -1072,7 +1162,7 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
 
     for k in range(iterations):
         tr.iteration()
-        log_iteration(tr, st, score_col, min_episodes, conv_col, window, threshold)
+        log_iteration(tr, st, score_col, min_episodes, conv_col, window, threshold, merge_ranks)
         validated = val is not None and (st.rows % every == 0 or k == iterations - 1)
         if validated:
             validate()
@@ -1096,10 +1186,13 @@ def training_log(tr) -> TrainingLog:
         last._resolve()  # an earlier log still waiting for its copy takes it before the staging is reused
     if st.rows:
         st.host_table[:st.rows].copy_(st.table[:st.rows], non_blocking=True)
+    if st.merged and st.rows:
+        st.host_rank_log[:st.rows].copy_(st.rank_log[:st.rows], non_blocking=True)
     st.host_header.copy_(st.header, non_blocking=True)
     st.event.record(torch.cuda.current_stream(tr.dev))
     log = TrainingLog(window=st.window, settings=st.settings,
-                      _pending=(st.event, st.host_table, st.host_header, st.rows), validation=validation_log(tr))
+                      _pending=(st.event, st.host_table, st.host_header, st.rows,
+                                st.host_rank_log if st.merged else None), validation=validation_log(tr))
     st.last_log = weakref.ref(log)
     return log
 
@@ -1156,7 +1249,16 @@ def read_checkpoint(path):
         return {k: z[k] for k in z.files if k != "meta"}, meta
 
 
+def _rank_of(tr) -> int:
+    if not tr.collective:
+        return 0
+    import torch.distributed as dist
+    return dist.get_rank(tr.pg) if tr.pg is not None else dist.get_rank()
+
+
 def save_checkpoint(tr, path):
+    """This trainer's checkpoint; on a collective trainer this rank's file (ranks differ in env slab,
+    running returns and global_env_offset), with the world size and the rank in its JSON part."""
     env = tr.env
     st = getattr(tr, "_run", None)
     torch.cuda.synchronize(tr.dev)
@@ -1176,6 +1278,9 @@ def save_checkpoint(tr, path):
         arrays.update(log_table=host(st.table[:st.rows]), log_header=host(st.header),
                       best_params=host(st.best_params))
         meta["log"] = {"rows": st.rows, "env_steps": st.env_steps, "window": st.window, "settings": st.settings}
+        if st.merged:  # optional entries: a run without merge_ranks writes the file it always did
+            arrays["log_ranks"] = host(st.rank_log[:st.rows])
+            meta["log"]["merge_ranks"] = True
         if st.val is not None:  # optional entries: a run never validated writes the file it always did
             v = st.val
             arrays.update(validation_arrays(host(v.table[:v.rows]), host(v.header), host(v.best_params),
@@ -1187,6 +1292,8 @@ def save_checkpoint(tr, path):
                                             failure={name: host(getattr(v, name)[:v.rows]) for name in
                                                      v.optional_tables() if name.startswith("failure_")}))
             meta["validation"] = validation_meta(st.val.rows, st.val.fingerprint, st.val.object_names, st.val.settings)
+    if tr.collective:  # likewise optional: a one-rank trainer writes the file it always did
+        meta["world"], meta["rank"] = int(tr.world), _rank_of(tr)
     write_checkpoint(path, arrays, meta)
 
 
@@ -1231,13 +1338,19 @@ def validation_log_of_checkpoint(arrays: Dict[str, np.ndarray], meta: Dict[str, 
                          failure_transitions=arrays["val_failure_transitions"] if failures and crn else None)
 
 
-def load_checkpoint(cls, path, env):
+def load_checkpoint(cls, path, env, process_group=None, world_size: int = 1):
     """A trainer on `env` continuing the checkpointed run.  `env` must have been built with the
     checkpoint's EnvConfig (ValueError otherwise); its state, curriculum table and episode
-    limit are overwritten with the checkpoint's."""
+    limit are overwritten with the checkpoint's.  process_group / world_size: the collective
+    trainer of a sharded run, each rank from its own file (the env's global_env_offset is part of
+    the fingerprint); ValueError when the checkpoint was written at another world size."""
     from .experiments import CurriculumConfig, scheduler_from_state
     from .trainer import TrainerConfig
     arrays, meta = read_checkpoint(path)
+    if int(meta.get("world", 1)) != int(world_size):  # absent: a one-rank trainer, or an older file
+        raise ValueError(f"{path}: the checkpoint was written by rank {meta.get('rank', 0)} of a run over "
+                         f"{meta.get('world', 1)} ranks, and world_size is {world_size}: a sharded run resumes at "
+                         "the world size it was saved at")
     want, have = meta["env"], env_fingerprint(env)
     if want != have:
         diff = sorted(k for k in set(want) | set(have) if want.get(k) != have.get(k))
@@ -1245,7 +1358,9 @@ def load_checkpoint(cls, path, env):
                          f"{', '.join(diff)})")
     cfg = dict(meta["trainer_config"])
     cfg["betas"] = tuple(cfg["betas"])
-    tr = cls(env, TrainerConfig(**cfg))
+    tr = cls(env, TrainerConfig(**cfg), process_group=process_group, world_size=world_size)
+    if tr.collective and int(meta.get("rank", 0)) != _rank_of(tr):
+        raise ValueError(f"{path}: the checkpoint of rank {meta.get('rank', 0)}, loaded on rank {_rank_of(tr)}")
     env.max_episode_steps = int(meta["max_episode_steps"])
     tr.max_steps = tr.cfg.max_steps or env.max_episode_steps
     if meta["scheduler"] is not None:
@@ -1270,6 +1385,10 @@ def load_checkpoint(cls, path, env):
             put(st.table[:st.rows], "log_table")
         put(st.header, "log_header")
         put(st.best_params, "best_params")
+        if lg.get("merge_ranks"):  # absent in runs without merge_ranks and in older files
+            st.merge_ranks(tr)
+            if st.rows:
+                put(st.rank_log[:st.rows], "log_ranks")
         v = meta.get("validation")  # absent in checkpoints written before validation existed
         if v is not None:
             val = st.val = _ValState(tr, v["fingerprint"], v["object_names"], int(v["rows"]))

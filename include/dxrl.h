@@ -1157,6 +1157,67 @@ int dxrl_pg_log_partial_doubles(int64_t num_envs, int64_t horizon, int64_t* out)
 int dxrl_pg_log_row(int32_t device, const dxrl_pg_log_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * The training log of a sharded trainer (csrc/dxrl_pg_log.hip): dxrl_pg_log_row split where the
+ * ranks must meet.  Per logged iteration every rank calls dxrl_pg_log_rank_pack on its own tape,
+ * all-gathers the records in rank order (the caller's collective, on the same stream) and calls
+ * dxrl_pg_log_row_world on the gathered records; since every rank finishes from the same bytes,
+ * table, header and best_params are identical on all ranks.
+ *
+ * dxrl_pg_log_rank_pack reduces the rank's num_envs x horizon samples, episode counters and
+ * loss_partial blocks into record[DXRL_PG_LOG_RANK_DOUBLES] (enum dxrl_pg_log_rank_col), in the
+ * reduction order of dxrl_pg_log_row.  It writes neither log nor header nor best_params.
+ *   samples                    the rank's sample count, num_envs * horizon
+ *   reward_sum, value_sum      sums of rew and of values[m], m < M
+ *   done_count                 non-zero done bytes
+ *   target_mean, target_m2     mean and sum of squared deviations of ret (count: samples)
+ *   residual_mean, residual_m2 the same of (double)ret[m] - (double)values[m]
+ *   episodes, length_sum,      sums of ep_count / ep_sum_length / ep_successes / ep_sum_return
+ *   successes, return_sum
+ *   policy_loss_sum, value_se_sum, clip_sum, kl_sum
+ *                              the four columns of loss_partial summed over loss_blocks
+ *   loss_rows                  args->loss_rows
+ * Entries from DXRL_PG_LOG_RANK_NAMED up to DXRL_PG_LOG_RANK_DOUBLES are written as 0.
+ *
+ * dxrl_pg_log_row_world merges records[world][DXRL_PG_LOG_RANK_DOUBLES] in rank order (sums: f64
+ * additions; the two triples: Chan's update) and writes row `row` as dxrl_pg_log_row does, with
+ * every per-sample column over the sum of the records' samples and the loss columns over the sum
+ * of their loss_rows -- shards need not be equal.  adv_mean, adv_std and grad_norm come from
+ * stats and gnorm2 (global already on a sharded trainer); iteration and env_steps from args
+ * (env_steps: the caller's global count).  Keep-best, convergence, the header and the conditional
+ * copy of params are dxrl_pg_log_row's.  rank_log (nullable): f64 [cap][world]
+ * [DXRL_PG_LOG_RANK_DOUBLES]; row `row` receives the gathered records.  With world == 1, pack
+ * followed by row_world writes the bytes dxrl_pg_log_row writes.  The sample inputs of args are
+ * not read by row_world but are checked as dxrl_pg_log_row checks them.
+ * DXRL_E_INVALID before any launch: null record / records, world < 1, and everything
+ * dxrl_pg_log_row refuses.
+ * ------------------------------------------------------------------------ */
+#define DXRL_PG_LOG_RANK_DOUBLES 20
+enum dxrl_pg_log_rank_col {
+    DXRL_PG_LOG_RANK_SAMPLES = 0,
+    DXRL_PG_LOG_RANK_REWARD_SUM,
+    DXRL_PG_LOG_RANK_VALUE_SUM,
+    DXRL_PG_LOG_RANK_DONE_COUNT,
+    DXRL_PG_LOG_RANK_TARGET_MEAN,
+    DXRL_PG_LOG_RANK_TARGET_M2,
+    DXRL_PG_LOG_RANK_RESIDUAL_MEAN,
+    DXRL_PG_LOG_RANK_RESIDUAL_M2,
+    DXRL_PG_LOG_RANK_EPISODES,
+    DXRL_PG_LOG_RANK_LENGTH_SUM,
+    DXRL_PG_LOG_RANK_SUCCESSES,
+    DXRL_PG_LOG_RANK_RETURN_SUM,
+    DXRL_PG_LOG_RANK_POLICY_LOSS_SUM,
+    DXRL_PG_LOG_RANK_VALUE_SE_SUM,
+    DXRL_PG_LOG_RANK_CLIP_SUM,
+    DXRL_PG_LOG_RANK_KL_SUM,
+    DXRL_PG_LOG_RANK_LOSS_ROWS,
+    DXRL_PG_LOG_RANK_NAMED /* 17 named entries, padded to DXRL_PG_LOG_RANK_DOUBLES (160 bytes) */
+};
+
+int dxrl_pg_log_rank_pack(int32_t device, const dxrl_pg_log_args* args, double* record, void* stream);
+int dxrl_pg_log_row_world(int32_t device, const dxrl_pg_log_args* args, const double* records, int32_t world,
+                          double* rank_log, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Held-out validation row of a training run (csrc/dxrl_pg_val.hip).  One call per validation,
  * enqueued behind dxrl_evaluate_mlp on the same stream: it reduces the episode records of an
  * object-major evaluation (G objects x K episodes, E = G K, the record of object o, episode k

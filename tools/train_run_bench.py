@@ -7,8 +7,14 @@ Three arms on one trainer, alternated over repeats, each timed with device event
                                                                (the only way to a curve before fit)
 Prints one JSON line: ms per iteration per arm (median, min, max over repeats).
 
+--sharded measures the rank-merged log instead: a world-1 RCCL process group is created before any
+GPU work (as bench.py --dist does), the trainer is collective, and two arms alternate:
+  a  the plain iteration() loop on the collective trainer
+  d  fit(merge_ranks=True)          (rank record, one all-gather over RCCL, the row from the records)
+
     python tools/train_run_bench.py [--iters 30] [--repeats 5] [--out FILE]
-    python tools/train_run_bench.py --profile   # a short fit for rocprofv3 --kernel-trace --stats
+    python tools/train_run_bench.py --sharded [--repeats 7] [--out FILE]
+    python tools/train_run_bench.py [--sharded] --profile   # a short fit for rocprofv3 --kernel-trace --stats
 """
 import argparse
 import json
@@ -29,13 +35,38 @@ def main():
     p.add_argument("--horizon", type=int, default=200)
     p.add_argument("--out", default=None)
     p.add_argument("--profile", action="store_true")
+    p.add_argument("--sharded", action="store_true", help="a collective trainer on a world-1 RCCL group")
     a = p.parse_args()
     import torch
     from dexterous_rl_manipulation_amd import workloads
     dev = torch.device("cuda", 0)
-    env, tr = workloads.build_pg_workload("easy", dev, envs=a.envs, horizon=a.horizon)
+    group = None
+    if a.sharded:  # before any GPU work
+        import datetime
+        import socket
+        import torch.distributed as dist
+        s = socket.socket()
+        s.bind(("127.0.0.1", 0))
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", str(s.getsockname()[1]))
+        s.close()
+        torch.cuda.set_device(dev)
+        dist.init_process_group("nccl", device_id=dev, rank=0, world_size=1, timeout=datetime.timedelta(seconds=120))
+        group = dist.group.WORLD
+    env, tr = workloads.build_pg_workload("easy", dev, envs=a.envs, horizon=a.horizon, process_group=group)
+    try:
+        measure(a, tr, dev)
+    finally:
+        if group is not None:
+            torch.cuda.synchronize()
+            dist.destroy_process_group()
+
+
+def measure(a, tr, dev):
+    import torch
+    merge = dict(merge_ranks=True) if a.sharded else {}
     if a.profile:
-        tr.fit(a.iters)
+        tr.fit(a.iters, **merge)
         torch.cuda.synchronize()
         return
 
@@ -52,8 +83,13 @@ def main():
             tr.episode_stats()
             tr.loss_stats()
 
+    def fit_merged():
+        tr.fit(a.iters, poll_every=0, merge_ranks=True)
+
     arms = {"a_iteration": plain, "b_fit": fit, "c_iteration_host_stats": host_curve}
-    tr.fit(a.warmup)
+    if a.sharded:
+        arms = {"a_iteration": plain, "d_fit_merge_ranks": fit_merged}
+    tr.fit(a.warmup, **merge)
     for f in arms.values():
         f()
     torch.cuda.synchronize()
@@ -67,10 +103,11 @@ def main():
             e1.synchronize()
             ms[name].append(e0.elapsed_time(e1) / a.iters)
     res = {"envs": a.envs, "horizon": a.horizon, "iters": a.iters, "repeats": a.repeats,
-           "device": torch.cuda.get_device_name(dev)}
+           "device": torch.cuda.get_device_name(dev), "sharded": bool(a.sharded)}
     for name, v in ms.items():
         res[name] = {"ms_per_iteration_median": statistics.median(v), "min": min(v), "max": max(v), "all": v}
-    res["b_minus_a_ms"] = res["b_fit"]["ms_per_iteration_median"] - res["a_iteration"]["ms_per_iteration_median"]
+    other = "d_fit_merge_ranks" if a.sharded else "b_fit"
+    res[other[:1] + "_minus_a_ms"] = res[other]["ms_per_iteration_median"] - res["a_iteration"]["ms_per_iteration_median"]
     res["a_spread_ms"] = res["a_iteration"]["max"] - res["a_iteration"]["min"]
     line = json.dumps(res)
     print(line)
