@@ -14,6 +14,8 @@ Drop-in surfaces (same names as the reference modules):
   robustness_analysis.{analyze_robustness_results,plot_robustness_results,print_robustness_report,
                        run_robustness_study},
   reward_comparison.{run_training_comparison,compare_rewards}
+Studies of the PG trainer (arms x seeds of fit(), reduced on the device): training_study.run_training_study,
+  ablation.run_pg_component_study, curriculum_ablation.run_pg_curriculum_study, `python -m ...pg_ablation`.
 Batched device API: envs.VecEnv, policies.VecSimpleLearner, training.SimpleLearnerRollout,
 trainer.PGTrainer (iteration, fit, checkpoints; training_run.TrainingLog; `python -m ...train`).
 The compute runs in libdxrl.so (HIP, gfx950; C ABI in include/dxrl.h).  No CPU fallback.
@@ -28,6 +30,7 @@ def __getattr__(name):
     import importlib
     if name in ("envs", "policies", "training", "evaluation", "build", "_native", "trainer",
                 "evaluator", "metrics", "curriculum_ablation", "seed_variance", "failure_analysis", "failure_statistics",
-                "robustness_analysis", "training_run", "workloads", "reward_comparison"):
+                "robustness_analysis", "training_run", "workloads", "reward_comparison", "ablation",
+                "training_study", "pg_ablation"):
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -320,12 +320,38 @@ class PgValFailureArgs(C.Structure):
                                           "failure_modes", "failure_levels", "failure_transitions")]
 
 
+# dxrl_pg_runs_summarize: a set of runs' tables reduced to run rows, group tables and contrasts
+PG_RUNS_MAX_SPECS = 16  # DXRL_PG_RUNS_MAX_SPECS
+# enum dxrl_pg_runs_run_col: the columns of a run row, in table order
+PG_RUNS_RUN_COLUMNS = ("rows", "final_window_mean", "best", "best_row", "convergence_row", "x_at_convergence",
+                       "curve_mean", "nan_rows")
+PG_RUNS_RUN_COLS = len(PG_RUNS_RUN_COLUMNS)  # DXRL_PG_RUNS_RUN_COLS
+# enum dxrl_pg_runs_metric: the metrics of the group and contrast tables, in table order
+PG_RUNS_METRICS = ("final_window_mean", "best", "convergence_row", "x_at_convergence", "curve_mean")
+PG_RUNS_GROUP_COLUMNS = ("count", "mean", "std", "min", "max", "num_converged")  # DXRL_PG_RUNS_GROUP_COLS
+PG_RUNS_CONTRAST_COLUMNS = ("pairs", "mean", "std", "stderr", "t")              # DXRL_PG_RUNS_CONTRAST_COLS
+PG_RUNS_ST_RANGE, PG_RUNS_ST_ROWS, PG_RUNS_ST_CONTRAST = 1, 2, 4
+
+
+class PgRunsSpec(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("col", "x_col", "window", "final_window")] + [("threshold", C.c_double)]
+
+
+class PgRunsArgs(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("num_runs", "cap", "cols", "num_specs", "num_groups", "num_members",
+                                         "num_contrasts", "reserved")] + \
+               [("specs", C.POINTER(PgRunsSpec))] + \
+               [(k, C.c_void_p) for k in ("tables", "run_rows", "group_offsets", "group_runs", "contrast_weights",
+                                          "run_table", "group_table", "contrast_table", "status")]
+
+
 # the structs added after tests/test_native_abi.py fixed its list: (C name, mirror), sized against
 # include/dxrl.h by the tests of the layers that use them
 LATER_STRUCTS = (("dxrl_pg_log_args", PgLogArgs), ("dxrl_pg_log_header", PgLogHeader),
                  ("dxrl_pg_val_args", PgValArgs), ("dxrl_pg_val_header", PgValHeader),
                  ("dxrl_pg_val_levels_args", PgValLevelsArgs), ("dxrl_pg_val_paired_args", PgValPairedArgs),
-                 ("dxrl_pg_val_failure_args", PgValFailureArgs))
+                 ("dxrl_pg_val_failure_args", PgValFailureArgs), ("dxrl_pg_runs_spec", PgRunsSpec),
+                 ("dxrl_pg_runs_args", PgRunsArgs))
 
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
@@ -392,6 +418,7 @@ _SIGS = {
     "dxrl_pg_val_paired_row": (C.c_int, [_I32, C.POINTER(PgValPairedArgs), _P]),
     "dxrl_pg_val_failure_partial_doubles": (C.c_int, [_I32, _I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_val_failure_row": (C.c_int, [_I32, C.POINTER(PgValFailureArgs), _P]),
+    "dxrl_pg_runs_summarize": (C.c_int, [_I32, C.POINTER(PgRunsArgs), _P]),
     "dxrl_sched_scratch_bytes": (C.c_int, [_I32, _I32, _I64, _I32, C.POINTER(_I64)]),
     "dxrl_sched_scan": (C.c_int, [_I32, C.POINTER(SchedArgs), _P]),
     "dxrl_sched_pack_words": (C.c_int, [_I32, _I64, _I32, _I32, C.POINTER(_I64)]),

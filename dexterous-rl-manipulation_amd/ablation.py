@@ -23,6 +23,12 @@ dense and a sparse ``DeviceStudy`` on two streams write one lane table, and
 ``dxrl_study_summarize`` reduces it to ``compute_ablation_statistics``' dictionary on the device.
 There the scheduler moves whenever its rule says so (``success_rule="terminated"``, thresholds
 <= 0); ``train_many`` above keeps its restriction.
+
+``run_pg_component_study`` is the 2 x 2 on the learner this project is about: every (configuration,
+seed) is one ``PGTrainer.fit`` of the MLP actor-critic (``training_study.run_training_study``), a
+curriculum arm with ``study_scheduler`` attached, every run validated on the same held-out
+episodes, and ``dxrl_pg_runs_summarize`` reduces the runs' device tables to the same dictionary
+plus the effects paired by seed (``python -m dexterous_rl_manipulation_amd.pg_ablation``).
 """
 from __future__ import annotations
 
@@ -336,6 +342,85 @@ def run_component_study(num_episodes: int = 200, max_episode_steps: int = 200, s
     return (stats, out) if return_runs else stats
 
 
+# ------------------------------------------------------------------ the study on the policy-gradient trainer
+# the 2 x 2 as contrasts over the four arms (weights per arm; runs paired by seed): both main
+# effects, the interaction, and every arm against the baseline
+PG_COMPONENT_CONTRASTS = {
+    "curriculum_effect": {"baseline": 0.5, "no_dense_reward": 0.5, "no_curriculum": -0.5, "minimal": -0.5},
+    "dense_reward_effect": {"baseline": 0.5, "no_curriculum": 0.5, "no_dense_reward": -0.5, "minimal": -0.5},
+    "interaction": {"baseline": 1.0, "no_curriculum": -1.0, "no_dense_reward": -1.0, "minimal": 1.0},
+    "no_curriculum_vs_baseline": {"no_curriculum": 1.0, "baseline": -1.0},
+    "no_dense_reward_vs_baseline": {"no_dense_reward": 1.0, "baseline": -1.0},
+    "minimal_vs_baseline": {"minimal": 1.0, "baseline": -1.0},
+}
+
+
+def pg_component_arms(curriculum_scheduler_config=None):
+    """The four ``ABLATION_CONFIGS`` as arms of a ``training_study``: a curriculum arm trains under
+    ``study_scheduler(curriculum_scheduler_config)``, the others on the hard preset."""
+    from .training_study import Arm
+    return [Arm(nm, c, "dense" if d else "sparse", scheduler_config=curriculum_scheduler_config)
+            for nm, c, d in ABLATION_CONFIGS]
+
+
+def pg_study_specs(window: int = 10, threshold: float = 0.5, final_window: int = 10):
+    """The specs both slabs of a PG ablation are reduced with: the success rate (its final window
+    and its convergence, reported in env steps), the mean episode length and the mean return."""
+    from .training_study import Spec
+    return tuple(Spec(c, "env_steps", int(window), float(threshold), int(final_window))
+                 for c in ("success_rate", "mean_length", "mean_return"))
+
+
+def _none_if_nan(x: float):
+    return None if np.isnan(x) else float(x)
+
+
+def pg_statistics(result, effects: bool = True) -> Dict[str, Dict]:
+    """``compute_ablation_statistics``' dictionary from a ``StudyResult``'s group tables -- the
+    validation slab's when a validation ran, else the training slab's: ``final_success_rate`` is
+    the final-window mean of ``success_rate``, ``mean_episode_length`` the curve mean of
+    ``mean_length``, ``convergence_step`` the env steps at the convergence of ``success_rate`` over
+    the runs that converged.  With ``effects``, an ``"effects"`` entry holds, per contrast, the
+    mean, standard error and pair count of the paired final success rate."""
+    slab = result.yardstick
+    stats: Dict[str, Dict] = {}
+    for arm in result.arms:
+        fsr = slab.group(arm, "success_rate", "final_window_mean")
+        mel = slab.group(arm, "mean_length", "curve_mean")
+        conv = slab.group(arm, "success_rate", "x_at_convergence")
+        stats[arm] = {
+            "final_success_rate": {k: fsr[k] for k in ("mean", "std", "min", "max")},
+            "mean_episode_length": {k: mel[k] for k in ("mean", "std")},
+            "convergence_step": {"mean": _none_if_nan(conv["mean"]), "std": _none_if_nan(conv["std"]),
+                                 "num_converged": int(conv["count"])},
+        }
+    if effects:
+        stats["effects"] = {}
+        for name in slab.contrast_names:
+            c = slab.contrast(name, "success_rate", "final_window_mean")
+            stats["effects"][name] = {"mean": c["mean"], "stderr": c["stderr"], "pairs": int(c["pairs"])}
+    return stats
+
+
+def run_pg_component_study(iterations: int, seeds: Sequence[int] = (42, 123, 456), *, curriculum_scheduler_config=None,
+                           convergence_window: int = 10, convergence_threshold: float = 0.5, final_window: int = 10,
+                           return_study: bool = False, **study_kw):
+    """component_ablation.py:198-322 on the policy-gradient trainer: the four configurations x
+    seeds as ``training_study.run_training_study`` jobs (``study_kw`` goes there: num_envs,
+    horizon, max_steps, heldout_set, validate_every, val_episodes, device_summary, ...), reduced by
+    ``dxrl_pg_runs_summarize`` to ``compute_ablation_statistics``' dictionary plus ``"effects"``
+    (``pg_statistics``), which feeds ``print_ablation_report``.  ``return_study=True`` also returns
+    the ``StudyResult``."""
+    from .training_study import run_training_study
+    specs = pg_study_specs(convergence_window, convergence_threshold, final_window)
+    study_kw.setdefault("train_specs", specs)
+    study_kw.setdefault("val_specs", specs)
+    study_kw.setdefault("contrasts", PG_COMPONENT_CONTRASTS)
+    result = run_training_study(pg_component_arms(curriculum_scheduler_config), list(seeds), iterations, **study_kw)
+    stats = pg_statistics(result)
+    return (stats, result) if return_study else stats
+
+
 def main(argv: Optional[Sequence[str]] = None):
     """evaluation/run_component_ablation.py:24-102 on ``run_component_study`` (plots are not part of
     this build: the reference's warning line is printed in their place)."""
@@ -406,7 +491,7 @@ def print_ablation_report(all_results: Dict[str, List[TrainingResults]], stats: 
              f"  Final Success Rate: {base:.3f} +/- {stats[base_name]['final_success_rate']['std']:.3f}",
              "\n" + rule, "Component Contributions:", rule]
     for name, st in stats.items():
-        if name == base_name:
+        if name == base_name or name == "effects":  # "effects": pg_statistics' contrasts, not a configuration
             continue
         m, sd = st["final_success_rate"]["mean"], st["final_success_rate"]["std"]
         diff = m - base

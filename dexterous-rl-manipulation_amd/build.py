@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = ["dxrl_env.hip", "dxrl_rollout.hip", "dxrl_gemm.hip", "dxrl_pg.hip", "dxrl_pg_fused.hip", "dxrl_pg_rollout8.hip", "dxrl_eval.hip", "dxrl_eval_mlp.hip",
            "dxrl_sched.hip", "dxrl_eval_summary.hip", "dxrl_failure_summary.hip",
            "dxrl_robustness_summary.hip", "dxrl_study_summary.hip", "dxrl_pg_log.hip", "dxrl_pg_val.hip",
-           "dxrl_pg_val_levels.hip", "dxrl_pg_val_paired.hip", "dxrl_pg_val_failure.hip"]
+           "dxrl_pg_val_levels.hip", "dxrl_pg_val_paired.hip", "dxrl_pg_val_failure.hip", "dxrl_pg_runs.hip"]
 HEADERS = ["dxrl_device.h", "dxrl_internal.h", "dxrl_mfma.h", "dxrl_gemm.h", "dxrl_pg.h", "dxrl_pg_rollout.h",
            "dxrl_pg_mlp.h", "dxrl_eval.h", "dxrl_eval_row.h", "dxrl_hist_row.h", "dxrl_moments.h", "dxrl_pg_val_common.h",
            "dxrl_reduce.h", "dxrl_keep_best.h", "dxrl_metrics_groups.h", "dxrl_failure_rules.h"]

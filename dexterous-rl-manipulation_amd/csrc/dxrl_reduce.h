@@ -38,6 +38,23 @@ __device__ __forceinline__ int wave_max(int v) {
     }
     return v;
 }
+// the same over doubles that are not NaN (a lane without a value passes +inf / -inf)
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double b = __shfl_down(v, o, 64);
+        v = b < v ? b : v;
+    }
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double b = __shfl_down(v, o, 64);
+        v = b > v ? b : v;
+    }
+    return v;
+}
 
 // The flagged rows of [0, rows) listed in ascending order by one workgroup of NT threads: thread t
 // owns rows [t c, (t + 1) c), counts its flagged rows (first(r), called once per row), an inclusive

@@ -848,3 +848,61 @@ def run_ablation_study(num_episodes: int = 200, num_runs: int = 5, output_dir: s
     print(f"\nResults saved to {path}")
     print(bar)
     return results
+
+
+# ------------------------------------------------------------------ the study on the policy-gradient trainer
+PG_CURRICULUM_CONTRASTS = {"curriculum_effect": {"with_curriculum": 1.0, "without_curriculum": -1.0}}
+# aggregate key -> (spec column, metric) of the study's group tables
+_PG_AGGREGATES = {"convergence_step": ("success_rate", "x_at_convergence"),
+                  "final_success_rate": ("success_rate", "final_window_mean"),
+                  "best_success_rate": ("success_rate", "best"),
+                  "mean_success_rate": ("success_rate", "curve_mean"),
+                  "final_reward": ("mean_return", "final_window_mean"),
+                  "mean_reward": ("mean_return", "curve_mean"),
+                  "mean_episode_length": ("mean_length", "curve_mean")}
+
+
+def pg_aggregates(result) -> Dict:
+    """A ``training_study.StudyResult`` of the two arms as ``aggregate_metrics``-shaped
+    dictionaries (mean and std over the runs that have the metric, None when no run does; no
+    median: the device tables carry none) plus the effects paired by seed, from the validation
+    slab when a validation ran, else the training slab."""
+    slab = result.yardstick
+    out: Dict = {}
+    for arm in result.arms:
+        agg = {}
+        for key, (column, metric) in _PG_AGGREGATES.items():
+            g = slab.group(arm, column, metric)
+            agg[key] = {"mean": g["mean"], "std": g["std"]} if g["count"] > 0 else None
+        agg["num_converged"] = int(slab.group(arm, "success_rate", "x_at_convergence")["count"])
+        out[arm] = {"aggregated_metrics": agg}
+    out["effects"] = {}
+    for name in slab.contrast_names:
+        out["effects"][name] = {}
+        for key, (column, metric) in _PG_AGGREGATES.items():
+            c = slab.contrast(name, column, metric)
+            out["effects"][name][key] = ({"mean": c["mean"], "stderr": c["stderr"], "pairs": int(c["pairs"])}
+                                         if c["pairs"] > 0 else None)
+    return out
+
+
+def run_pg_curriculum_study(iterations: int, num_runs: int = 5, *, curriculum_scheduler_config=None,
+                            convergence_window: int = 10, convergence_threshold: float = 0.5, final_window: int = 10,
+                            return_study: bool = False, **study_kw):
+    """curriculum_ablation.py:206-357 on the policy-gradient trainer: ``num_runs`` runs (seeds 42 +
+    run) with ``ablation.study_scheduler`` attached and ``num_runs`` on the fixed hard config, both
+    on the dense reward, as ``training_study.run_training_study`` jobs (``study_kw`` goes there).
+    Returns ``pg_aggregates``' dictionary: ``with_curriculum`` / ``without_curriculum`` and the
+    paired ``effects``; with ``return_study`` also the ``StudyResult``."""
+    from .ablation import pg_study_specs
+    from .training_study import Arm, run_training_study
+    arms = [Arm("with_curriculum", True, "dense", scheduler_config=curriculum_scheduler_config),
+            Arm("without_curriculum", False, "dense")]
+    specs = pg_study_specs(convergence_window, convergence_threshold, final_window)
+    study_kw.setdefault("train_specs", specs)
+    study_kw.setdefault("val_specs", specs)
+    study_kw.setdefault("contrasts", PG_CURRICULUM_CONTRASTS)
+    result = run_training_study(arms, [42 + r for r in range(int(num_runs))], iterations, **study_kw)
+    out = pg_aggregates(result)
+    out["num_runs"], out["iterations"] = int(num_runs), int(iterations)
+    return (out, result) if return_study else out

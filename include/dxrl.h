@@ -1627,6 +1627,129 @@ int dxrl_pg_val_failure_partial_doubles(int32_t num_levels, int64_t num_objects,
                                         int64_t* out);
 int dxrl_pg_val_failure_row(int32_t device, const dxrl_pg_val_failure_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * A set of training runs reduced on the device (csrc/dxrl_pg_runs.hip): the layer above
+ * one fit().  The runs' device tables -- training logs (cols = DXRL_PG_LOG_COLS) or
+ * validation tables (cols = DXRL_PG_VAL_COLS), one call per slab -- lie in one slab
+ *   tables f64 [R][cap][cols],  run_rows i32 [R] (rows written of every run),
+ * and are reduced to per-run rows, per-group tables (CSR groups of runs, the semantics of
+ * dxrl_study_summarize: group g holds group_runs[group_offsets[g] .. group_offsets[g+1]),
+ * groups may overlap or be empty) and contrasts paired by member position.  At most three
+ * launches on the caller's stream (run pass; group pass when G > 0; contrast pass when
+ * Q > 0), no host synchronisation, no floating-point atomics: the same inputs give the
+ * same bytes on every call.
+ *
+ * A spec s is (col, x_col, window W, threshold, final_window FW): the column the
+ * statistics are taken of, the column reported at convergence, and dxrl_pg_log_row's
+ * convergence rule.  S specs per call (1 .. DXRL_PG_RUNS_MAX_SPECS), read on the host.
+ *
+ * Run pass, a wavefront per (run, spec), n = run_rows[r], v_i = tables[r][i][col]:
+ * run_table f64 [R][S][DXRL_PG_RUNS_RUN_COLS]:
+ *   0 n
+ *   1 final_window_mean: the left-to-right f64 sum of v_{n-k} .. v_{n-1}, k = min(FW, n),
+ *     divided by k; NaN if one of them is NaN or n = 0
+ *   2 best, 3 best_row: the maximum over the non-NaN rows, the first maximum wins;
+ *     NaN / -1 if there is none
+ *   4 convergence_row: dxrl_pg_log_row's rule -- the first row i >= W - 1 whose window mean
+ *     (v_{i-W+1} + .. + v_i, summed oldest first in f64, divided by W) is strictly above
+ *     threshold; a NaN in the window does not converge; -1 if no row does
+ *   5 x_at_convergence: tables[r][convergence_row][x_col], NaN if not converged
+ *   6 curve_mean: the sum of the non-NaN rows divided by their number (NaN if none).
+ *     SUMMATION ORDER: wave lane t adds rows t, t + 64, t + 128, .. in ascending order to
+ *     a partial that starts at 0.0 (a NaN row adds nothing); the 64 partials are added in
+ *     the fixed tree p[t] += p[t + o] for o = 32, 16, 8, 4, 2, 1
+ *   7 the number of NaN rows
+ *
+ * Group pass, a wavefront per (group, spec).  The five metrics of a run, in this order:
+ * DXRL_PG_RUNS_FINAL_WINDOW_MEAN (column 1), _BEST (2), _CONVERGENCE_ROW (4; a run that
+ * did not converge has no value), _X_AT_CONVERGENCE (5), _CURVE_MEAN (6).
+ * group_table f64 [G][S][5][DXRL_PG_RUNS_GROUP_COLS], per metric over the group's runs
+ * whose value is finite: 0 count, 1 mean, 2 population standard deviation (np.std), 3 min,
+ * 4 max (1 .. 4 NaN when count = 0), 5 the number of the group's runs that converged
+ * (column 4 >= 0; the same in all five rows).  ORDER: wave lane t takes members t, t + 64,
+ * .. of the group in ascending position as Welford steps into a (count, mean, M2) triple;
+ * the 64 triples are merged with Chan et al.'s update in the tree t[i] = merge(t[i],
+ * t[i + o]) for o = 32, .., 1; std = sqrt(M2 / count).
+ *
+ * Contrast pass, a wavefront per (contrast, spec): contrast_weights f64 [Q][G].  The
+ * groups with a non-zero weight in contrast q must have one member count m (else status
+ * bit 2 and the contrast's rows are NaN).  For position j < m,
+ *   d_j = sum over g, ascending, of w[q][g] * x[member j of g]     (w[q][g] != 0 only),
+ * the products added left to right to 0.0: member j is the same seed in every arm, so a
+ * pairwise difference is the weights (+1, -1), a main effect of a 2 x 2 (+-1/2) and the
+ * interaction (+1 -1 -1 +1).  contrast_table f64 [Q][S][5][DXRL_PG_RUNS_CONTRAST_COLS],
+ * per metric over the positions j whose every term is finite (an out-of-range member has
+ * no finite value): 0 pairs n, 1 mean of d, 2 sample standard deviation (ddof 1, NaN for
+ * n < 2), 3 standard error std / sqrt(n), 4 mean / standard error; 1 .. 4 are NaN when
+ * n = 0.  ORDER: as the group pass, over positions.
+ *
+ * status i32 [1] (zeroed on the stream by the call): bit 0 = a group offset or member was
+ * out of range (skipped: a group with bad offsets is an empty group; nothing is accessed
+ * out of bounds); bit 1 = run_rows[r] outside [0, cap] (the run is treated as empty);
+ * bit 2 = a contrast whose weighted groups differ in size, or one of which has bad offsets
+ * (its rows are NaN).
+ * DXRL_E_INVALID before any launch: null args or a null required pointer (tables,
+ * run_rows, specs, run_table, status; group_offsets and group_table when G > 0,
+ * group_runs when num_members > 0; contrast_weights and contrast_table when Q > 0);
+ * R, cap, cols or S < 1; S > DXRL_PG_RUNS_MAX_SPECS; col or x_col outside [0, cols);
+ * W or FW < 1; G, Q or num_members < 0; Q > 0 with G = 0.
+ * ------------------------------------------------------------------------ */
+#define DXRL_PG_RUNS_MAX_SPECS 16
+#define DXRL_PG_RUNS_RUN_COLS 8
+#define DXRL_PG_RUNS_METRICS 5
+#define DXRL_PG_RUNS_GROUP_COLS 6
+#define DXRL_PG_RUNS_CONTRAST_COLS 5
+enum dxrl_pg_runs_run_col {
+    DXRL_PG_RUNS_RUN_ROWS = 0,
+    DXRL_PG_RUNS_RUN_FINAL_WINDOW_MEAN,
+    DXRL_PG_RUNS_RUN_BEST,
+    DXRL_PG_RUNS_RUN_BEST_ROW,
+    DXRL_PG_RUNS_RUN_CONVERGENCE_ROW,
+    DXRL_PG_RUNS_RUN_X_AT_CONVERGENCE,
+    DXRL_PG_RUNS_RUN_CURVE_MEAN,
+    DXRL_PG_RUNS_RUN_NAN_ROWS
+};
+enum dxrl_pg_runs_metric {
+    DXRL_PG_RUNS_FINAL_WINDOW_MEAN = 0,
+    DXRL_PG_RUNS_BEST,
+    DXRL_PG_RUNS_CONVERGENCE_ROW,
+    DXRL_PG_RUNS_X_AT_CONVERGENCE,
+    DXRL_PG_RUNS_CURVE_MEAN
+};
+
+typedef struct dxrl_pg_runs_spec {
+    int32_t col;                     /* the column the statistics are taken of              */
+    int32_t x_col;                   /* the column reported at the convergence row          */
+    int32_t window;                  /* W >= 1                                               */
+    int32_t final_window;            /* FW >= 1                                              */
+    double  threshold;
+} dxrl_pg_runs_spec;
+
+typedef struct dxrl_pg_runs_args {
+    int32_t num_runs;                /* R                                                    */
+    int32_t cap;                     /* rows of every run's table in the slab                */
+    int32_t cols;                    /* f64 columns of a row                                 */
+    int32_t num_specs;               /* S, 1 .. DXRL_PG_RUNS_MAX_SPECS                       */
+    int32_t num_groups;              /* G (0 = no group pass)                                */
+    int32_t num_members;             /* entries of group_runs (bounds check)                 */
+    int32_t num_contrasts;           /* Q (0 = no contrast pass)                             */
+    int32_t reserved;
+    const dxrl_pg_runs_spec* specs;  /* HOST [S]                                             */
+    /* device inputs */
+    const double*  tables;           /* f64 [R][cap][cols]                                   */
+    const int32_t* run_rows;         /* i32 [R]                                              */
+    const int32_t* group_offsets;    /* i32 [G + 1] CSR offsets into group_runs              */
+    const int32_t* group_runs;       /* i32 [num_members] runs (slab rows)                   */
+    const double*  contrast_weights; /* f64 [Q][G]                                           */
+    /* device outputs */
+    double*  run_table;              /* f64 [R][S][8]                                        */
+    double*  group_table;            /* f64 [G][S][5][6]                                     */
+    double*  contrast_table;         /* f64 [Q][S][5][5]                                     */
+    int32_t* status;                 /* i32 [1]                                              */
+} dxrl_pg_runs_args;
+
+int dxrl_pg_runs_summarize(int32_t device, const dxrl_pg_runs_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
