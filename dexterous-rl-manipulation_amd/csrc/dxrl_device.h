@@ -23,7 +23,6 @@ constexpr int kReset = kD + DXRL_RESET_EXTRA;
 // rounded to f32 (NEP 50 weak scalar), not the decimal rounded to f32.
 constexpr float kC09 = (float)0.9, kC01 = (float)0.1, kDt = (float)0.01;
 constexpr double kGz = -9.81 * 0.01;  // ME:211-212 gravity (f64)
-constexpr double kLo[3] = {-0.2, -0.2, 0.0}, kHi[3] = {0.2, 0.2, 0.3};  // ME:119
 
 // flag word bits
 constexpr uint32_t kPrevShift = 8, kHasPrev = 1u << 16, kOpIsF32 = 1u << 17, kHasObject = 1u << 18,
@@ -198,65 +197,130 @@ __device__ __forceinline__ float count_over_f_f32(uint32_t k) {
 static_assert(kF == 5, "div_f: the finger count's reciprocal constant");
 __device__ __forceinline__ float div_f(float x) { return (float)((double)x * 0.2); }
 
-// RS:101-187 dense terms + weighted total (RS:84-89); updates prev contacts.
-__device__ __forceinline__ double dense_reward(Env& e, uint32_t c, double dmin, const Weights& w, double comp[4]) {
-    const double dist = exp(-5.0 * dmin);                 // RS:111-116
-    const int n = __popc(c);
-    const double con = count_over_f_f64((uint32_t)n);     // RS:128-134 (n / 5)
-    float sum = 0.0f;                                     // RS:147-162
+// ---------------------------------------------------------------- the env's formulas
+// Each of the reference's formulas is stated once here.  The scalar form below (env_step,
+// dense_reward, env_reset: one lane per env), the lane-split rollout kernels (k_pg_rollout_ws,
+// k_pg_rollout_e8) and the evaluation row program (EpisodeRow) all call these; a caller decides
+// only which lanes compute, which lanes commit and in which phase.
+
+// ME:199-207 one joint: the clipped action into the velocity, the velocity into the position
+__device__ __forceinline__ void joint_step(float& jp, float& jv, float a) {
+    const float ak = clipf(a, -1.0f, 1.0f);           // ME:199
+    jv = kC09 * jv + kC01 * ak;                       // ME:203 (f32, no FMA)
+    jp = clipf(jp + jv * kDt, -1.0f, 1.0f);           // ME:204-207
+}
+
+// ME:212-235 one axis of the object: damping, gravity, position increment, wall clip, wall stop.
+// (op, ov): the axis' position and velocity; flags: kOpIsF32 / kFricF64 of the env (the caller
+// clears kOpIsF32 once the step's axes are done).  Workspace limits ME:119, gravity ME:211-212.
+struct AxisState {
+    double q;
+    float v;
+};
+__device__ __forceinline__ AxisState object_axis_step(double op, float ov, int axis, double fric, uint32_t flags) {
+    const double gz = axis == 2 ? kGz : 0.0, lo = axis == 2 ? 0.0 : -0.2, hi = axis == 2 ? 0.3 : 0.2;
+    const double damp = 1.0 - (fric * 0.1 * 0.01);  // ME:215
+    const float dampf = (float)damp;
+    const bool op32 = (flags & kOpIsF32) != 0, fric_f64 = (flags & kFricF64) != 0;
+    float v = fric_f64 ? (float)((double)ov * damp) : ov * dampf;            // ME:216 (NEP 50)
+    v = (float)((double)v + gz);                                             // ME:219 f32 += f64
+    const float inc = v * kDt;                                               // ME:222
+    double q = op32 ? (double)((float)op + inc) : op + (double)inc;
+    q = clipd(q, lo, hi);                                                    // ME:225-229 -> f64
+    if ((q <= lo && v < 0.0f) || (q >= hi && v > 0.0f)) v = 0.0f;            // ME:232-235
+    return AxisState{q, v};
+}
+
+// Flag-word transitions.  Previous contacts as the stability term takes them: the mask of the
+// last dense step, or kNoPrev (prev_contacts = None, RS:45-48).
+constexpr uint32_t kNoPrev = 0x100u;
+__device__ __forceinline__ uint32_t prev_contacts(uint32_t flags) {
+    return (flags & kHasPrev) ? ((flags >> kPrevShift) & 0xFFu) : kNoPrev;
+}
+// after a step's contacts c: every step sets the contact bits (flags_with_contacts); the dense
+// reward first remembers c as its previous contacts (RS:185, flags_with_prev_contacts), the sparse
+// reward leaves those bits alone
+__device__ __forceinline__ uint32_t flags_with_contacts(uint32_t flags, uint32_t c) { return (flags & ~0xFFu) | c; }
+__device__ __forceinline__ uint32_t flags_with_prev_contacts(uint32_t flags, uint32_t c) {
+    return (flags & ~(0xFFu << kPrevShift)) | (c << kPrevShift) | kHasPrev;
+}
+// after a reset, before its contacts (ME:176) are or-ed in: no previous contacts, an f32-valued
+// position, and the episode friction's type (the host marks rows whose friction is a numpy.float64)
+// (the bool by reference: by value, EpisodeRow's member reaches the select through another
+// conversion, k_eval_mlp allocates its registers differently and measured 3-4 % slower)
+__device__ __forceinline__ uint32_t flags_after_reset(const bool& fric_f64) {
+    return kOpIsF32 | kHasObject | (fric_f64 ? kFricF64 : 0u);
+}
+
+// RS:147-162 the closure term's sum of one finger's negative joint positions, in joint order
+__device__ __forceinline__ float negative_sum(const float* joints) {
+    float acc = 0.0f;
 #pragma unroll
-    for (int f = 0; f < kF; ++f) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kJ; ++j) {
-            const float v = e.jp[kJ * f + j];
-            if (v < 0.0f) acc = acc + v;
-        }
-        sum = sum + (-acc);
-    }
-    const float avg = div_f(sum);                         // np.mean(...)  (f32 / 5)
-    const float clo = clipf(div_f(avg), 0.0f, 1.0f);      // avg / num_fingers
-    float st = 0.0f;                                      // RS:166-187
-    if (e.flags & kHasPrev) {
-        const uint32_t prev = (e.flags >> kPrevShift) & 0xFFu;
+    for (int j = 0; j < kJ; ++j)
+        if (joints[j] < 0.0f) acc = acc + joints[j];
+    return acc;
+}
+// RS:86-91 the weighted total of the four dense terms
+__device__ __forceinline__ double weighted_reward(const Weights& w, const double comp[4]) {
+    return ((w.w_dist * comp[0] + w.w_con * comp[1]) + w.w_clo * comp[2]) + w.w_st * comp[3];
+}
+// RS:50-187 dense reward from its inputs: dmin the minimum tip distance, c / prev the contacts and
+// the previous ones (kNoPrev: none), closure_sum the f32 sum over the fingers of the negated sums
+// of their negative joint positions (RS:147-162; each caller forms it in the reference's order).
+// comp[]: distance, contact, closure, stability.
+__device__ __forceinline__ double dense_reward_of(double dmin, uint32_t c, uint32_t prev, float closure_sum,
+                                                  const Weights& w, double comp[4]) {
+    comp[0] = exp(-5.0 * dmin);                                 // RS:111-116
+    comp[1] = count_over_f_f64((uint32_t)__popc(c));            // RS:128-134 (n / 5)
+    const float avg = div_f(closure_sum);                       // np.mean(...)  (f32 / 5)
+    comp[2] = (double)clipf(div_f(avg), 0.0f, 1.0f);            // avg / num_fingers
+    float st = 0.0f;                                            // RS:166-187
+    if (prev != kNoPrev) {
         float ch = 0.0f;
 #pragma unroll
         for (int f = 0; f < kF; ++f) ch = ch + (float)(((c ^ prev) >> f) & 1u);
         st = clipf(1.0f - count_over_f_f32((uint32_t)ch), 0.0f, 1.0f);
     }
-    e.flags = (e.flags & ~(0xFFu << kPrevShift)) | (c << kPrevShift) | kHasPrev;
-    comp[0] = dist;
-    comp[1] = con;
-    comp[2] = (double)clo;
     comp[3] = (double)st;
-    return ((w.w_dist * dist + w.w_con * con) + w.w_clo * (double)clo) + w.w_st * (double)st;
+    return weighted_reward(w, comp);
+}
+// RS:228-234 sparse reward of a contact mask
+__device__ __forceinline__ double sparse_reward(uint32_t c) { return __popc(c) >= 3 ? 1.0 : -0.01; }
+
+// Reset tail (ME:124-182).  A uniform(lo, hi) draw from u in [0, 1); the joint draw ME:143-145;
+// a curriculum sampler (config.py:44-113) tabled as {lo, span} with a range and {constant, NaN}
+// without one (u is never NaN); the object axis: sticky position rounded through f32 (ME:156-161),
+// velocity zeroed.
+__device__ __forceinline__ double uniform_draw(double lo, double hi, double u) { return lo + (hi - lo) * u; }
+__device__ __forceinline__ double joint_reset_draw(double u) { return uniform_draw(-0.1, 0.1, u); }
+__device__ __forceinline__ double sampler_value(double lo, double span, double u) {
+    return span == span ? lo + span * u : lo;
+}
+__device__ __forceinline__ void object_axis_reset(double& op, float& ov, bool has, double spawn) {
+    op = (double)(float)(has ? op : spawn);
+    ov = 0.0f;
 }
 
-// ME:198-252 one step.  a[] = raw action (clipped here, ME:199).
+// ---------------------------------------------------------------- the scalar form (one lane, one env)
+// dense reward of the env's state (the closure sum in the scalar order); flags: previous contacts
+__device__ __forceinline__ double dense_reward(const Env& e, uint32_t c, double dmin, const Weights& w, double comp[4]) {
+    float sum = 0.0f;
+#pragma unroll
+    for (int f = 0; f < kF; ++f) sum = sum + (-negative_sum(e.jp + kJ * f));
+    return dense_reward_of(dmin, c, prev_contacts(e.flags), sum, w, comp);
+}
+
+// ME:198-252 one step.  a[] = raw action (clipped in joint_step, ME:199).
 // Returns reward; term/trunc flags; comp[] the reward components.
 __device__ __forceinline__ double env_step(Env& e, const float* a, bool dense, const Weights& w,
                                            int max_episode_steps, bool& term, bool& trunc, double comp[4]) {
 #pragma unroll
-    for (int k = 0; k < kD; ++k) {
-        const float ak = clipf(a[k], -1.0f, 1.0f);
-        e.jv[k] = kC09 * e.jv[k] + kC01 * ak;                  // ME:203 (f32, no FMA)
-        e.jp[k] = clipf(e.jp[k] + e.jv[k] * kDt, -1.0f, 1.0f);  // ME:204-207
-    }
-    const double damp = 1.0 - (e.fric * 0.1 * 0.01);  // ME:215
-    const float dampf = (float)damp;
-    const double g[3] = {0.0, 0.0, kGz};
-    const bool op32 = (e.flags & kOpIsF32) != 0;
-    const bool fric_f64 = (e.flags & kFricF64) != 0;
+    for (int k = 0; k < kD; ++k) joint_step(e.jp[k], e.jv[k], a[k]);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        float v = fric_f64 ? (float)((double)e.ov[i] * damp) : e.ov[i] * dampf;  // ME:216 (NEP 50)
-        v = (float)((double)v + g[i]);                                          // ME:219 f32 += f64
-        const float inc = v * kDt;                                              // ME:222
-        double p = op32 ? (double)((float)e.op[i] + inc) : e.op[i] + (double)inc;
-        p = clipd(p, kLo[i], kHi[i]);                                           // ME:225-229 -> f64
-        if ((p <= kLo[i] && v < 0.0f) || (p >= kHi[i] && v > 0.0f)) v = 0.0f;   // ME:232-235
-        e.op[i] = p;
-        e.ov[i] = v;
+        const AxisState ax = object_axis_step(e.op[i], e.ov[i], i, e.fric, e.flags);
+        e.op[i] = ax.q;
+        e.ov[i] = ax.v;
     }
     e.flags &= ~kOpIsF32;
     double dmin;
@@ -264,11 +328,12 @@ __device__ __forceinline__ double env_step(Env& e, const float* a, bool dense, c
     double r;
     if (dense) {
         r = dense_reward(e, c, dmin, w, comp);
+        e.flags = flags_with_prev_contacts(e.flags, c);
     } else {
-        r = (__popc(c) >= 3) ? 1.0 : -0.01;  // RS:226-231
+        r = sparse_reward(c);
         comp[0] = comp[1] = comp[2] = comp[3] = 0.0;
     }
-    e.flags = (e.flags & ~0xFFu) | c;
+    e.flags = flags_with_contacts(e.flags, c);
     term = __popc(c) >= 3;                   // ME:332-336
     trunc = e.t >= max_episode_steps;        // ME:245 (before the increment)
     e.t += 1;                                // ME:247
@@ -287,13 +352,9 @@ __device__ __forceinline__ void env_reset(Env& e, const double* draw, const dxrl
     e.fric = cu.has_friction_range ? draw[kD + 2] : cu.friction_coefficient;
     const bool has = (e.flags & kHasObject) != 0;  // ME:156-161 sticky position
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        e.op[i] = (double)(float)(has ? e.op[i] : draw[kD + 3 + i]);
-        e.ov[i] = 0.0f;
-    }
+    for (int i = 0; i < 3; ++i) object_axis_reset(e.op[i], e.ov[i], has, draw[kD + 3 + i]);
     e.t = 0;
-    // prev_contacts = None (RS:45-48); the host marks rows whose episode friction is a numpy.float64
-    e.flags = kOpIsF32 | kHasObject | (cu.friction_is_f64_scalar ? kFricF64 : 0u);
+    e.flags = flags_after_reset(cu.friction_is_f64_scalar != 0);
     double dmin;
     e.flags |= contacts_of(e, dmin);  // ME:176
 }
@@ -311,12 +372,12 @@ __device__ __forceinline__ void philox_reset_draws(double* d, const dxrl_curricu
         if (4 * b + 3 < 2 * kReset + 2) u[4 * b + 3] = r.w;
     }
 #pragma unroll
-    for (int k = 0; k < kD; ++k) d[k] = -0.1 + (0.1 - -0.1) * u01_53(u[2 * k], u[2 * k + 1]);
+    for (int k = 0; k < kD; ++k) d[k] = joint_reset_draw(u01_53(u[2 * k], u[2 * k + 1]));
     const double* rng[6] = {cu.size_range, cu.mass_range, cu.friction_range,
                             cu.spawn_x_range, cu.spawn_y_range, cu.spawn_z_range};
 #pragma unroll
     for (int k = 0; k < 6; ++k)
-        d[kD + k] = rng[k][0] + (rng[k][1] - rng[k][0]) * u01_53(u[2 * (kD + k)], u[2 * (kD + k) + 1]);
+        d[kD + k] = uniform_draw(rng[k][0], rng[k][1], u01_53(u[2 * (kD + k)], u[2 * (kD + k) + 1]));
 }
 
 // env_reset(philox_reset_draws(...)) without materialising the 21 draws: each
@@ -335,28 +396,25 @@ __device__ __forceinline__ void env_reset_philox(Env& e, const dxrl_curriculum& 
             if (k >= kReset) break;
             const double u = half ? u01_53(r.z, r.w) : u01_53(r.x, r.y);
             if (k < kD) {
-                e.jp[k] = (float)(-0.1 + (0.1 - -0.1) * u);
+                e.jp[k] = (float)joint_reset_draw(u);
                 e.jv[k] = 0.0f;
             } else if (k == kD + 0) {
-                e.size = cu.has_size_range ? cu.size_range[0] + (cu.size_range[1] - cu.size_range[0]) * u : cu.object_size;
+                e.size = cu.has_size_range ? uniform_draw(cu.size_range[0], cu.size_range[1], u) : cu.object_size;
             } else if (k == kD + 1) {
-                e.mass = cu.has_mass_range ? cu.mass_range[0] + (cu.mass_range[1] - cu.mass_range[0]) * u : cu.object_mass;
+                e.mass = cu.has_mass_range ? uniform_draw(cu.mass_range[0], cu.mass_range[1], u) : cu.object_mass;
             } else if (k == kD + 2) {
-                e.fric = cu.has_friction_range ? cu.friction_range[0] + (cu.friction_range[1] - cu.friction_range[0]) * u
+                e.fric = cu.has_friction_range ? uniform_draw(cu.friction_range[0], cu.friction_range[1], u)
                                                : cu.friction_coefficient;
             } else {
                 const double* rg = k == kD + 3 ? cu.spawn_x_range : (k == kD + 4 ? cu.spawn_y_range : cu.spawn_z_range);
-                spawn[k - kD - 3] = rg[0] + (rg[1] - rg[0]) * u;
+                spawn[k - kD - 3] = uniform_draw(rg[0], rg[1], u);
             }
         }
     }
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        e.op[i] = (double)(float)(has ? e.op[i] : spawn[i]);
-        e.ov[i] = 0.0f;
-    }
+    for (int i = 0; i < 3; ++i) object_axis_reset(e.op[i], e.ov[i], has, spawn[i]);
     e.t = 0;
-    e.flags = kOpIsF32 | kHasObject | (cu.friction_is_f64_scalar ? kFricF64 : 0u);
+    e.flags = flags_after_reset(cu.friction_is_f64_scalar != 0);
     double dmin;
     e.flags |= contacts_of(e, dmin);
 }

@@ -211,7 +211,7 @@ __global__ void k_reward_compute(int64_t count, bool dense, Weights w, const flo
     }
     double* o = out + i * 5;
     if (!dense) {  // RS:228-242
-        o[0] = __popc(mask) >= 3 ? 1.0 : -0.01;
+        o[0] = sparse_reward(mask);
         o[1] = o[2] = o[3] = o[4] = 0.0;
         return;
     }
@@ -240,7 +240,7 @@ __global__ void k_reward_compute(int64_t count, bool dense, Weights w, const flo
     for (int f = 0; f < kF; ++f) prev[i * kF + f] = c[f];
     has_prev[i] = 1;
     comp[3] = (double)st;
-    o[0] = ((w.w_dist * comp[0] + w.w_con * comp[1]) + w.w_clo * comp[2]) + w.w_st * comp[3];  // RS:86-91
+    o[0] = weighted_reward(w, comp);
     o[1] = comp[0];
     o[2] = comp[1];
     o[3] = comp[2];

@@ -198,8 +198,8 @@ struct EvalRow {
         } else {
             uint32_t rk0, rk1;
             env_key(a.reset_seed, key(rec), rk0, rk1);
-            u1 = -0.1 + (0.1 - -0.1) * reset_uniform_at(sa, rk0, rk1, 0);
-            v2 = has2 ? lo2 + (hi2 - lo2) * reset_uniform_at(kD + s2, rk0, rk1, 0) : cst2;
+            u1 = joint_reset_draw(reset_uniform_at(sa, rk0, rk1, 0));
+            v2 = has2 ? uniform_draw(lo2, hi2, reset_uniform_at(kD + s2, rk0, rk1, 0)) : cst2;
         }
         jp = s < kD ? (float)u1 : 0.0f;  // ME:143-145 .astype(float32)
         jv = 0.0f;
@@ -207,13 +207,10 @@ struct EvalRow {
         fric = row_bcast<2>(v2);
         const double sx = row_bcast<3>(v2), sy = row_bcast<4>(v2), sz = row_bcast<5>(v2);
         const double spawn = s == 1 ? sy : (s == 2 ? sz : sx);
-        const bool has = (flags & kHasObject) != 0;  // ME:156-161 sticky position
-        if (s < 3) {
-            opd = (double)(float)(has ? opd : spawn);
-            ovd = 0.0f;
-        }
+        const bool has = (flags & kHasObject) != 0;
+        if (s < 3) object_axis_reset(opd, ovd, has, spawn);
         et = 0;
-        flags = kOpIsF32 | kHasObject | (fric64 ? kFricF64 : 0u);
+        flags = flags_after_reset(fric64);
         double op3[3], dmin;
         float g3[3];
         row_object(opd, op3);
@@ -266,27 +263,11 @@ struct EvalRow {
     // history byte and moments.  Returns terminated || truncated and leaves `step`, the step limit
     // and the phase to the caller; noff / have: take_obs_noise of the observation the step returns.
     __device__ __forceinline__ bool step_env(const EvalParams& p, float act, int64_t& noff, bool& have) {
-        if (s < kD) {
-            const float ak = clipf(act, -1.0f, 1.0f);
-            jv = kC09 * jv + kC01 * ak;
-            jp = clipf(jp + jv * kDt, -1.0f, 1.0f);
-        }
-        {
-            const double damp = 1.0 - (fric * 0.1 * 0.01);
-            const float dampf = (float)damp;
-            const bool op32 = (flags & kOpIsF32) != 0, fric_f64 = (flags & kFricF64) != 0;
-            const int ax = s < 3 ? s : 0;
-            const double gz = ax == 2 ? kGz : 0.0, lo = ax == 2 ? 0.0 : -0.2, hi = ax == 2 ? 0.3 : 0.2;
-            float v = fric_f64 ? (float)((double)ovd * damp) : ovd * dampf;
-            v = (float)((double)v + gz);
-            const float inc = v * kDt;
-            double q = op32 ? (double)((float)opd + inc) : opd + (double)inc;
-            q = clipd(q, lo, hi);
-            if ((q <= lo && v < 0.0f) || (q >= hi && v > 0.0f)) v = 0.0f;
-            if (s < 3) {
-                opd = q;
-                ovd = v;
-            }
+        if (s < kD) joint_step(jp, jv, act);
+        const AxisState ax = object_axis_step(opd, ovd, s < 3 ? s : 0, fric, flags);
+        if (s < 3) {
+            opd = ax.q;
+            ovd = ax.v;
         }
         flags &= ~kOpIsF32;
         double op3[3], dmin;
@@ -294,31 +275,16 @@ struct EvalRow {
         row_object(opd, op3);
         const uint32_t c = row_contacts(jp, op3, size, s, gbit, dmin, g3);
         double r;
-        if (p.dense) {  // RS:50-187
-            const double dist = exp(-5.0 * dmin);
-            const double con = count_over_f_f64(__popc(c));
-            float nacc = 0.0f;
-#pragma unroll
-            for (int j = 0; j < kJ; ++j)
-                if (g3[j] < 0.0f) nacc = nacc + g3[j];
+        if (p.dense) {
             float sum = 0.0f;
-            row_neg_sum_fingers(nacc, sum);  // nacc of finger f on lane 3 f
-            const float avg = div_f(sum);
-            const float clo = clipf(div_f(avg), 0.0f, 1.0f);
-            float st = 0.0f;
-            if (flags & kHasPrev) {
-                const uint32_t prev = (flags >> kPrevShift) & 0xFFu;
-                float ch = 0.0f;
-#pragma unroll
-                for (int f = 0; f < kF; ++f) ch = ch + (float)(((c ^ prev) >> f) & 1u);
-                st = clipf(1.0f - count_over_f_f32((uint32_t)ch), 0.0f, 1.0f);
-            }
-            flags = (flags & ~(0xFFu << kPrevShift)) | (c << kPrevShift) | kHasPrev;
-            r = ((p.w.w_dist * dist + p.w.w_con * con) + p.w.w_clo * (double)clo) + p.w.w_st * (double)st;
+            row_neg_sum_fingers(negative_sum(g3), sum);  // finger f's on lane 3 f
+            double comp[4];
+            r = dense_reward_of(dmin, c, prev_contacts(flags), sum, p.w, comp);
+            flags = flags_with_prev_contacts(flags, c);
         } else {
-            r = (__popc(c) >= 3) ? 1.0 : -0.01;  // RS:226-231
+            r = sparse_reward(c);
         }
-        flags = (flags & ~0xFFu) | c;
+        flags = flags_with_contacts(flags, c);
         te = __popc(c) >= 3;                        // ME:332-336
         const bool tr = et >= p.max_episode_steps;  // ME:245 (before the increment)
         et += 1;

@@ -4,7 +4,7 @@
 // object axes -- so one 8-wave workgroup holds 32 envs and 8192 envs run in ONE round of 256
 // workgroups (k_pg_rollout_ws holds 16 envs per workgroup: two rounds).
 //
-// Same step structure as k_pg_rollout_ws (dxrl_pg.hip): env waves 0..3 hold the envs, aux waves
+// Same step structure as k_pg_rollout_ws (dxrl_pg_rollout16.hip): env waves 0..3 hold the envs, aux waves
 // 4..7 are their lane-for-lane twins; all 8 waves split the actor MLP, now on two 16-row tiles.
 // Every value is produced by the same instruction sequence on the same operands:
 //   * the MLP: the same 16x16x32 MFMA chains in the same k order (a row's result does not depend
@@ -147,13 +147,13 @@ struct E8Samplers {  // per env and extra slot: lo + span u with a range, the co
 struct __attribute__((aligned(16))) E8Reward {  // an env's reward / log pi inputs and episode end of one step
     float term[16];      // log-density terms of the policy's action, action order (15 used)
     double dmin;         // np.min of the fingers' tip-object distances
-    uint32_t c, prev;    // contacts, previous contacts (0x100: none)
+    uint32_t c, prev;    // contacts, previous contacts (kNoPrev: none)
     float nacc[kF];      // per finger: sum of its negative joint positions
     int32_t len, done, te;
     unsigned long long rctr;  // reset counter after the step (the next step's reset draws use it)
 };
 
-// kDense = false: the sparse reward (RS:228-234), as in k_pg_rollout_ws -- the settle reads the
+// kDense = false: the sparse reward, as in k_pg_rollout_ws -- the settle reads the
 // contacts only; dmin, nacc[] and prev stay unwritten and the flags' previous-contact bits untouched
 template <bool kNoise, bool kDiag, bool kDense = true>
 __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p) {
@@ -226,8 +226,8 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
     float ovd = 0.0f;
     uint32_t flags = 0;
     int32_t et = 0;
-    double size = 0.0, mass = 0.0, fric = 0.0, ep_ret = 0.0, sum_ret = 0.0;
-    int32_t cnt = 0, sum_len = 0, succ = 0;
+    double size = 0.0, mass = 0.0, fric = 0.0;
+    EpisodeBook book;
     uint64_t rctr = 0;
     bool fric64 = false;
     if (live) {
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
                 RW[1][eg].rctr = rctr;  // "after step -1"
             }
         } else {
-            ep_ret = p.ep_ret[i];
+            book.ep_ret = p.ep_ret[i];
         }
     }
     const bool obs_noise = kNoise && p.obs_noise > 0.0f, dyn_noise = kNoise && p.dyn_noise > 0.0f;
@@ -319,10 +319,9 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
             const int k = 2 * b + h;
             const double u = h ? ub : ua;
             if (k < kD) {
-                DR.jp0[16 * e + k] = (float)(-0.1 + (0.1 - -0.1) * u);
+                DR.jp0[16 * e + k] = (float)joint_reset_draw(u);
             } else if (k < kReset) {
-                const double lo = RSMP.lo[8 * e + k - kD], span = RSMP.span[8 * e + k - kD];
-                DR.v2[8 * e + k - kD] = span == span ? lo + span * u : lo;
+                DR.v2[8 * e + k - kD] = sampler_value(RSMP.lo[8 * e + k - kD], RSMP.span[8 * e + k - kD], u);
             }
         }
     };
@@ -349,58 +348,25 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
                 continue;
             }
             *reinterpret_cast<float4*>(&DR.on[buf][kObsLd * e + 4 * b]) = nz;
-            if (kDiag && p.obs_noise_tape) {  // parity tape: the value write_obs_row adds
-                const int64_t row = (int64_t)(c - p.iteration * (uint64_t)T);
-                const int64_t ie = (int64_t)blockIdx.x * kE8Envs + e;
-                float4 v;
-                v.x = 4 * b + 0 < kObs ? p.obs_noise * nz.x : 0.0f;
-                v.y = 4 * b + 1 < kObs ? p.obs_noise * nz.y : 0.0f;
-                v.z = 4 * b + 2 < kObs ? p.obs_noise * nz.z : 0.0f;
-                v.w = 4 * b + 3 < kObs ? p.obs_noise * nz.w : 0.0f;
-                *reinterpret_cast<float4*>(p.obs_noise_tape + (row * n + ie) * kObsNoiseLd + 4 * b) = v;
-            }
+            if (kDiag && p.obs_noise_tape)  // parity tape: the value write_obs_row adds
+                write_obs_noise_tape(p, (int64_t)(c - p.iteration * (uint64_t)T), (int64_t)blockIdx.x * kE8Envs + e, b, n4);
         }
     };
-    // ---- aux: the reward (dense RS:50-187, sparse RS:228-234) and the episode bookkeeping of a
+    // ---- aux: the reward (dense_reward_of / sparse_reward) and the episode bookkeeping of a
     // finished step
     const auto settle = [&](int64_t t_) {
         const E8Reward& w = RW[t_ & 1][eg];
         double r;
         if constexpr (kDense) {
-            const double dist = exp(-5.0 * w.dmin);
-            const double con = count_over_f_f64(__popc(w.c));
             float sum = 0.0f;
 #pragma unroll
             for (int f = 0; f < kF; ++f) sum = sum + (-w.nacc[f]);
-            const float avg = div_f(sum);
-            const float clo = clipf(div_f(avg), 0.0f, 1.0f);
-            float st = 0.0f;
-            if (w.prev != 0x100u) {
-                float ch = 0.0f;
-#pragma unroll
-                for (int f = 0; f < kF; ++f) ch = ch + (float)(((w.c ^ w.prev) >> f) & 1u);
-                st = clipf(1.0f - count_over_f_f32((uint32_t)ch), 0.0f, 1.0f);
-            }
-            r = ((p.w.w_dist * dist + p.w.w_con * con) + p.w.w_clo * (double)clo) + p.w.w_st * (double)st;
+            double comp[4];
+            r = dense_reward_of(w.dmin, w.c, w.prev, sum, p.w, comp);
         } else {
-            r = __popc(w.c) >= 3 ? 1.0 : -0.01;  // RS:228-234
+            r = sparse_reward(w.c);
         }
-        ep_ret += r;
-        if (s == 0) p.rew[t_ * n + i] = (float)r;
-        if (w.done) {
-            if (s == 0 && cnt < p.record_cap) {
-                const int64_t o = i * p.record_cap + cnt;
-                p.rec_return[o] = ep_ret;
-                p.rec_length[o] = w.len;
-                p.rec_success[o] = p.success_terminated ? (uint8_t)w.te : (uint8_t)0;
-                p.rec_end_step[o] = (int32_t)t_;
-            }
-            ++cnt;
-            sum_ret += ep_ret;
-            sum_len += w.len;
-            succ += w.te;
-            ep_ret = 0.0;
-        }
+        book.settle_step(p, r, w.done, w.te, w.len, t_, i, s == 0);
     };
     // ---- env lanes, P0: the observation row (ME:254-264): finger lane f its joint positions /
     // velocities 3 f .. 3 f + 2 and contact flag f, object lane 5 + a the object position /
@@ -433,20 +399,10 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
     // ---- env lanes, head phase: the object's damping, gravity, position and wall stops
     // (ME:212-235; independent of the action)
     const auto env_object_step = [&]() {
-        const double damp = 1.0 - (fric * 0.1 * 0.01);
-        const float dampf = (float)damp;
-        const bool op32 = (flags & kOpIsF32) != 0, fric_f64 = (flags & kFricF64) != 0;
-        const int a3 = finger ? 0 : ax;
-        const double gz = a3 == 2 ? kGz : 0.0, lo = a3 == 2 ? 0.0 : -0.2, hi = a3 == 2 ? 0.3 : 0.2;
-        float v = fric_f64 ? (float)((double)ovd * damp) : ovd * dampf;
-        v = (float)((double)v + gz);
-        const float inc = v * kDt;
-        double q = op32 ? (double)((float)opd + inc) : opd + (double)inc;
-        q = clipd(q, lo, hi);
-        if ((q <= lo && v < 0.0f) || (q >= hi && v > 0.0f)) v = 0.0f;
+        const AxisState st = object_axis_step(opd, ovd, finger ? 0 : ax, fric, flags);
         if (!finger) {
-            opd = q;
-            ovd = v;
+            opd = st.q;
+            ovd = st.v;
         }
         flags &= ~kOpIsF32;
     };
@@ -468,11 +424,7 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
                 if (kDiag && p.applied_act) p.applied_act[m * kActPad + k] = a;
                 if (kDiag && p.dyn_noise_tape)
                     p.dyn_noise_tape[m * kActPad + k] = dyn_noise ? p.dyn_noise * DR.dzn[16 * eg + k] : 0.0f;
-                if (env_on) {
-                    const float ak = clipf(a, -1.0f, 1.0f);
-                    jv[j] = kC09 * jv[j] + kC01 * ak;
-                    jp[j] = clipf(jp[j] + jv[j] * kDt, -1.0f, 1.0f);
-                }
+                if (env_on) joint_step(jp[j], jv[j], a);
             }
         } else if (s == kF) {  // the tapes' padding slot
             p.act[m * kActPad + kAct] = 0.0f;
@@ -484,13 +436,7 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
             const uint32_t c = contacts8(jp, opd, size, finger, gbit, x);
             E8Reward& rw = RW[t & 1][eg];
             if constexpr (kDense) {
-                if (finger) {  // the reward's inputs for the aux twin (RS:101-187)
-                    float nacc = 0.0f;
-#pragma unroll
-                    for (int j = 0; j < kJ; ++j)
-                        if (jp[j] < 0.0f) nacc = nacc + jp[j];
-                    rw.nacc[s] = nacc;
-                }
+                if (finger) rw.nacc[s] = negative_sum(jp);  // the reward's inputs for the aux twin
                 // dmin = min_f sqrt_rn(x_f) = sqrt_rn(min_f x_f) (the rounded root is monotone)
                 double xm = bcast8<0>(x);
                 const double x1 = bcast8<1>(x), x2 = bcast8<2>(x), x3 = bcast8<3>(x), x4 = bcast8<4>(x);
@@ -501,22 +447,20 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
                 if (s == 0) {
                     rw.dmin = sqrt(xm);
                     rw.c = c;
-                    rw.prev = (flags & kHasPrev) ? ((flags >> kPrevShift) & 0xFFu) : 0x100u;
+                    rw.prev = prev_contacts(flags);
                 }
-                flags = (flags & ~(0xFFu << kPrevShift)) | (c << kPrevShift) | kHasPrev;
             } else {
                 if (s == 0) rw.c = c;  // the sparse reward's one input
             }
-            flags = (flags & ~0xFFu) | c;
+            if (kDense) flags = flags_with_prev_contacts(flags, c);
+            flags = flags_with_contacts(flags, c);
             te = __popc(c) >= 3;
             tr = et >= p.max_episode_steps;
             et += 1;
         }
         const bool d = env_on && (te || tr || et >= p.max_steps);
         if (s == 0) {
-            p.done[m] = d;
-            if (p.ep_code)
-                p.ep_code[m] = d ? (uint16_t)((et << 1) | (p.success_terminated && te ? 1 : 0)) : (uint16_t)0;
+            write_step_end(p, m, d, te, et);
             E8Reward& rw = RW[t & 1][eg];
             rw.done = d;
             rw.te = te;
@@ -535,13 +479,9 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
             mass = DR.v2[8 * eg + 1];
             fric = DR.v2[8 * eg + 2];
             const bool has = (flags & kHasObject) != 0;
-            if (!finger) {
-                const double spawn = DR.v2[8 * eg + 3 + ax];
-                opd = (double)(float)(has ? opd : spawn);
-                ovd = 0.0f;
-            }
+            if (!finger) object_axis_reset(opd, ovd, has, DR.v2[8 * eg + 3 + ax]);
             et = 0;
-            flags = kOpIsF32 | kHasObject | (fric64 ? kFricF64 : 0u);
+            flags = flags_after_reset(fric64);
             double x;
             flags |= contacts8(jp, opd, size, finger, gbit, x);  // ME:176
             ++rctr;
@@ -676,13 +616,7 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
         if (T > 0 && env_on) settle(T - 1);
         if (kDiag && (p.diag & 2))
             for (int64_t t = 0; t < T && s == 0; ++t) p.rew[t * n + i] = 0.0f;
-        if (s == 0) {
-            p.ep_ret[i] = ep_ret;
-            p.ep_count[i] = cnt;
-            p.ep_sum_ret[i] = sum_ret;
-            p.ep_sum_len[i] = sum_len;
-            p.ep_succ[i] = succ;
-        }
+        if (s == 0) book.store(p, i);
     }
     if (live && !aux) {
         // bootstrap observation (slot T), then the state back to the slab
@@ -715,15 +649,9 @@ __global__ __launch_bounds__(kE8Threads, 1) void k_pg_rollout_e8(PgRolloutArgs p
 
 int launch_pg_rollout_e8(const PgRolloutArgs& p, int64_t n, bool noise, bool diag, bool dense, hipStream_t st) {
     const dim3 grid((unsigned)((n + kE8Envs - 1) / kE8Envs)), block(kE8Threads);
-    if (!dense) {
-        if (noise && diag) hipLaunchKernelGGL((k_pg_rollout_e8<true, true, false>), grid, block, 0, st, p);
-        else if (noise) hipLaunchKernelGGL((k_pg_rollout_e8<true, false, false>), grid, block, 0, st, p);
-        else if (diag) hipLaunchKernelGGL((k_pg_rollout_e8<false, true, false>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((k_pg_rollout_e8<false, false, false>), grid, block, 0, st, p);
-    } else if (noise && diag) hipLaunchKernelGGL((k_pg_rollout_e8<true, true>), grid, block, 0, st, p);
-    else if (noise) hipLaunchKernelGGL((k_pg_rollout_e8<true, false>), grid, block, 0, st, p);
-    else if (diag) hipLaunchKernelGGL((k_pg_rollout_e8<false, true>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((k_pg_rollout_e8<false, false>), grid, block, 0, st, p);
+    with_rollout_switches(noise, diag, dense, [&](auto kNoise, auto kDiag, auto kDense) {
+        hipLaunchKernelGGL((k_pg_rollout_e8<kNoise(), kDiag(), kDense()>), grid, block, 0, st, p);
+    });
     if (int rc = launch_check("k_pg_rollout_e8")) return rc;
     if (p.diag & 128) {  // diagnostics: mean cycles per env per step segment, env / aux waves
         std::vector<unsigned long long> h((size_t)n * 16);

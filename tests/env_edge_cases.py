@@ -1,8 +1,8 @@
 """Crafted env states that reach the rare branches of the env step (test infrastructure).
 
-The env physics exists in four device implementations (csrc/dxrl_device.h env_step and its
-lane-split restatements in dxrl_pg.hip, dxrl_pg_rollout8.hip and dxrl_eval_row.h, which k_eval_ls
-and k_eval_mlp share).
+The env physics runs in four device forms (csrc/dxrl_device.h env_step and the lane-split forms
+in dxrl_pg_rollout16.hip, dxrl_pg_rollout8.hip and dxrl_eval_row.h, which k_eval_ls and k_eval_mlp
+share), all built from the formulas that dxrl_device.h states once.
 States that come from ordinary resets and ordinary policies never take the x / y wall stops, the
 z ceiling, the joint clip at +-1, sqrt_below()'s exact-root branch, most of the 32 x 33 contact /
 previous-contact combinations, or the truncation bound.  ``build(mode)`` returns lanes that do, in

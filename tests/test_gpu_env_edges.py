@@ -1,8 +1,10 @@
 """GPU: every env-step implementation on the crafted edge lanes of tests/env_edge_cases.py.
 
-The env physics is written out four times (csrc/dxrl_device.h env_step; the lane-split
-restatements in dxrl_pg.hip, dxrl_pg_rollout8.hip and dxrl_eval_row.h, the last one compiled into
-both k_eval_ls and k_eval_mlp) and runs in five kernel families.  States
+The env's formulas are stated once (csrc/dxrl_device.h: joint_step, object_axis_step,
+dense_reward_of, sparse_reward, the flag-word transitions, the reset tail) but scheduled four ways
+-- the scalar env_step, and the lane-split forms in dxrl_pg_rollout16.hip, dxrl_pg_rollout8.hip
+and dxrl_eval_row.h, the last one compiled into both k_eval_ls and k_eval_mlp: which lanes compute,
+which commit, in which phase and through which LDS records -- and run in five kernel families.  States
 from ordinary resets and policies never take the x / y wall stops, the z ceiling, the joint clip,
 sqrt_below()'s exact-root branch, most contact / previous-contact combinations or the truncation
 bounds; these lanes do (tests/test_env_edge_cases_host.py proves it on the CPU, and every test

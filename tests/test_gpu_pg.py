@@ -503,6 +503,48 @@ def test_lane_split_rollout_matches_64_env_kernel(pkg, cur, n, noise):
             assert torch.equal(a, b), k
 
 
+@pytest.mark.parametrize("noise", [0.0, 0.05])
+@pytest.mark.parametrize("reward", ["dense", "sparse"])
+@pytest.mark.parametrize("cur", ["easy", "hard"])
+def test_rollout_kernels_settle_episodes_alike(pkg, cur, reward, noise):
+    """The episode settle of the three rollout kernels (diag 16 / 0 / 1024), where the twin test
+    above does not look: 40 envs (a ragged last workgroup of the 16- and of the 32-env kernel),
+    max_steps 5 on a 24-step horizon (every env ends at least four episodes per launch) and
+    record_cap 1 (the cnt < record_cap guard refuses most episode ends), two launches.  Equal bit for
+    bit: the open-episode return, the episode count and the sums of returns, lengths and successes,
+    the record block -- whose slots past record_cap keep their initial bytes -- and the done /
+    ep_code bytes."""
+    n, T, cap, slots = 40, 24, 1, 3
+    fill = {"rec_return": -7.0, "rec_length": -7, "rec_success": 0xA5, "rec_end": -7}
+    outs = []
+    for diag in (16, 0, 1024):
+        env = pkg.envs.VecEnv(n, curriculum_config=pkg.CurriculumConfig.named(cur), reward_type=reward, seed=11)
+        cfg = pkg.trainer.TrainerConfig(horizon=T, seed=5, max_steps=5, record_cap=cap, success_rule="terminated",
+                                        obs_noise_std=noise, dyn_noise_std=noise)
+        tr = pkg.trainer.PGTrainer(env, cfg)
+        env.reset(write_obs=False)
+        tr.diag_flags = diag
+        tr.ep_code = torch.full((T * n,), -1, dtype=torch.int16, device=tr.done.device)  # the scheduler feed
+        for name, v in fill.items():  # env i's records at i cap + k, k < cap: `slots` x as many slots
+            setattr(tr, name, torch.full((slots * n * cap,), v, dtype=getattr(tr, name).dtype, device=tr.done.device))
+        out = []
+        for _ in range(2):
+            tr.rollout()
+            tr.iteration_index += 1
+            torch.cuda.synchronize()
+            out += [t.clone() for t in (tr.ep_ret, tr.ep_count, tr.ep_sum_ret, tr.ep_sum_len, tr.ep_succ, tr.rec_return,
+                                        tr.rec_length, tr.rec_success, tr.rec_end, tr.done, tr.ep_code, tr.rew)]
+        assert int(tr.ep_count.min()) >= 4
+        assert int(tr.rec_length[:n * cap].min()) >= 1 and int(tr.rec_end[:n * cap].min()) >= 0
+        assert (tr.ep_code != 0).sum() == tr.done.sum() == tr.ep_count.sum()
+        for name, v in fill.items():
+            assert bool((getattr(tr, name)[n * cap:] == v).all()), name
+        outs.append(out)
+    for other in outs[1:]:
+        for k, (a, b) in enumerate(zip(outs[0], other)):
+            assert torch.equal(a, b), k
+
+
 def test_minibatch_gradients_sum_to_full_batch(pkg):
     """Time-contiguous minibatches (pointer offsets into the tape, same kernels): each pass is
     the gradient of the mean loss over its own samples (scale 1 / its rows), so the mean of the

@@ -39,6 +39,7 @@ for k in range(0, len(subs), 3):
     txt = open(path).read()
     assert old in txt, f"{subs[k + 1]} not found in {fn}"
     open(path, "w").write(txt.replace(old, new))
-subprocess.run([B.HIPCC, *B.FLAGS, *os.environ.get("EXTRA_FLAGS", "").split(), "-o", out, *[os.path.join(csrc, s) for s in B.SOURCES]], check=True, cwd=csrc)
+sources = sorted(f for f in os.listdir(csrc) if f.endswith(".hip")) if rev else B.SOURCES  # an older commit: its own files
+subprocess.run([B.HIPCC, *B.FLAGS, *os.environ.get("EXTRA_FLAGS", "").split(), "-o", out, *[os.path.join(csrc, s) for s in sources]], check=True, cwd=csrc)
 shutil.rmtree(src_root)
 print(out)
