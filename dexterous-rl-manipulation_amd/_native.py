@@ -345,6 +345,24 @@ class PgRunsArgs(C.Structure):
                                           "run_table", "group_table", "contrast_table", "status")]
 
 
+# dxrl_pg_adam_step_ctl: the control struct, the state slots (enum dxrl_pg_opt_slot, with the word
+# type of each) and the columns of an iteration's row (enum dxrl_pg_opt_col), in order
+class PgLrControl(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("lr_nominal", "lr_min", "lr_max", "target_kl", "stop_factor",
+                                          "adapt_factor", "adapt_band")] + \
+               [(k, C.c_int32) for k in ("adapt", "pass_index", "last_epoch", "last_pass")] + [("calls", C.c_int64)]
+
+
+PG_OPT_SLOTS = (("applied", "i64"), ("skipped", "i64"), ("scale", "f64"), ("stopped", "i64"), ("stop_pass", "i64"),
+                ("iter_applied", "i64"), ("iter_skipped", "i64"), ("lr_first", "f64"), ("lr_last", "f64"),
+                ("kl_max", "f64"), ("kl_sum", "f64"), ("kl_rows", "f64"))
+PG_OPT_NAMED = len(PG_OPT_SLOTS)            # DXRL_PG_OPT_NAMED
+PG_OPT_SLOT_WORDS = 16                      # DXRL_PG_OPT_SLOT_WORDS
+PG_OPT_STATE_WORDS = 2 * PG_OPT_SLOT_WORDS  # DXRL_PG_OPT_STATE_WORDS
+PG_OPT_COLUMNS = ("lr", "lr_last", "updates", "skipped", "stop_pass", "kl_max", "kl_epoch", "lr_scale")
+PG_OPT_COLS = len(PG_OPT_COLUMNS)           # DXRL_PG_OPT_COLS
+
+
 # the structs added after tests/test_native_abi.py fixed its list: (C name, mirror), sized against
 # include/dxrl.h by the tests of the layers that use them
 LATER_STRUCTS = (("dxrl_pg_log_args", PgLogArgs), ("dxrl_pg_log_header", PgLogHeader),
@@ -432,6 +450,8 @@ _SIGS = {
                                          _P, _P, _P, _P]),
     "dxrl_pg_adam_step": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _I64, _F64, _F64, _F64, _F64, _I64, _F64, _P,
                                     _I32, _P, _P, _P]),
+    "dxrl_pg_adam_step_ctl": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _I64, _F64, _F64, _F64, _F64, _P, _I32, _P,
+                                        _P, _P, _I32, _I64, PgLrControl, _P, _P, _P]),
 }
 
 _lib = None

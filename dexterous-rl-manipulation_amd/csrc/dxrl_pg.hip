@@ -542,13 +542,15 @@ __device__ __forceinline__ double block_sum256(double s, double* red4) {
 // (thread t adds partial[t], partial[t + 256], ... in that order; the loads go out in batches of 8
 // ahead of their adds -- one L2 latency per batch, not per partial, for the ~2.6 k partials of
 // dxrl_pg_fused_pair_gnorm -- and the + 0.0 of a batch's tail leaves the sum's bits unchanged)
+// (kStride: the partials are one column of a row-major table, partial[k * kStride])
+template <int kStride = 1>
 __device__ __forceinline__ double block_sum_partials(const double* __restrict__ partial, int nb, double* red4) {
     constexpr int kB = 8;
     double s = 0.0;
     for (int k0 = threadIdx.x; k0 < nb; k0 += 256 * kB) {
         double v[kB];
 #pragma unroll
-        for (int u = 0; u < kB; ++u) v[u] = k0 + 256 * u < nb ? partial[k0 + 256 * u] : 0.0;
+        for (int u = 0; u < kB; ++u) v[u] = k0 + 256 * u < nb ? partial[(int64_t)(k0 + 256 * u) * kStride] : 0.0;
 #pragma unroll
         for (int u = 0; u < kB; ++u) s += v[u];
     }
@@ -825,25 +827,147 @@ struct AdamPackArgs {
     bf16* w;
 };
 
-__global__ __launch_bounds__(256) void k_adam_pack(AdamPackArgs a) {
-    __shared__ double red4[4];
-    const double g2 = block_sum_partials(a.partial, a.nb, red4);
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.gnorm2[0] = g2;
-    float scale = 1.0f;
-    if (a.max_norm > 0.0f) {
-        const float nrm = (float)sqrt(g2);
-        scale = nrm > a.max_norm ? a.max_norm / (nrm + 1e-6f) : 1.0f;
-    }
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= a.n) return;
+// The global-norm clip factor and the Adam update of one master element, stated once for both
+// optimiser-step kernels (k_adam's expressions).
+__device__ __forceinline__ float clip_scale(double g2, float max_norm) {
+    if (!(max_norm > 0.0f)) return 1.0f;
+    const float nrm = (float)sqrt(g2);
+    return nrm > max_norm ? max_norm / (nrm + 1e-6f) : 1.0f;
+}
+
+__device__ __forceinline__ void adam_pack_element(const AdamPackArgs& a, int64_t j, float scale, float lr, float bc1,
+                                                  float bc2) {
     const float gk = a.g[j] * scale;
     const float m = a.b1 * a.m1[j] + (1.0f - a.b1) * gk;
     const float v = a.b2 * a.m2[j] + (1.0f - a.b2) * gk * gk;
-    const float pn = a.p[j] - a.lr * (m / a.bc1) / (sqrtf(v / a.bc2) + a.eps);
+    const float pn = a.p[j] - lr * (m / bc1) / (sqrtf(v / bc2) + a.eps);
     a.po[j] = pn;
     a.m1o[j] = m;
     a.m2o[j] = v;
     pack_scatter(j, pn, a.w);
+}
+
+__global__ __launch_bounds__(256) void k_adam_pack(AdamPackArgs a) {
+    __shared__ double red4[4];
+    const double g2 = block_sum_partials(a.partial, a.nb, red4);
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.gnorm2[0] = g2;
+    const float scale = clip_scale(g2, a.max_norm);
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= a.n) return;
+    adam_pack_element(a, j, scale, a.lr, a.bc1, a.bc2);
+}
+
+// k_adam_pack with the step size decided on the device (dxrl_pg_adam_step_ctl; include/dxrl.h has
+// the rules).  Every workgroup finishes the pass's KL sum from the loss partials' column 3 in
+// block_sum_partials' fixed order and reads the same state slot, so all workgroups hold the same
+// decision bits with no grid-wide exchange; workgroup 0 alone writes the next state, into the
+// other slot (the slot a call reads is never the one it writes: the other workgroups of the launch
+// may still be reading it).  A stopped pass copies master and moments through and leaves the pack.
+struct AdamCtlArgs {
+    AdamPackArgs a;            // a.lr unused; a.bc1 / a.bc2: the host's corrections for t = calls
+    dxrl_pg_lr_control c;
+    double beta1, beta2;
+    const double* loss;        // f64 [loss_rows][4], column 3 = the pass's approx-KL sums
+    int loss_rows;
+    double rows;               // samples of the pass
+    const int64_t* rd;         // state slot read
+    int64_t* wr;               // state slot written
+    double* row;               // f64 [DXRL_PG_OPT_COLS] or null
+};
+
+__global__ __launch_bounds__(256) void k_adam_pack_ctl(AdamCtlArgs x) {
+    __shared__ double red4[4];
+    const AdamPackArgs& a = x.a;
+    const dxrl_pg_lr_control& c = x.c;
+    const double g2 = block_sum_partials(a.partial, a.nb, red4);
+    __syncthreads();  // red4 is reused
+    const double kl_sum = block_sum_partials<4>(x.loss + 3, x.loss_rows, red4);
+    const double* rdf = reinterpret_cast<const double*>(x.rd);
+    const bool first = c.pass_index == 0;
+    const int64_t applied = x.rd[DXRL_PG_OPT_APPLIED], skipped = x.rd[DXRL_PG_OPT_SKIPPED];
+    const double lr_scale = rdf[DXRL_PG_OPT_SCALE];
+    const double kl = kl_sum / x.rows;
+    bool stopped = !first && x.rd[DXRL_PG_OPT_STOPPED] != 0;
+    const bool stops = c.target_kl > 0.0 && !stopped && kl > c.stop_factor * c.target_kl;
+    stopped = stopped || stops;
+    double lr = c.lr_nominal * lr_scale;
+    lr = lr < c.lr_min ? c.lr_min : (lr > c.lr_max ? c.lr_max : lr);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.gnorm2[0] = g2;
+        double* wrf = reinterpret_cast<double*>(x.wr);
+        const int64_t it_applied = (first ? 0 : x.rd[DXRL_PG_OPT_ITER_APPLIED]) + (stopped ? 0 : 1);
+        const int64_t it_skipped = (first ? 0 : x.rd[DXRL_PG_OPT_ITER_SKIPPED]) + (stopped ? 1 : 0);
+        const int64_t stop_pass = stops ? (int64_t)c.pass_index : (first ? -1 : x.rd[DXRL_PG_OPT_STOP_PASS]);
+        double lr_first = first ? 0.0 : rdf[DXRL_PG_OPT_LR_FIRST], lr_last = first ? 0.0 : rdf[DXRL_PG_OPT_LR_LAST];
+        if (!stopped) {
+            if (it_applied == 1) lr_first = lr;
+            lr_last = lr;
+        }
+        const double kl_prev = rdf[DXRL_PG_OPT_KL_MAX];
+        const double kl_max = first || kl > kl_prev ? kl : kl_prev;
+        double acc_kl = first ? 0.0 : rdf[DXRL_PG_OPT_KL_SUM], acc_rows = first ? 0.0 : rdf[DXRL_PG_OPT_KL_ROWS];
+        if (c.last_epoch) {
+            acc_kl += kl_sum;
+            acc_rows += x.rows;
+        }
+        double next = lr_scale;
+        if (c.last_pass) {
+            const double kl_epoch = acc_rows > 0.0 ? acc_kl / acc_rows : 0.0;
+            if (c.adapt && c.target_kl > 0.0 && acc_rows > 0.0) {
+                if (kl_epoch > c.adapt_band * c.target_kl) next = next / c.adapt_factor;
+                else if (kl_epoch < c.target_kl / c.adapt_band) next = next * c.adapt_factor;
+            }
+            // lr_nominal * next kept inside [lr_min, lr_max]: the quotient, one ulp inwards when
+            // the product of the rounded quotient still lands outside
+            if (c.lr_nominal * next > c.lr_max) {
+                next = c.lr_max / c.lr_nominal;
+                if (c.lr_nominal * next > c.lr_max) next = nextafter(next, 0.0);
+            } else if (c.lr_nominal * next < c.lr_min) {
+                next = c.lr_min / c.lr_nominal;
+                if (c.lr_nominal * next < c.lr_min) next = nextafter(next, HUGE_VAL);
+            }
+            if (x.row) {
+                x.row[DXRL_PG_OPT_COL_LR] = lr_first;
+                x.row[DXRL_PG_OPT_COL_LR_LAST] = lr_last;
+                x.row[DXRL_PG_OPT_COL_UPDATES] = (double)it_applied;
+                x.row[DXRL_PG_OPT_COL_SKIPPED] = (double)it_skipped;
+                x.row[DXRL_PG_OPT_COL_STOP_PASS] = (double)stop_pass;
+                x.row[DXRL_PG_OPT_COL_KL_MAX] = kl_max;
+                x.row[DXRL_PG_OPT_COL_KL_EPOCH] = kl_epoch;
+                x.row[DXRL_PG_OPT_COL_LR_SCALE] = next;
+            }
+        }
+        x.wr[DXRL_PG_OPT_APPLIED] = applied + (stopped ? 0 : 1);
+        x.wr[DXRL_PG_OPT_SKIPPED] = skipped + (stopped ? 1 : 0);
+        wrf[DXRL_PG_OPT_SCALE] = next;
+        x.wr[DXRL_PG_OPT_STOPPED] = stopped ? 1 : 0;
+        x.wr[DXRL_PG_OPT_STOP_PASS] = stop_pass;
+        x.wr[DXRL_PG_OPT_ITER_APPLIED] = it_applied;
+        x.wr[DXRL_PG_OPT_ITER_SKIPPED] = it_skipped;
+        wrf[DXRL_PG_OPT_LR_FIRST] = lr_first;
+        wrf[DXRL_PG_OPT_LR_LAST] = lr_last;
+        wrf[DXRL_PG_OPT_KL_MAX] = kl_max;
+        wrf[DXRL_PG_OPT_KL_SUM] = acc_kl;
+        wrf[DXRL_PG_OPT_KL_ROWS] = acc_rows;
+        for (int k = DXRL_PG_OPT_NAMED; k < DXRL_PG_OPT_SLOT_WORDS; ++k) x.wr[k] = 0;
+    }
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= a.n) return;
+    if (stopped) {
+        a.po[j] = a.p[j];
+        a.m1o[j] = a.m1[j];
+        a.m2o[j] = a.m2[j];
+        return;
+    }
+    // Adam's t counts applied passes.  While no pass was ever skipped t is the host's call count
+    // and the host's corrections are used (the parent's bytes); afterwards 1 - beta^t in f64 here.
+    float bc1 = a.bc1, bc2 = a.bc2;
+    if (skipped != 0) {
+        const double t = (double)(applied + 1);
+        bc1 = (float)(1.0 - pow(x.beta1, t));
+        bc2 = (float)(1.0 - pow(x.beta2, t));
+    }
+    adam_pack_element(a, j, clip_scale(g2, a.max_norm), (float)lr, bc1, bc2);
 }
 
 static int reduce_to(const double* partial, int nb, double* out, int slot, hipStream_t st) {
@@ -1092,6 +1216,43 @@ int dxrl_pg_adam_step(int32_t device, const float* params, const float* grads, c
                    (float)max_norm, gnorm_partial, gnorm_blocks, gnorm2, static_cast<bf16*>(packed)};
     hipLaunchKernelGGL(k_adam_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), a);
     return launch_check("k_adam_pack");
+}
+
+int dxrl_pg_adam_step_ctl(int32_t device, const float* params, const float* grads, const float* m1, const float* m2,
+                          float* params_out, float* m1_out, float* m2_out, int64_t n, double beta1, double beta2,
+                          double eps, double max_norm, double* gnorm_partial, int32_t gnorm_blocks, double* gnorm2,
+                          void* packed, const double* loss_partial, int32_t loss_blocks, int64_t pass_rows,
+                          dxrl_pg_lr_control ctl, int64_t* state, double* row_out, void* stream) {
+    DXRL_REQUIRE(params && grads && m1 && m2 && params_out && m1_out && m2_out && gnorm_partial && gnorm2 && packed &&
+                     loss_partial && state && gnorm_blocks >= 0 && loss_blocks >= 1 && pass_rows >= 1,
+                 "bad adam_step_ctl arguments");
+    DXRL_REQUIRE(n == kParams, "adam_step_ctl: n must be the padded parameter count %lld", (long long)kParams);
+    DXRL_REQUIRE(params != params_out && m1 != m1_out && m2 != m2_out, "adam_step_ctl: outputs must not alias inputs");
+    DXRL_REQUIRE(ctl.calls >= 1 && ctl.pass_index >= 0, "adam_step_ctl: calls >= 1 and pass_index >= 0");
+    DXRL_REQUIRE(ctl.lr_nominal > 0.0 && ctl.lr_min > 0.0 && ctl.lr_min <= ctl.lr_max && ctl.target_kl >= 0.0 &&
+                     ctl.stop_factor > 0.0 && ctl.adapt_factor > 0.0 && ctl.adapt_band > 0.0,
+                 "adam_step_ctl: 0 < lr_nominal, 0 < lr_min <= lr_max, target_kl >= 0, positive factors");
+    DeviceGuard g(device);
+    hipStream_t st = as_stream(stream);
+    if (gnorm_blocks == 0) {  // dxrl_pg_optimizer_step's source of the norm: gnorm_partial is f64 [512] scratch
+        gnorm_blocks = 512;
+        hipLaunchKernelGGL(k_sumsq, dim3(gnorm_blocks), dim3(256), 0, st, grads, n, gnorm_partial);
+        if (int rc = launch_check("k_sumsq")) return rc;
+    }
+    AdamCtlArgs x{};
+    x.a = AdamPackArgs{params, grads, m1, m2, params_out, m1_out, m2_out, n, 0.0f, (float)beta1, (float)beta2,
+                       (float)eps, (float)(1.0 - pow(beta1, (double)ctl.calls)),
+                       (float)(1.0 - pow(beta2, (double)ctl.calls)), (float)max_norm, gnorm_partial, gnorm_blocks,
+                       gnorm2, static_cast<bf16*>(packed)};
+    x.c = ctl;
+    x.beta1 = beta1, x.beta2 = beta2;
+    x.loss = loss_partial, x.loss_rows = loss_blocks, x.rows = (double)pass_rows;
+    // call c reads slot (c - 1) & 1 and writes slot c & 1
+    x.rd = state + ((ctl.calls - 1) & 1) * DXRL_PG_OPT_SLOT_WORDS;
+    x.wr = state + (ctl.calls & 1) * DXRL_PG_OPT_SLOT_WORDS;
+    x.row = ctl.last_pass ? row_out : nullptr;
+    hipLaunchKernelGGL(k_adam_pack_ctl, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x);
+    return launch_check("k_adam_pack_ctl");
 }
 
 int dxrl_pg_adam(int32_t device, float* params, const float* grads, float* m1, float* m2, int64_t n, double lr,

@@ -16,6 +16,14 @@
                        first-three x first-three combinations; at most 16 levels).  --val-keep-best may
                        then name a score over the levels: worst_success_rate, mean_success_rate,
                        mean_noisy_success_rate, worst_mean_return
+  --lr-schedule S --lr-final LR
+                       linear or cosine learning-rate schedule from the trainer's lr to LR over
+                       --iterations iterations (TrainerConfig.lr_schedule)
+  --target-kl KL [--kl-adaptive] [--no-kl-stop] [--lr-min LR] [--lr-max LR]
+                       step-size control on the device: skip the rest of an iteration's PPO updates once a
+                       pass's KL exceeds 1.5 KL, and / or steer the learning rate towards KL inside
+                       [--lr-min, --lr-max]; needs --epochs x --minibatches > 1, one rank.  The log gains
+                       its optimizer table
   --gpus N [--backend nccl|gloo]
                        a sharded run, one rank per GPU: --envs is the global count, split equally; every
                        rank trains its shard (global env ids rank * n ..) with fit(merge_ranks=True), so
@@ -81,6 +89,14 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--epochs", type=int, default=1)
     p.add_argument("--minibatches", type=int, default=1)
     p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--lr-schedule", choices=("constant", "linear", "cosine"), default="constant")
+    p.add_argument("--lr-final", type=float, default=None, metavar="LR",
+                   help="the schedule's learning rate after --iterations iterations")
+    p.add_argument("--target-kl", type=float, default=None, metavar="KL")
+    p.add_argument("--kl-adaptive", action="store_true", help="steer the learning rate towards --target-kl")
+    p.add_argument("--no-kl-stop", action="store_true", help="with --target-kl: adapt only, never skip updates")
+    p.add_argument("--lr-min", type=float, default=None, metavar="LR")
+    p.add_argument("--lr-max", type=float, default=None, metavar="LR")
     p.add_argument("--device", default=None)
     p.add_argument("--gpus", type=int, default=1, metavar="N", help="ranks of a sharded run, one per GPU")
     p.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
@@ -96,6 +112,34 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(f"--envs {total} does not split equally over --gpus {a.gpus}")
     if a.iterations < 0:
         p.error("--iterations must be >= 0")
+    a.lr_control = {}  # the TrainerConfig fields of the step-size flags (empty: none given)
+    if a.lr_schedule != "constant":
+        if a.lr_final is None:
+            p.error(f"--lr-schedule {a.lr_schedule} needs --lr-final")
+        a.lr_control.update(lr_schedule=a.lr_schedule, lr_final=a.lr_final,
+                            lr_schedule_iterations=max(1, a.iterations))
+    elif a.lr_final is not None:
+        p.error("--lr-final needs --lr-schedule linear or cosine")
+    if a.target_kl is not None:
+        a.lr_control.update(target_kl=a.target_kl, kl_adaptive=a.kl_adaptive, kl_stop=not a.no_kl_stop)
+    elif a.kl_adaptive or a.no_kl_stop:
+        p.error("--kl-adaptive / --no-kl-stop need --target-kl")
+    for flag, value in (("lr_min", a.lr_min), ("lr_max", a.lr_max)):
+        if value is not None:
+            if not a.lr_control:
+                p.error("--lr-min / --lr-max need --lr-schedule or --target-kl")
+            a.lr_control[flag] = value
+    if a.lr_control:
+        if a.gpus > 1:
+            p.error("step-size control (--lr-schedule / --target-kl) runs on one rank: --gpus 1")
+        if a.resume is not None:
+            p.error("a --resume run keeps the step-size settings of its checkpoint")
+        from .lr_control import validate_lr_control
+        from .trainer import TrainerConfig
+        try:
+            validate_lr_control(TrainerConfig(epochs=a.epochs, minibatches=a.minibatches, **a.lr_control))
+        except ValueError as e:
+            p.error(str(e))
     if a.converge is not None:
         col, w, thr = a.converge
         if col not in _SCORE_COLUMNS:
@@ -152,7 +196,7 @@ def _build(a, fresh: bool, rank: int = 0, world: int = 1, group=None):
     from .envs import VecEnv
     from .experiments import CurriculumConfig
     from .trainer import PGTrainer, TrainerConfig
-    kw = dict(horizon=a.horizon, epochs=a.epochs, minibatches=a.minibatches, max_steps=a.max_steps)
+    kw = dict(horizon=a.horizon, epochs=a.epochs, minibatches=a.minibatches, max_steps=a.max_steps, **a.lr_control)
     if a.config is None:
         w = workloads.WORKLOADS[a.config_name]
         n = (a.envs or w["envs"]) // world

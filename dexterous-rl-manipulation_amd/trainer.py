@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import lr_control
 from .distributed import all_gather_into_, all_reduce_sum_, gather_adv_moments_, global_count, loss_scales
 from .envs import VecEnv
 
@@ -121,6 +122,27 @@ class TrainerConfig:
     # much for the critic when epochs x minibatches == 1 (else its store would cost more than the
     # first minibatch pass saves)
     reuse_h2: bool = True
+    # step-size control on the device (lr_control.py, dxrl_pg_adam_step_ctl): with a non-constant
+    # schedule or a target_kl every optimiser step is the controlled launch, which decides the
+    # learning rate, Adam's t and whether the pass is applied from the pass's approx-KL and a
+    # device state block -- no host read.  The defaults leave the trainer's launches as they are.
+    # lr_schedule: lr -> lr_final over lr_schedule_iterations iterations, then held.
+    # target_kl: with kl_stop the iteration's remaining Adam steps are skipped (copied through)
+    # once a pass's KL exceeds kl_stop_factor x target_kl; with kl_adaptive the learning rate is
+    # lr_nominal x scale, scale divided / multiplied by kl_adapt_factor once per iteration when the
+    # last epoch's KL is above kl_adapt_band x target_kl / below target_kl / kl_adapt_band, and
+    # lr_nominal x scale kept inside [lr_min, lr_max].
+    lr_schedule: str = "constant"            # "constant" | "linear" | "cosine"
+    lr_final: Optional[float] = None
+    lr_schedule_iterations: Optional[int] = None
+    target_kl: Optional[float] = None
+    kl_stop: bool = True
+    kl_stop_factor: float = 1.5
+    kl_adaptive: bool = False
+    kl_adapt_factor: float = 1.5
+    kl_adapt_band: float = 2.0
+    lr_min: float = 1e-6
+    lr_max: float = 1e-2
 
 
 def minibatch_bounds(M: int, B: int, round_samples: int):
@@ -174,6 +196,13 @@ class PGTrainer:
         # collectives run with several ranks or with an explicit process group (a world-1 group
         # executes the same RCCL calls: bench.py --dist, tests/test_gpu_rccl.py)
         self.collective = process_group is not None or world_size > 1
+        lr_control.validate_lr_control(cfg)
+        self.lr_control = lr_control.control_enabled(cfg)  # optimizer_step() is dxrl_pg_adam_step_ctl
+        if self.lr_control and self.collective:
+            raise ValueError("step-size control (lr_schedule / target_kl) runs on one rank: each rank's KL is its own "
+                             "shard's, so the ranks would decide differently and their weights diverge.  The missing "
+                             "piece is one all-reduce of (kl_sum, rows) over the ranks before the optimiser step, "
+                             "the KL all-reduce, which is not built")
         # Exchanges that overlap compute (collective mode): the advantage-moment all-gather runs
         # beside the critic's train pass (which does not read the normalisation), the critic
         # half of the gradient all-reduce beside the actor's, the scheduler's code exchange
@@ -255,6 +284,15 @@ class PGTrainer:
             self.splits = min(self.splits, self.learner_cus)
         self._kpartial = None  # [splits + 16][256][288] f32, allocated on first use (kpartial)
         self.gnorm2 = torch.zeros(1, dtype=torch.float64, device=d)
+        # step-size control: the device state block (two slots, _native.PG_OPT_SLOTS), the last
+        # iteration's row, and where the iteration's last step writes its row (fit() points it
+        # into its table; None: opt_row)
+        self.opt_state = self.opt_row = self._opt_row_target = None
+        if self.lr_control:
+            self.opt_state = torch.zeros(N.PG_OPT_STATE_WORDS, dtype=torch.int64, device=d)
+            self.opt_state.view(torch.float64)[[k for k, (nm, _) in enumerate(N.PG_OPT_SLOTS) if nm == "scale"]] = 1.0
+            self.opt_state[[k for k, (nm, _) in enumerate(N.PG_OPT_SLOTS) if nm == "stop_pass"]] = -1
+            self.opt_row = torch.zeros(N.PG_OPT_COLS, dtype=torch.float64, device=d)
         tr_, pf_ = C.c_int32(), C.c_int64()
         N.call("dxrl_pg_fused_sizes", C.byref(tr_), C.byref(pf_))
         # up to two learner workgroups per CU (64-sample tiles); the library clamps to its geometry
@@ -484,11 +522,13 @@ class PGTrainer:
         c = self.cfg
         bounds = self.minibatch_bounds()
         rng = np.random.default_rng([int(c.seed), self.iteration_index])
-        for _ in range(c.epochs):
-            for k in rng.permutation(c.minibatches):
+        last = c.epochs * c.minibatches - 1
+        for e in range(c.epochs):
+            for i, k in enumerate(rng.permutation(c.minibatches)):
                 self._mb = (bounds[k], bounds[k + 1] - bounds[k])
                 self.train_passes()
-                self.optimizer_step()
+                u = e * c.minibatches + i
+                self.optimizer_step(pass_index=u, last_epoch=e == c.epochs - 1, last_pass=u == last)
         self._mb = (0, self.M)
 
     def train_passes(self):
@@ -570,10 +610,15 @@ class PGTrainer:
             self._gemm(self.dH2, H, self._bf(f"W2{net}T"), H, M, H, H, gate=H1, ldg=HX, Crm=self.dH1, ldc=H)
             self._wgrad(self.dH1, H, H, self.obs_rm, IN, IN, self.block(f"W1{net}", G))
 
-    def optimizer_step(self):
+    def optimizer_step(self, pass_index: int = 0, last_epoch: bool = True, last_pass: bool = True):
         """Gradient all-reduce (collective mode), then dxrl_pg_optimizer_step: grad-norm partials
         + one clipped-Adam-and-pack launch writing the next master / moments into the spare
-        buffers, which then become current (params / m1 / m2 are swapped, not copied)."""
+        buffers, which then become current (params / m1 / m2 are swapped, not copied).
+
+        With step-size control (cfg.lr_schedule / cfg.target_kl) the launch is
+        dxrl_pg_adam_step_ctl on either source of the norm: pass_index within the iteration and the
+        last_epoch / last_pass flags are ppo_updates()'s; a single-update iteration is pass 0 with
+        both set.  A pass the device skips leaves its inputs in the swapped-in buffers."""
         c = self.cfg
         if self._grads_pending:  # critic half already in flight on the comm stream
             self._allreduce(self.grads[:OFF["W1c"]])
@@ -584,7 +629,9 @@ class PGTrainer:
         if self._spare is None:
             self._spare = tuple(torch.empty_like(t) for t in (self.params, self.m1, self.m2))
         po, m1o, m2o = self._spare
-        if self._gn_blocks:  # one rank: the paired reduction left the norm's partials (no k_sumsq)
+        if self.lr_control:
+            self._controlled_step(po, m1o, m2o, int(pass_index), bool(last_epoch), bool(last_pass))
+        elif self._gn_blocks:  # one rank: the paired reduction left the norm's partials (no k_sumsq)
             N.call("dxrl_pg_adam_step", self.dev.index, N.ptr(self.params), N.ptr(self.grads), N.ptr(self.m1),
                    N.ptr(self.m2), N.ptr(po), N.ptr(m1o), N.ptr(m2o), NPARAMS, c.lr, c.betas[0], c.betas[1],
                    c.adam_eps, self.step_count, c.max_grad_norm, N.ptr(self.gn_partial), self._gn_blocks,
@@ -598,6 +645,38 @@ class PGTrainer:
         self._spare = (self.params, self.m1, self.m2)
         self.params, self.m1, self.m2 = po, m1o, m2o
         self._h2a_fresh = self._h2c_fresh = False  # new weights: the stored activations are stale
+
+    def _controlled_step(self, po, m1o, m2o, pass_index, last_epoch, last_pass):
+        c = self.cfg
+        k = N.PgLrControl()
+        k.lr_nominal = lr_control.lr_nominal(c, self.iteration_index)
+        k.lr_min, k.lr_max = c.lr_min, c.lr_max
+        k.target_kl = 0.0 if c.target_kl is None else c.target_kl
+        k.stop_factor = c.kl_stop_factor if c.kl_stop else math.inf
+        k.adapt, k.adapt_factor, k.adapt_band = int(c.kl_adaptive), c.kl_adapt_factor, c.kl_adapt_band
+        k.pass_index, k.last_epoch, k.last_pass, k.calls = pass_index, int(last_epoch), int(last_pass), self.step_count
+        loss = self.fused_loss if c.fused else self.loss_partial
+        rows = self._loss_rows if c.fused else self.M
+        # the pair's norm partials, or (0 blocks) the 512-partial scratch a k_sumsq launch fills
+        gn = self.gn_partial if self._gn_blocks else self.partial
+        row = self.opt_row if self._opt_row_target is None else self._opt_row_target
+        N.call("dxrl_pg_adam_step_ctl", self.dev.index, N.ptr(self.params), N.ptr(self.grads), N.ptr(self.m1),
+               N.ptr(self.m2), N.ptr(po), N.ptr(m1o), N.ptr(m2o), NPARAMS, c.betas[0], c.betas[1], c.adam_eps,
+               c.max_grad_norm, N.ptr(gn), self._gn_blocks, N.ptr(self.gnorm2), N.ptr(self.packed), N.ptr(loss),
+               loss.shape[0], rows, k, N.ptr(self.opt_state), N.ptr(row), self._s())
+        self._gn_blocks = 0
+
+    def optimizer_state(self) -> Dict[str, float]:
+        """The device's step-size state after the last optimiser step (one small read):
+        applied / skipped passes so far (applied is Adam's t), the KL-adaptive scale, and whether
+        the current iteration is stopped.  step_count stays the number of calls."""
+        if not self.lr_control:
+            raise ValueError("this trainer runs without step-size control (cfg.lr_schedule / cfg.target_kl)")
+        slot = self.opt_state.view(2, N.PG_OPT_SLOT_WORDS)[self.step_count & 1].cpu()
+        f = slot.view(torch.float64)
+        out = {nm: (float(f[k]) if ty == "f64" else int(slot[k])) for k, (nm, ty) in enumerate(N.PG_OPT_SLOTS)}
+        out["stopped"] = bool(out["stopped"])
+        return out
 
     def attach_curriculum(self, scheduler):
         """Host-side CurriculumScheduler (experiments/curriculum_scheduler.py) fed with every

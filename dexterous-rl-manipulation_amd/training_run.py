@@ -37,6 +37,12 @@ numbers -- the class transitions against the baseline.
 ``dxrl_pg_log_rank_pack`` reduces the rank's tape to one record, the records are all-gathered, and
 ``dxrl_pg_log_row_world`` finishes the row from all of them, so every rank holds the same table,
 header and best parameters; ``log.ranks`` keeps the records, and each rank checkpoints its own file.
+
+On a trainer with step-size control (``TrainerConfig.lr_schedule`` / ``target_kl``) the run keeps a
+third device table, ``log.optimizer``: the last ``dxrl_pg_adam_step_ctl`` launch of every iteration
+writes the iteration's row (learning rate, updates applied / skipped, stop pass, KLs, next scale)
+straight into it.  The table and the trainer's device state block ride the JSON and the checkpoint
+as optional entries.
 """
 from __future__ import annotations
 
@@ -61,6 +67,8 @@ _HEADER_BYTES = C.sizeof(N.PgLogHeader)
 RANK_COLUMNS = N.PG_LOG_RANK_COLUMNS    # the named entries of a rank record (fit(merge_ranks=True))
 RANK_DOUBLES = N.PG_LOG_RANK_DOUBLES
 _MIN_CAP = 256
+OPT_COLUMNS = N.PG_OPT_COLUMNS          # the named columns of log.optimizer (step-size control)
+OPT_COLS = N.PG_OPT_COLS
 VAL_COLUMNS = N.PG_VAL_COLUMNS
 VAL_COLS = N.PG_VAL_COLS
 _VAL_SCORE_COLUMNS = VAL_COLUMNS[:N.PG_VAL_IS_BEST]  # columns the validation keep-best may read
@@ -97,6 +105,33 @@ def column_index(name: Optional[str], what: str) -> int:
     return COLUMNS.index(name)
 
 
+# ====================================================================== OptimizerLog
+class OptimizerLog:
+    """The step-size rows of a run on a trainer with step-size control: f64 [rows][8], one row per
+    logged iteration (``column(name)`` / ``log.optimizer["lr"]``, names in OPT_COLUMNS): ``lr`` /
+    ``lr_last`` the learning rate of the iteration's first / last applied pass (0: none applied),
+    ``updates`` / ``skipped`` its passes applied / copied through, ``stop_pass`` the pass the KL
+    stop hit (-1: none), ``kl_max`` the largest pass KL, ``kl_epoch`` the last epoch's KL over
+    every sample, ``lr_scale`` the KL-adaptive scale the next iteration starts with."""
+
+    def __init__(self, table):
+        self.table = np.array(table, dtype=np.float64).reshape(-1, OPT_COLS)
+
+    def column(self, name: str) -> np.ndarray:
+        if name not in OPT_COLUMNS:
+            raise ValueError(f"an optimizer column is one of {list(OPT_COLUMNS)}, got {name!r}")
+        return self.table[:, OPT_COLUMNS.index(name)]
+
+    __getitem__ = column
+
+    @property
+    def columns(self) -> Dict[str, np.ndarray]:
+        return {name: self.table[:, k] for k, name in enumerate(OPT_COLUMNS)}
+
+    def __len__(self) -> int:
+        return self.table.shape[0]
+
+
 # ====================================================================== TrainingLog
 class TrainingLog:
     """The learning curve of a run: one row per iteration, named NumPy columns
@@ -109,12 +144,16 @@ class TrainingLog:
 
     ``ranks``: f64 [rows][world][RANK_DOUBLES], the ranks' records every row was finished from
     (``rank_column(name)`` -> [rows][world], names in RANK_COLUMNS), for a run logged with
-    ``fit(merge_ranks=True)``; None otherwise."""
+    ``fit(merge_ranks=True)``; None otherwise.
+
+    ``optimizer``: the ``OptimizerLog`` of a run on a trainer with step-size control; None
+    otherwise."""
 
     def __init__(self, table=None, header: Optional[Dict[str, Any]] = None, window: Optional[int] = None,
                  settings: Optional[Dict[str, Any]] = None, _pending=None, validation: "Optional[ValidationLog]" = None,
-                 ranks=None):
+                 ranks=None, optimizer=None):
         self._pending = _pending
+        self._optimizer = None if optimizer is None else OptimizerLog(optimizer)
         self._ranks = None if ranks is None else np.array(ranks, dtype=np.float64)
         if self._ranks is not None and (self._ranks.ndim != 3 or self._ranks.shape[2] != RANK_DOUBLES):
             raise ValueError(f"ranks must be [rows][world][{RANK_DOUBLES}], got shape {self._ranks.shape}")
@@ -127,8 +166,10 @@ class TrainingLog:
     # -- lazy fill (fit enqueued the copy; the first read waits for it)
     def _resolve(self):
         if self._pending is not None:
-            event, host_table, host_header, rows, host_ranks = self._pending
+            event, host_table, host_header, rows, host_ranks, host_opt = self._pending
             event.synchronize()
+            if host_opt is not None:
+                self._optimizer = OptimizerLog(host_opt[:rows].numpy().copy())
             self._table = host_table[:rows].numpy().copy()
             self._header = header_dict(host_header.numpy())
             if host_ranks is not None:
@@ -150,6 +191,12 @@ class TrainingLog:
         """f64 [rows][world][RANK_DOUBLES], or None for a run logged without merge_ranks."""
         self._resolve()
         return self._ranks
+
+    @property
+    def optimizer(self) -> Optional[OptimizerLog]:
+        """The step-size rows (OptimizerLog), or None for a trainer without step-size control."""
+        self._resolve()
+        return self._optimizer
 
     def rank_column(self, name: str) -> np.ndarray:
         """[rows][world]: one entry of the ranks' records."""
@@ -220,6 +267,9 @@ class TrainingLog:
         if self.ranks is not None:  # likewise: a run without merge_ranks serialises as it always did
             out["rank_columns"] = list(RANK_COLUMNS)
             out["ranks"] = [[[_enc(x) for x in rec] for rec in row] for row in self.ranks.tolist()]
+        if self.optimizer is not None:  # likewise: a run without step-size control
+            out["optimizer_columns"] = list(OPT_COLUMNS)
+            out["optimizer"] = [[_enc(x) for x in row] for row in self.optimizer.table.tolist()]
         return out
 
     @classmethod
@@ -236,8 +286,13 @@ class TrainingLog:
                 raise ValueError("not a training log with this build's rank columns")
             ranks = np.array([[[_dec(x) for x in rec] for rec in row] for row in d["ranks"]], dtype=np.float64)
             ranks = ranks.reshape(len(d["rows"]), -1, RANK_DOUBLES)
+        opt = None
+        if d.get("optimizer") is not None:  # absent in runs without step-size control and in older files
+            if list(d.get("optimizer_columns", [])) != list(OPT_COLUMNS):
+                raise ValueError("not a training log with this build's optimizer columns")
+            opt = np.array([[_dec(x) for x in row] for row in d["optimizer"]], dtype=np.float64).reshape(-1, OPT_COLS)
         return cls(table, {k: _dec(v) for k, v in d["header"].items()}, d.get("window"), d.get("settings"),
-                   validation=val, ranks=ranks)
+                   validation=val, ranks=ranks, optimizer=opt)
 
     def save(self, path):
         with open(path, "w") as f:
@@ -996,6 +1051,9 @@ class _RunState:
         # fit(merge_ranks=True): this rank's record, the gathered records and the per-rank log
         self.merged = False
         self.record = self.records_all = self.rank_log = self.host_rank_log = None
+        # a trainer with step-size control: the optimizer table, one row per logged iteration
+        self.controlled = bool(getattr(tr, "lr_control", False))
+        self.opt_table = self.host_opt_table = None
         self.reserve(tr, cap)
 
     def merge_ranks(self, tr):
@@ -1025,6 +1083,12 @@ class _RunState:
             table[:self.rows].copy_(self.table[:self.rows])
         self.table, self.cap = table, cap
         self.host_table = torch.zeros(cap, COLS, dtype=torch.float64).pin_memory()
+        if self.controlled:
+            opt = torch.zeros(cap, OPT_COLS, dtype=torch.float64, device=tr.dev)
+            if self.opt_table is not None and self.rows:
+                opt[:self.rows].copy_(self.opt_table[:self.rows])
+            self.opt_table = opt
+            self.host_opt_table = torch.zeros(cap, OPT_COLS, dtype=torch.float64).pin_memory()
         if self.merged:
             self._rank_tables(tr, cap)
 
@@ -1161,7 +1225,12 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
                        score_table=val_table)
 
     for k in range(iterations):
-        tr.iteration()
+        if st.controlled:  # the iteration's last optimiser launch writes its row into the table
+            tr._opt_row_target = st.opt_table[st.rows]
+        try:
+            tr.iteration()
+        finally:
+            tr._opt_row_target = None
         log_iteration(tr, st, score_col, min_episodes, conv_col, window, threshold, merge_ranks)
         validated = val is not None and (st.rows % every == 0 or k == iterations - 1)
         if validated:
@@ -1188,11 +1257,14 @@ def training_log(tr) -> TrainingLog:
         st.host_table[:st.rows].copy_(st.table[:st.rows], non_blocking=True)
     if st.merged and st.rows:
         st.host_rank_log[:st.rows].copy_(st.rank_log[:st.rows], non_blocking=True)
+    if st.controlled and st.rows:
+        st.host_opt_table[:st.rows].copy_(st.opt_table[:st.rows], non_blocking=True)
     st.host_header.copy_(st.header, non_blocking=True)
     st.event.record(torch.cuda.current_stream(tr.dev))
     log = TrainingLog(window=st.window, settings=st.settings,
                       _pending=(st.event, st.host_table, st.host_header, st.rows,
-                                st.host_rank_log if st.merged else None), validation=validation_log(tr))
+                                st.host_rank_log if st.merged else None,
+                                st.host_opt_table if st.controlled else None), validation=validation_log(tr))
     st.last_log = weakref.ref(log)
     return log
 
@@ -1268,15 +1340,19 @@ def save_checkpoint(tr, path):
               "env_state": host(env.state)}
     meta: Dict[str, Any] = {
         "step_count": int(tr.step_count), "iteration_index": int(tr.iteration_index),
-        "trainer_config": dataclasses.asdict(tr.cfg),
+        "trainer_config": _trainer_config_state(tr.cfg),
         "env": env_fingerprint(env), "max_episode_steps": int(env.max_episode_steps),
         "curriculum_configs": [_config_state(c) for c in env.curriculum_configs],
         "scheduler": tr.scheduler.get_state() if tr.scheduler is not None else None,
         "log": None,
     }
+    if tr.lr_control:  # optional entry: a trainer without step-size control writes the file it always did
+        arrays["opt_state"] = host(tr.opt_state)
     if st is not None:
         arrays.update(log_table=host(st.table[:st.rows]), log_header=host(st.header),
                       best_params=host(st.best_params))
+        if st.controlled:
+            arrays["log_optimizer"] = host(st.opt_table[:st.rows])
         meta["log"] = {"rows": st.rows, "env_steps": st.env_steps, "window": st.window, "settings": st.settings}
         if st.merged:  # optional entries: a run without merge_ranks writes the file it always did
             arrays["log_ranks"] = host(st.rank_log[:st.rows])
@@ -1295,6 +1371,15 @@ def save_checkpoint(tr, path):
     if tr.collective:  # likewise optional: a one-rank trainer writes the file it always did
         meta["world"], meta["rank"] = int(tr.world), _rank_of(tr)
     write_checkpoint(path, arrays, meta)
+
+
+def _trainer_config_state(cfg) -> Dict[str, Any]:
+    """The checkpoint's trainer_config: the dataclass's fields, without the step-size fields that
+    sit at their defaults (a trainer without step-size control writes the entry it always did;
+    a missing field loads as its default)."""
+    from .lr_control import CONFIG_DEFAULTS
+    d = dataclasses.asdict(cfg)
+    return {k: v for k, v in d.items() if k not in CONFIG_DEFAULTS or v != CONFIG_DEFAULTS[k]}
 
 
 def validation_arrays(table, header, best_params, objects, levels=None, robust=None, paired=None,
@@ -1376,6 +1461,8 @@ def load_checkpoint(cls, path, env, process_group=None, world_size: int = 1):
     put(tr.packed, "packed")
     tr._h2a_fresh = tr._h2c_fresh = False
     tr.step_count, tr.iteration_index = int(meta["step_count"]), int(meta["iteration_index"])
+    if tr.lr_control:
+        put(tr.opt_state, "opt_state")
     if meta["log"] is not None:
         lg = meta["log"]
         st = run_state(tr, int(lg["rows"]))
@@ -1385,6 +1472,8 @@ def load_checkpoint(cls, path, env, process_group=None, world_size: int = 1):
             put(st.table[:st.rows], "log_table")
         put(st.header, "log_header")
         put(st.best_params, "best_params")
+        if st.controlled and st.rows:
+            put(st.opt_table[:st.rows], "log_optimizer")
         if lg.get("merge_ranks"):  # absent in runs without merge_ranks and in older files
             st.merge_ranks(tr)
             if st.rows:

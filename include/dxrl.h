@@ -544,6 +544,82 @@ int dxrl_pg_adam_step(int32_t device, const float* params, const float* grads, c
                       double eps, int64_t step, double max_norm, const double* gnorm_partial, int32_t gnorm_blocks,
                       double* gnorm2, void* packed, void* stream);
 
+/* ---- step-size control on the device (PPO: LR schedule, KL stop, KL-adaptive LR) --------
+ * dxrl_pg_adam_step_ctl is dxrl_pg_adam_step / dxrl_pg_optimizer_step with the learning rate,
+ * Adam's t and whether the pass is applied at all decided inside the one optimiser launch, from
+ * the pass's approx-KL sums (column 3 of the learner's loss partials) and a device state block.
+ * No reference counterpart (policies/simple_learner.py has one fixed learning rate).
+ *
+ * State: 2 slots of DXRL_PG_OPT_SLOT_WORDS 64-bit words (int64 or f64 per slot enum below).  Call
+ * number c (ctl.calls, 1-based, the host's count) reads slot (c - 1) & 1 and writes slot c & 1.
+ * A fresh block: all zero but DXRL_PG_OPT_SCALE = 1.0 and DXRL_PG_OPT_STOP_PASS = -1 in slot 0.
+ *
+ * Pass u of an iteration, kl = (sum of column 3) / pass_rows:
+ *   pass_index == 0 clears the iteration's stop flag and accumulators;
+ *   target_kl > 0, not yet stopped and kl > stop_factor * target_kl (strict): stopped at u;
+ *   stopped: *_out = inputs bit for bit, pack untouched, the pass counts as skipped;
+ *   else lr = clamp(lr_nominal * scale, lr_min, lr_max) (f64, then f32), Adam with
+ *   t = applied + 1 (skipped passes do not advance t; while no pass was ever skipped the bias
+ *   corrections are the host's for t = calls, dxrl_pg_adam_step's bytes; afterwards
+ *   1 - pow(beta, t) in f64 on the device);
+ *   last_epoch passes add (KL sum, pass_rows) to the epoch accumulators, applied or not;
+ *   last_pass: kl_epoch = accumulated sum / rows (0 with no rows); with adapt and target_kl > 0:
+ *   kl_epoch > adapt_band * target_kl: scale /= adapt_factor, else kl_epoch < target_kl /
+ *   adapt_band: scale *= adapt_factor; scale is then moved so that lr_nominal * scale is inside
+ *   [lr_min, lr_max]; the row (enum dxrl_pg_opt_col) is written to row_out when it is non-null.
+ * The new scale holds from the next call on.  gnorm2 is written by every call. */
+typedef struct dxrl_pg_lr_control {
+    double lr_nominal, lr_min, lr_max;
+    double target_kl;      /* 0: no KL rule                                     */
+    double stop_factor;    /* +inf: adapt without stopping                      */
+    double adapt_factor, adapt_band;
+    int32_t adapt;         /* 0 / 1                                             */
+    int32_t pass_index;    /* within the iteration                              */
+    int32_t last_epoch;    /* 0 / 1: a pass of the iteration's last epoch       */
+    int32_t last_pass;     /* 0 / 1: the iteration's last pass                  */
+    int64_t calls;         /* the host's call count, this call included (>= 1)  */
+} dxrl_pg_lr_control;
+
+enum dxrl_pg_opt_slot {
+    DXRL_PG_OPT_APPLIED = 0,      /* i64 passes applied so far (Adam's t)            */
+    DXRL_PG_OPT_SKIPPED,          /* i64 passes skipped so far                       */
+    DXRL_PG_OPT_SCALE,            /* f64 the KL-adaptive factor on lr_nominal        */
+    DXRL_PG_OPT_STOPPED,          /* i64 0 / 1: this iteration is stopped            */
+    DXRL_PG_OPT_STOP_PASS,        /* i64 the pass it stopped at, -1: none            */
+    DXRL_PG_OPT_ITER_APPLIED,     /* i64 passes applied in this iteration            */
+    DXRL_PG_OPT_ITER_SKIPPED,     /* i64 passes skipped in this iteration            */
+    DXRL_PG_OPT_LR_FIRST,         /* f64 lr of the iteration's first applied pass, 0 */
+    DXRL_PG_OPT_LR_LAST,          /* f64 lr of its last applied pass, 0              */
+    DXRL_PG_OPT_KL_MAX,           /* f64 largest pass KL of the iteration            */
+    DXRL_PG_OPT_KL_SUM,           /* f64 KL sums of the last epoch's passes          */
+    DXRL_PG_OPT_KL_ROWS,          /* f64 samples of the last epoch's passes          */
+    DXRL_PG_OPT_NAMED
+};
+#define DXRL_PG_OPT_SLOT_WORDS 16
+#define DXRL_PG_OPT_STATE_WORDS (2 * DXRL_PG_OPT_SLOT_WORDS)
+
+enum dxrl_pg_opt_col {            /* the row of an iteration, f64 [DXRL_PG_OPT_COLS] */
+    DXRL_PG_OPT_COL_LR = 0,       /* lr of the first applied pass (0: none applied)  */
+    DXRL_PG_OPT_COL_LR_LAST,      /* lr of the last applied pass                     */
+    DXRL_PG_OPT_COL_UPDATES,      /* passes applied                                  */
+    DXRL_PG_OPT_COL_SKIPPED,      /* passes skipped                                  */
+    DXRL_PG_OPT_COL_STOP_PASS,    /* -1: no stop                                     */
+    DXRL_PG_OPT_COL_KL_MAX,
+    DXRL_PG_OPT_COL_KL_EPOCH,
+    DXRL_PG_OPT_COL_LR_SCALE,     /* the scale of the next iteration                 */
+    DXRL_PG_OPT_COLS
+};
+
+/* gnorm_blocks > 0: gnorm_partial holds that many f64 partials of the squared grad norm
+ * (dxrl_pg_fused_pair_gnorm's); gnorm_blocks == 0: gnorm_partial is f64 [512] scratch that a
+ * k_sumsq launch fills first, as in dxrl_pg_optimizer_step.  loss_partial: f64 [loss_blocks][4];
+ * state: [DXRL_PG_OPT_STATE_WORDS]; row_out: f64 [DXRL_PG_OPT_COLS] or NULL. */
+int dxrl_pg_adam_step_ctl(int32_t device, const float* params, const float* grads, const float* m1, const float* m2,
+                          float* params_out, float* m1_out, float* m2_out, int64_t n, double beta1, double beta2,
+                          double eps, double max_norm, double* gnorm_partial, int32_t gnorm_blocks, double* gnorm2,
+                          void* packed, const double* loss_partial, int32_t loss_blocks, int64_t pass_rows,
+                          dxrl_pg_lr_control ctl, int64_t* state, double* row_out, void* stream);
+
 /* ---- fused one-pass learner step (csrc/dxrl_pg_fused.hip) ----------------------------
  * One launch per network replaces forward GEMMs + heads + backward GEMMs of the
  * layer-by-layer path (dxrl_gemm_bf16 / dxrl_pg_heads / dxrl_wgrad_bf16): per
