@@ -407,6 +407,8 @@ _SIGS = {
     "dxrl_pg_rollout": (C.c_int, [_P, _P, _P, C.POINTER(PgRolloutArgs), _P]),
     "dxrl_pg_gae": (C.c_int, [_I32, _P, _P, _P, _I64, _I64, _F64, _F64, _P, _P, _P, _P, _P]),
     "dxrl_pg_gae_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
+    "dxrl_pg_gae_timelimit": (C.c_int, [_I32, _P, _P, _P, _I64, _I64, _F64, _F64, _P, _P, _P, _P, _P, _P]),
+    "dxrl_pg_gae_timelimit_count_words": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_adv_finalize": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P]),
     "dxrl_pg_adv_combine": (C.c_int, [_I32, _P, _I32, _P, _P]),
     "dxrl_pg_heads": (C.c_int, [_I32, C.POINTER(PgHeadsArgs), _P]),
@@ -500,6 +502,13 @@ def gae_partial_doubles(num_envs: int, horizon: int) -> int:
     """f64 elements of dxrl_pg_gae's `partial` scratch (include/dxrl.h)."""
     out = C.c_int64()
     call("dxrl_pg_gae_partial_doubles", num_envs, horizon, C.byref(out))
+    return out.value
+
+
+def gae_timelimit_count_words(num_envs: int, horizon: int) -> int:
+    """i64 elements of dxrl_pg_gae_timelimit's `counts` (include/dxrl.h)."""
+    out = C.c_int64()
+    call("dxrl_pg_gae_timelimit_count_words", num_envs, horizon, C.byref(out))
     return out.value
 
 

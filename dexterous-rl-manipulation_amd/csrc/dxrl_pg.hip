@@ -273,22 +273,59 @@ __global__ __launch_bounds__(64 * kRolloutWaves, 1) void k_pg_rollout(PgRolloutA
 // with Chan et al.'s pairwise update in a fixed order (deterministic).  A plain
 // sum(A^2) - mean sum(A) loses ~(mean/std)^2 ulps (2.8e-6 relative at mean/std = 4.6e4).
 // Moments, merge and block_merge: dxrl_moments.h.
+//
+// Time-limit form (kTimeLimit, dxrl_pg_gae_timelimit): the tape is the rollout's u16 episode-end
+// code (write_step_end: 0, or (episode length << 1) | terminated) in place of the done byte.  An
+// end whose bit 0 is clear is the run_episode loop bound, a time limit: the chain stops there as at
+// a termination, but the step still bootstraps -- with V_t, the critic's value of the state the
+// last action was taken in, standing in for the value of the pre-reset state the rollout does not
+// keep (an approximation: joints and object move by first-order dynamics, so the two states are
+// close).  gae_timelimit_terms states the sample's delta_t and chain coefficient c_t once for both
+// kernels; the scans, the moments and the merges are the done-byte form's.  Each workgroup also
+// counts its real envs' (time limits, terminations) into ends[2 group], ends[2 group + 1]: `ends`
+// is a trailing kernel argument of the time-limit instantiation alone (the pack Ends is int64_t*
+// there and empty in the done-byte form, whose arguments and code stay as they were).
+template <bool kTimeLimit>
+using GaeTape = std::conditional_t<kTimeLimit, uint16_t, uint8_t>;
+struct GaeTerms {
+    float delta, c;
+};
+__device__ __forceinline__ GaeTerms gae_timelimit_terms(uint16_t code, float r, float v0, float v1, float gamma,
+                                                        float gl) {
+    const bool end = code != 0, term = (code & 1) != 0, timeout = end && !term;
+    const float vb = timeout ? v0 : v1;
+    const float nb = term ? 0.0f : 1.0f;
+    return GaeTerms{r + gamma * vb * nb - v0, end ? 0.0f : gl};
+}
+template <typename Count>
+__device__ __forceinline__ void gae_count_end(uint16_t code, Count& timeouts, Count& terminations) {
+    terminations += code & 1;
+    timeouts += code != 0 && !(code & 1);
+}
+__device__ __forceinline__ void gae_store_ends(int64_t group, int64_t timeouts, int64_t terminations, int64_t* ends) {
+    ends[2 * group] = timeouts;
+    ends[2 * group + 1] = terminations;
+}
 
 constexpr int kGaeChunk = 32, kGaeThreads = 64;
-__global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ rew, const uint8_t* __restrict__ done,
+template <bool kTimeLimit, typename... Ends>
+__global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ rew,
+                                                     const GaeTape<kTimeLimit>* __restrict__ done,
                                                      const float* __restrict__ V, int64_t n, int64_t T, float gamma,
                                                      float lam, float* __restrict__ adv, float* __restrict__ ret,
-                                                     Moments* __restrict__ partial) {
+                                                     Moments* __restrict__ partial, Ends... ends) {
+    static_assert(sizeof...(Ends) == (kTimeLimit ? 1 : 0), "ends: the time-limit form's int64_t*");
     __shared__ Moments red[kGaeThreads];
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t ic = i < n ? i : n - 1;  // clamped: every lane loads, only real envs store
     double s = 0.0, s2 = 0.0, K = 0.0;
     float next_adv = 0.0f;
     float next_v = V[T * n + ic];
+    int64_t n_timeout = 0, n_term = 0;
     for (int64_t hi = T; hi > 0; hi -= kGaeChunk) {
         const int64_t lo = hi - kGaeChunk > 0 ? hi - kGaeChunk : 0;
         float rv[kGaeChunk], vv[kGaeChunk];
-        uint8_t dv[kGaeChunk];
+        GaeTape<kTimeLimit> dv[kGaeChunk];
 #pragma unroll
         for (int k = 0; k < kGaeChunk; ++k) {
             const int64_t t = lo + k < hi ? lo + k : hi - 1;
@@ -300,9 +337,16 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ r
 #pragma unroll
         for (int k = kGaeChunk - 1; k >= 0; --k) {
             if (lo + k >= hi) continue;
-            const float nd = dv[k] ? 0.0f : 1.0f;
-            const float delta = rv[k] + gamma * next_v * nd - vv[k];
-            const float a = delta + gamma * lam * nd * next_adv;
+            float a;
+            if constexpr (kTimeLimit) {
+                const GaeTerms g = gae_timelimit_terms(dv[k], rv[k], vv[k], next_v, gamma, gamma * lam);
+                a = g.delta + g.c * next_adv;
+                if (i < n) gae_count_end(dv[k], n_timeout, n_term);
+            } else {
+                const float nd = dv[k] ? 0.0f : 1.0f;
+                const float delta = rv[k] + gamma * next_v * nd - vv[k];
+                a = delta + gamma * lam * nd * next_adv;
+            }
             const int64_t m = (lo + k) * n + ic;
             if (lo + k == T - 1) K = (double)a;
             if (i < n) {
@@ -323,6 +367,14 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ r
     }
     block_merge<kGaeThreads>(mo, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    if constexpr (kTimeLimit) {  // one wave per workgroup
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            n_timeout += __shfl_xor(n_timeout, o);
+            n_term += __shfl_xor(n_term, o);
+        }
+        if (threadIdx.x == 0) gae_store_ends(blockIdx.x, n_timeout, n_term, ends...);
+    }
 }
 
 // k_gae_lds: the same per-env recurrence (k_gae's expressions), with everything but the
@@ -359,11 +411,13 @@ __device__ __forceinline__ int64_t xcd_contiguous(int64_t b, int64_t nb) {
 __host__ __device__ constexpr int64_t gae_pitch(int64_t T) { return (T + 7) / 8 * 8 + 4; }
 // delta, coefficient and advantage rows [16][pitch] (env-major), V_t [T][16]
 __host__ __device__ constexpr int64_t gae_lds_bytes(int64_t T) { return kGlEnvs * (12 * gae_pitch(T) + 4 * T); }
+template <bool kTimeLimit, typename... Ends>
 __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict__ rew,
-                                                        const uint8_t* __restrict__ done, const float* __restrict__ V,
-                                                        int64_t n, int T, float gamma, float lam,
-                                                        float* __restrict__ adv, float* __restrict__ ret,
-                                                        Moments* __restrict__ partial) {
+                                                        const GaeTape<kTimeLimit>* __restrict__ done,
+                                                        const float* __restrict__ V, int64_t n, int T, float gamma,
+                                                        float lam, float* __restrict__ adv, float* __restrict__ ret,
+                                                        Moments* __restrict__ partial, Ends... ends) {
+    static_assert(sizeof...(Ends) == (kTimeLimit ? 1 : 0), "ends: the time-limit form's int64_t*");
     extern __shared__ __attribute__((aligned(16))) float gl_lds[];
     const int P = (int)gae_pitch(T), T8 = (T + 7) / 8 * 8;
     float* Le = gl_lds;                            // [16][P] delta_t (env-major, zero past T)
@@ -378,9 +432,10 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
     const float gl = gamma * lam;
     // 1. batches of kGlBatch elements per thread, every load issued before any lands
     constexpr int kGlBatch = 16;
+    int n_timeout = 0, n_term = 0;  // this thread's ends of real envs (time-limit form)
     for (int64_t q0 = 0; q0 < cnt; q0 += (int64_t)kGlBatch * kGlThreads) {
         float rv[kGlBatch], v0[kGlBatch], v1[kGlBatch];
-        uint8_t dv[kGlBatch];
+        GaeTape<kTimeLimit> dv[kGlBatch];
 #pragma unroll
         for (int u = 0; u < kGlBatch; ++u) {
             const int64_t q = q0 + (int64_t)u * kGlThreads + tid;
@@ -397,9 +452,16 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
             const int64_t q = q0 + (int64_t)u * kGlThreads + tid;
             if (q < cnt) {
                 const int t = (int)(q / kGlEnvs), e = (int)(q % kGlEnvs);
-                const float nd = dv[u] ? 0.0f : 1.0f;
-                Le[e * P + t] = rv[u] + gamma * v1[u] * nd - v0[u];
-                Ce[e * P + t] = dv[u] ? 0.0f : gl;  // (gamma lambda) (1 - d_t), exactly
+                if constexpr (kTimeLimit) {
+                    const GaeTerms g = gae_timelimit_terms(dv[u], rv[u], v0[u], v1[u], gamma, gl);
+                    Le[e * P + t] = g.delta;
+                    Ce[e * P + t] = g.c;
+                    if (e0 + e < n) gae_count_end(dv[u], n_timeout, n_term);
+                } else {
+                    const float nd = dv[u] ? 0.0f : 1.0f;
+                    Le[e * P + t] = rv[u] + gamma * v1[u] * nd - v0[u];
+                    Ce[e * P + t] = dv[u] ? 0.0f : gl;  // (gamma lambda) (1 - d_t), exactly
+                }
                 Vs[q] = v0[u];
             }
         }
@@ -409,7 +471,29 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
         Le[e * P + t] = 0.0f;
         Ce[e * P + t] = 0.0f;
     }
-    __syncthreads();
+    if constexpr (kTimeLimit) {  // the workgroup's end counts: wave sums, then the four waves in order
+        __shared__ int wave_ends[2 * kGlThreads / 64];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            n_timeout += __shfl_xor(n_timeout, o);
+            n_term += __shfl_xor(n_term, o);
+        }
+        if ((tid & 63) == 0) {
+            wave_ends[2 * (tid >> 6)] = n_timeout;
+            wave_ends[2 * (tid >> 6) + 1] = n_term;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int64_t to = 0, te = 0;
+            for (int w = 0; w < kGlThreads / 64; ++w) {
+                to += wave_ends[2 * w];
+                te += wave_ends[2 * w + 1];
+            }
+            gae_store_ends(grp, to, te, ends...);
+        }
+    } else {
+        __syncthreads();
+    }
     // 2. the recurrence A_t = delta_t + c_t A_{t+1} as a wavefront prefix: 16 lanes per env (one
     //    wave holds 4 envs), lane s owns the 8-step chunks [s nc / 16, (s + 1) nc / 16) of its env's
     //    nc = T8 / 8 chunks.  (a) each lane composes its segment into the affine map A_start =
@@ -494,7 +578,7 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
 
 // Local moments of the rank, contiguous so ranks exchange them as one 3-element block:
 // stats[5] = count, stats[6] = mean, stats[7] = M2 (sum of squared deviations).
-__global__ void k_gae_sums(const Moments* __restrict__ partial, int nb, double* __restrict__ stats) {
+__device__ __forceinline__ void gae_sums(const Moments* __restrict__ partial, int nb, double* __restrict__ stats) {
     __shared__ Moments red[256];
     Moments a{0.0, 0.0, 0.0};
     for (int k = threadIdx.x; k < nb; k += blockDim.x) a = merge(a, partial[k]);
@@ -512,6 +596,41 @@ __global__ void k_gae_sums(const Moments* __restrict__ partial, int nb, double* 
         stats[2] = a1.mean;
         stats[3] = a1.m2;
         stats[4] = sqrt(a1.m2 / (a1.n > 1.0 ? a1.n - 1.0 : 1.0));
+    }
+}
+__global__ void k_gae_sums(const Moments* __restrict__ partial, int nb, double* __restrict__ stats) {
+    gae_sums(partial, nb, stats);
+}
+// Time-limit form: the moments as above, and the workgroups' (time limits, terminations) pairs
+// counts[2 + 2 g], counts[3 + 2 g] summed into counts[0], counts[1] -- thread-strided in index
+// order, then lanes and waves in order; integers, so exact in any order.
+__global__ void k_gae_sums_tl(const Moments* __restrict__ partial, int nb, double* __restrict__ stats,
+                              int64_t* __restrict__ counts) {
+    gae_sums(partial, nb, stats);
+    __shared__ int64_t wave_ends[2 * 256 / 64];
+    int64_t to = 0, te = 0;
+    for (int k = threadIdx.x; k < nb; k += blockDim.x) {
+        to += counts[2 + 2 * k];
+        te += counts[3 + 2 * k];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        to += __shfl_xor(to, o);
+        te += __shfl_xor(te, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wave_ends[2 * (threadIdx.x >> 6)] = to;
+        wave_ends[2 * (threadIdx.x >> 6) + 1] = te;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        to = te = 0;
+        for (int w = 0; w < 256 / 64; ++w) {
+            to += wave_ends[2 * w];
+            te += wave_ends[2 * w + 1];
+        }
+        counts[0] = to;
+        counts[1] = te;
     }
 }
 
@@ -1111,6 +1230,14 @@ int dxrl_pg_gae_partial_doubles(int64_t num_envs, int64_t horizon, int64_t* doub
     return DXRL_OK;
 }
 
+static bool gae_seq_forced() {  // A/B: k_gae, the chunked-load scan (DXRL_GAE_SEQ=1)
+    static const bool seq = [] {
+        const char* v = getenv("DXRL_GAE_SEQ");
+        return v && atoi(v) != 0;
+    }();
+    return seq;
+}
+
 int dxrl_pg_gae(int32_t device, const float* rew, const uint8_t* done, const float* values, int64_t num_envs,
                 int64_t horizon, double gamma, double lam, float* adv, float* ret, double* partial, double* stats,
                 void* stream) {
@@ -1118,27 +1245,63 @@ int dxrl_pg_gae(int32_t device, const float* rew, const uint8_t* done, const flo
     DXRL_REQUIRE(num_envs >= 1 && horizon >= 1, "num_envs and horizon must be >= 1");
     DeviceGuard g(device);
     hipStream_t st = as_stream(stream);
-    static const bool seq = [] {  // A/B: k_gae, the chunked-load scan (DXRL_GAE_SEQ=1)
-        const char* v = getenv("DXRL_GAE_SEQ");
-        return v && atoi(v) != 0;
-    }();
+    const bool seq = gae_seq_forced();
     int nb;
     const int64_t lds = gae_lds_bytes(horizon);
-    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gae_lds),
+    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gae_lds<false>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024) == hipSuccess;
     if (!seq && attr && lds <= 152 * 1024) {
         nb = (int)((num_envs + kGlEnvs - 1) / kGlEnvs);
-        hipLaunchKernelGGL(k_gae_lds, dim3(nb), dim3(kGlThreads), (size_t)lds, st, rew, done, values, num_envs,
-                           (int)horizon, (float)gamma, (float)lam, adv, ret, reinterpret_cast<Moments*>(partial));
+        hipLaunchKernelGGL(k_gae_lds<false>, dim3(nb), dim3(kGlThreads), (size_t)lds, st, rew, done, values,
+                           num_envs, (int)horizon, (float)gamma, (float)lam, adv, ret,
+                           reinterpret_cast<Moments*>(partial));
         if (int rc = launch_check("k_gae_lds")) return rc;
     } else {
         nb = (int)((num_envs + kGaeThreads - 1) / kGaeThreads);
-        hipLaunchKernelGGL(k_gae, dim3(nb), dim3(kGaeThreads), 0, st, rew, done, values, num_envs, horizon,
-                           (float)gamma, (float)lam, adv, ret, reinterpret_cast<Moments*>(partial));
+        hipLaunchKernelGGL(k_gae<false>, dim3(nb), dim3(kGaeThreads), 0, st, rew, done, values, num_envs,
+                           horizon, (float)gamma, (float)lam, adv, ret, reinterpret_cast<Moments*>(partial));
         if (int rc = launch_check("k_gae")) return rc;
     }
     hipLaunchKernelGGL(k_gae_sums, dim3(1), dim3(256), 0, st, reinterpret_cast<const Moments*>(partial), nb, stats);
     return launch_check("k_gae_sums");
+}
+
+int dxrl_pg_gae_timelimit_count_words(int64_t num_envs, int64_t horizon, int64_t* words) {
+    DXRL_REQUIRE(words && num_envs >= 1 && horizon >= 1, "bad argument");
+    // the two sums, then one (time limits, terminations) pair per workgroup of k_gae_lds<true>
+    *words = 2 + 2 * ((num_envs + kGlEnvs - 1) / kGlEnvs);
+    return DXRL_OK;
+}
+
+int dxrl_pg_gae_timelimit(int32_t device, const float* rew, const uint16_t* ep_code, const float* values,
+                          int64_t num_envs, int64_t horizon, double gamma, double lam, float* adv, float* ret,
+                          double* partial, double* stats, int64_t* counts, void* stream) {
+    DXRL_REQUIRE(rew && ep_code && values && adv && ret && partial && stats && counts, "null argument");
+    DXRL_REQUIRE(num_envs >= 1 && horizon >= 1, "num_envs and horizon must be >= 1");
+    DeviceGuard g(device);
+    hipStream_t st = as_stream(stream);
+    int nb;
+    const int64_t lds = gae_lds_bytes(horizon);
+    const auto lds_kernel = k_gae_lds<true, int64_t*>;
+    const auto seq_kernel = k_gae<true, int64_t*>;
+    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(lds_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024) == hipSuccess;
+    int64_t* ends = counts + 2;                            // the workgroups' pairs
+    if (!gae_seq_forced() && attr && lds <= 152 * 1024) {  // dxrl_pg_gae's choice
+        nb = (int)((num_envs + kGlEnvs - 1) / kGlEnvs);
+        hipLaunchKernelGGL(lds_kernel, dim3(nb), dim3(kGlThreads), (size_t)lds, st, rew, ep_code, values, num_envs,
+                           (int)horizon, (float)gamma, (float)lam, adv, ret, reinterpret_cast<Moments*>(partial),
+                           ends);
+        if (int rc = launch_check("k_gae_lds<true>")) return rc;
+    } else {
+        nb = (int)((num_envs + kGaeThreads - 1) / kGaeThreads);
+        hipLaunchKernelGGL(seq_kernel, dim3(nb), dim3(kGaeThreads), 0, st, rew, ep_code, values, num_envs, horizon,
+                           (float)gamma, (float)lam, adv, ret, reinterpret_cast<Moments*>(partial), ends);
+        if (int rc = launch_check("k_gae<true>")) return rc;
+    }
+    hipLaunchKernelGGL(k_gae_sums_tl, dim3(1), dim3(256), 0, st, reinterpret_cast<const Moments*>(partial), nb, stats,
+                       counts);
+    return launch_check("k_gae_sums_tl");
 }
 
 int dxrl_pg_adv_combine(int32_t device, const double* moments, int32_t world, double* stats, void* stream) {

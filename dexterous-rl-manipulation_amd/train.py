@@ -24,6 +24,10 @@
                        pass's KL exceeds 1.5 KL, and / or steer the learning rate towards KL inside
                        [--lr-min, --lr-max]; needs --epochs x --minibatches > 1, one rank.  The log gains
                        its optimizer table
+  --timeout-bootstrap  time-limit bootstrap in the returns (TrainerConfig.timeout_bootstrap): an episode cut
+                       by the step limit bootstraps with the critic's value of its last observed state (an
+                       approximation of the unobserved pre-reset state's); a --resume run keeps its
+                       checkpoint's setting
   --gpus N [--backend nccl|gloo]
                        a sharded run, one rank per GPU: --envs is the global count, split equally; every
                        rank trains its shard (global env ids rank * n ..) with fit(merge_ranks=True), so
@@ -97,6 +101,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--no-kl-stop", action="store_true", help="with --target-kl: adapt only, never skip updates")
     p.add_argument("--lr-min", type=float, default=None, metavar="LR")
     p.add_argument("--lr-max", type=float, default=None, metavar="LR")
+    p.add_argument("--timeout-bootstrap", action="store_true",
+                   help="bootstrap the returns at time-limit episode ends (approximate: V of the last observed state)")
     p.add_argument("--device", default=None)
     p.add_argument("--gpus", type=int, default=1, metavar="N", help="ranks of a sharded run, one per GPU")
     p.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
@@ -140,6 +146,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             validate_lr_control(TrainerConfig(epochs=a.epochs, minibatches=a.minibatches, **a.lr_control))
         except ValueError as e:
             p.error(str(e))
+    if a.timeout_bootstrap and a.resume is not None:
+        p.error("a --resume run keeps the --timeout-bootstrap setting of its checkpoint")
     if a.converge is not None:
         col, w, thr = a.converge
         if col not in _SCORE_COLUMNS:
@@ -197,6 +205,8 @@ def _build(a, fresh: bool, rank: int = 0, world: int = 1, group=None):
     from .experiments import CurriculumConfig
     from .trainer import PGTrainer, TrainerConfig
     kw = dict(horizon=a.horizon, epochs=a.epochs, minibatches=a.minibatches, max_steps=a.max_steps, **a.lr_control)
+    if a.timeout_bootstrap:
+        kw["timeout_bootstrap"] = True
     if a.config is None:
         w = workloads.WORKLOADS[a.config_name]
         n = (a.envs or w["envs"]) // world

@@ -9,7 +9,8 @@ actor-critic with GAE and policy gradients on top of the same env.  One
      the step kernel (bf16 MFMA), Gaussian sampling, optional fused noise
      injection (robustness_tests.py:140-211), auto-reset, training tape;
   2. critic forward over the T+1 observation blocks (bf16 MFMA GEMMs);
-  3. ``dxrl_pg_gae`` reverse scan + advantage normalisation from (count, mean, M2)
+  3. ``dxrl_pg_gae`` (``dxrl_pg_gae_timelimit`` with ``TrainerConfig.timeout_bootstrap``)
+     reverse scan + advantage normalisation from (count, mean, M2)
      moments merged without cancellation (global across ranks: one all-gather of each
      rank's 3 f64, merged in rank order by ``dxrl_pg_adv_combine``);
   4. actor forward, PPO-clip / value / entropy heads (``dxrl_pg_heads``);
@@ -143,6 +144,12 @@ class TrainerConfig:
     kl_adapt_band: float = 2.0
     lr_min: float = 1e-6
     lr_max: float = 1e-2
+    # time-limit bootstrap in the return computation (dxrl_pg_gae_timelimit): an episode cut by the
+    # rollout's loop bound max_steps still bootstraps, with V of the state its last action was taken
+    # in standing in for the unobserved pre-reset state (an approximation); terminations drop the
+    # bootstrap as before.  Reads the rollout's episode-end codes (needs success_rule "terminated",
+    # whose bit 0 tells the two ends apart); False leaves the trainer's launches as they are.
+    timeout_bootstrap: bool = False
 
 
 def minibatch_bounds(M: int, B: int, round_samples: int):
@@ -244,8 +251,17 @@ class PGTrainer:
         self.rec_end = z(n, max(cap, 1), dt=torch.int32)
         if cfg.success_rule not in ("training", "terminated"):
             raise ValueError("success_rule must be 'training' or 'terminated'")
+        if cfg.timeout_bootstrap and cfg.success_rule != "terminated":
+            raise ValueError("timeout_bootstrap needs success_rule='terminated': under success_rule='training' the "
+                             "episode-end code's success bit is always 0, so every termination would read as a "
+                             "time limit")
         self.scheduler = None
-        self.ep_code = None  # u16 [T N] episode-end codes (scheduler feed, attach_curriculum)
+        # u16 [T N] episode-end codes: the scheduler's feed (attach_curriculum) and the time-limit
+        # bootstrap's tape (one tape for both)
+        self.ep_code = torch.zeros(T * n, dtype=torch.int16, device=d) if cfg.timeout_bootstrap else None
+        # dxrl_pg_gae_timelimit's counts: [0] time limits, [1] terminations of the last iteration
+        self.end_counts = (torch.zeros(N.gae_timelimit_count_words(n, T), dtype=torch.int64, device=d)
+                           if cfg.timeout_bootstrap else None)
         # hidden activations, row-major [rows][288]: columns 0..255 = tanh units, column 256 = 1
         # (the next layer reads K = 256; the weight-gradient GEMM reads I = 288 and gets the bias
         # gradient as column 256)
@@ -562,8 +578,14 @@ class PGTrainer:
 
     def advantages(self):
         c = self.cfg
-        N.call("dxrl_pg_gae", self.dev.index, N.ptr(self.rew), N.ptr(self.done), N.ptr(self.V[0]), self.n, self.T,
-               c.gamma, c.lam, N.ptr(self.adv), N.ptr(self.ret), N.ptr(self.partial), N.ptr(self.stats), self._s())
+        if c.timeout_bootstrap:  # the episode-end codes in place of the done bytes
+            N.call("dxrl_pg_gae_timelimit", self.dev.index, N.ptr(self.rew), N.ptr(self.ep_code), N.ptr(self.V[0]),
+                   self.n, self.T, c.gamma, c.lam, N.ptr(self.adv), N.ptr(self.ret), N.ptr(self.partial),
+                   N.ptr(self.stats), N.ptr(self.end_counts), self._s())
+        else:
+            N.call("dxrl_pg_gae", self.dev.index, N.ptr(self.rew), N.ptr(self.done), N.ptr(self.V[0]), self.n,
+                   self.T, c.gamma, c.lam, N.ptr(self.adv), N.ptr(self.ret), N.ptr(self.partial), N.ptr(self.stats),
+                   self._s())
         # every rank's (count, mean, M2) in rank order, merged on device (identical on all ranks);
         # one rank: dxrl_pg_gae already wrote the combined statistics
         if self.collective:
@@ -697,7 +719,8 @@ class PGTrainer:
         self.scheduler = scheduler
         self.env.set_curriculum(scheduler.get_current_config())
         d, n, T = self.dev, self.n, self.T
-        self.ep_code = torch.zeros(T * n, dtype=torch.int16, device=d)
+        if self.ep_code is None:  # with timeout_bootstrap the tape is there already (one tape for both)
+            self.ep_code = torch.zeros(T * n, dtype=torch.int16, device=d)
         self.codes_all = self.ep_code if not self.collective else None  # host mode's all-gather (lazy)
         w = max(1, int(scheduler.window_size))
         self._sched_w = w
@@ -911,6 +934,14 @@ class PGTrainer:
             out["mean_length"] = float(self.ep_sum_len.sum().item()) / cnt
             out["success_rate"] = float(self.ep_succ.sum().item()) / cnt
         return out
+
+    def timeout_stats(self) -> Dict[str, int]:
+        """Episode ends on this rank's tape of the last iteration, by kind (timeout_bootstrap only):
+        time limits (the bootstrapped ends) and terminations.  One 16-byte read."""
+        if self.end_counts is None:
+            raise ValueError("timeout_stats() needs TrainerConfig.timeout_bootstrap")
+        timeouts, terminations = self.end_counts[:2].tolist()
+        return {"timeouts": int(timeouts), "terminations": int(terminations)}
 
     def loss_stats(self) -> Dict[str, float]:
         """Loss terms of the last train pass (the last minibatch of the last epoch), per sample of

@@ -1374,12 +1374,13 @@ def save_checkpoint(tr, path):
 
 
 def _trainer_config_state(cfg) -> Dict[str, Any]:
-    """The checkpoint's trainer_config: the dataclass's fields, without the step-size fields that
-    sit at their defaults (a trainer without step-size control writes the entry it always did;
-    a missing field loads as its default)."""
+    """The checkpoint's trainer_config: the dataclass's fields, without the step-size fields and
+    timeout_bootstrap where they sit at their defaults (a trainer without them writes the entry it
+    always did; a missing field loads as its default)."""
     from .lr_control import CONFIG_DEFAULTS
+    later = dict(CONFIG_DEFAULTS, timeout_bootstrap=False)
     d = dataclasses.asdict(cfg)
-    return {k: v for k, v in d.items() if k not in CONFIG_DEFAULTS or v != CONFIG_DEFAULTS[k]}
+    return {k: v for k, v in d.items() if k not in later or v != later[k]}
 
 
 def validation_arrays(table, header, best_params, objects, levels=None, robust=None, paired=None,

@@ -414,6 +414,32 @@ int dxrl_pg_gae(int32_t device, const float* rew, const uint8_t* done, const flo
                 void* stream);
 /* f64 elements of dxrl_pg_gae's `partial` scratch for (num_envs, horizon) (host-only query). */
 int dxrl_pg_gae_partial_doubles(int64_t num_envs, int64_t horizon, int64_t* doubles);
+/* dxrl_pg_gae with the time-limit bootstrap: the tape is the rollout's episode-end code ep_code
+ * u16 [T N] (dxrl_pg_rollout_args.ep_code under success_rule "terminated": 0, or
+ * (episode length << 1) | terminated) in place of the done byte.  Per sample, in f32, in this order:
+ *   end = code != 0, term = code & 1, timeout = end && !term
+ *   vb = timeout ? V_t : V_{t+1};  nb = term ? 0 : 1
+ *   delta_t = r_t + gamma vb nb - V_t;  c_t = end ? 0 : gamma lambda
+ *   A_t = delta_t + c_t A_{t+1};  ret_t = A_t + V_t
+ * The chain stops at either kind of end; a termination drops the bootstrap as dxrl_pg_gae does at
+ * every done, an end at the run_episode loop bound (a time limit, not a property of the state)
+ * keeps it.  The state the bootstrap belongs to, the one the episode's last step led to, is
+ * overwritten by the reset and not on the tape: V_t, the critic's value of the state the last
+ * action was taken in, stands in for it.  That is an approximation (the states are one first-order
+ * dynamics step apart), not the exact time-limit bootstrap.
+ * Kernels (chosen by horizon as in dxrl_pg_gae, DXRL_GAE_SEQ included), scans, moments, `partial`
+ * (dxrl_pg_gae_partial_doubles) and stats[0..7] are dxrl_pg_gae's; two launches.  On a tape whose
+ * codes all have bit 0 set, adv / ret are dxrl_pg_gae's on done = code != 0, bit for bit.
+ * counts: i64 [dxrl_pg_gae_timelimit_count_words(N, T)]: counts[0] = time limits, counts[1] =
+ * terminations on the tape -- exact: integer sums of the launched workgroups' (time limits,
+ * terminations) pairs, which follow from counts[2] on (16 envs per pair in k_gae_lds, 64 in k_gae).
+ * DXRL_E_INVALID before any launch on a null pointer or num_envs / horizon < 1. */
+int dxrl_pg_gae_timelimit(int32_t device, const float* rew, const uint16_t* ep_code, const float* values,
+                          int64_t num_envs, int64_t horizon, double gamma, double lam, float* adv, float* ret,
+                          double* partial, double* stats, int64_t* counts, void* stream);
+/* i64 elements of dxrl_pg_gae_timelimit's `counts` for (num_envs, horizon) (= 2 + 2 ceil(N / 16);
+ * host-only query). */
+int dxrl_pg_gae_timelimit_count_words(int64_t num_envs, int64_t horizon, int64_t* words);
 /* Global advantage statistics from every rank's (count, mean, M2) triple -- moments f64
  * [world][3] in rank order (all-gathered stats[5..7]) -- merged in rank order into
  * stats[0] count, [1] sum, [2] mean, [3] sum of squared deviations, [4] unbiased std (what the

@@ -1,13 +1,16 @@
 """Code-generation check for a refactor: per-kernel resources and instruction streams of two trees.
 
     python tools/kernel_isa.py emit OUTDIR [REV]      # gfx950 assembly + resource remarks of csrc (of commit REV)
-    python tools/kernel_isa.py compare DIR_A DIR_B    # table A vs B per kernel, "same ISA" yes / no
+    python tools/kernel_isa.py compare DIR_A DIR_B [OLD=NEW ..]   # table A vs B per kernel, "same ISA" yes / no
 
 emit compiles the env / rollout / eval translation units with build.py's FLAGS plus
 --cuda-device-only -S -Rpass-analysis=kernel-resource-usage (no GPU needed).  compare matches
 kernels by name across all files (a kernel may move between files) and calls two instruction
 streams the same when they are equal after dropping comments, debug directives and the kernel's
-own name, and renumbering labels in order of appearance."""
+own name, and renumbering labels in order of appearance.  OLD=NEW: a kernel of A whose demangled
+name starts with OLD is compared with the kernel of B whose name starts with NEW (a kernel that
+became a template instantiation: "dxrl::k_gae(=void dxrl::k_gae<false>(").  A template's code sits in
+a section of its own, so section directives are dropped too."""
 import os
 import re
 import subprocess
@@ -96,7 +99,7 @@ def normalise(name, body):
     for line in body:
         line = line.split(";")[0].rstrip()
         s = line.strip()
-        if not s or s.startswith((".loc", ".file", ".cfi", ".p2align", "s_nop", "s_code_end")):
+        if not s or s.startswith((".loc", ".file", ".cfi", ".p2align", "s_nop", "s_code_end", ".text", ".section")):
             continue
         line = line.replace(name, "KERNEL")
         res.append(re.sub(r"\.L(BB|tmp)\w+", lab, line))
@@ -111,10 +114,18 @@ def demangle(names):
         return {n: n for n in names}
 
 
-def compare(a, b):
+def compare(a, b, renames=()):
     ra, rb, sa, sb = resources(a), resources(b), streams(a), streams(b)
+    dm = demangle(sorted(set(ra) | set(rb)))
+    for pair in renames:
+        old, new = pair.split("=", 1)
+        na = [n for n in ra if n not in rb and dm[n].startswith(old)]
+        nb = [n for n in rb if n not in ra and dm[n].startswith(new)]
+        if len(na) != 1 or len(nb) != 1:
+            sys.exit(f"{pair}: {len(na)} kernels of A and {len(nb)} of B match")
+        rb[na[0]], sb[na[0]] = rb.pop(nb[0]), sb.pop(nb[0], None)
+        dm[na[0]] += f"  ->  {dm[nb[0]]}"
     names = sorted(set(ra) | set(rb))
-    dm = demangle(names)
     print("kernel | file A -> B | " + " | ".join(FIELDS) + " | same ISA")
     bad = 0
     for n in names:
@@ -143,4 +154,4 @@ if __name__ == "__main__":
     if sys.argv[1] == "emit":
         emit(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
     else:
-        sys.exit(compare(sys.argv[2], sys.argv[3]))
+        sys.exit(compare(sys.argv[2], sys.argv[3], sys.argv[4:]))
