@@ -363,13 +363,30 @@ PG_OPT_COLUMNS = ("lr", "lr_last", "updates", "skipped", "stop_pass", "kl_max", 
 PG_OPT_COLS = len(PG_OPT_COLUMNS)           # DXRL_PG_OPT_COLS
 
 
+# dxrl_pg_gae_vnorm: the args struct and the words of the state block (enum dxrl_pg_vnorm_word)
+class PgGaeVnormArgs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("rew", "done", "ep_code", "values")] + \
+               [("num_envs", C.c_int64), ("horizon", C.c_int64)] + \
+               [(k, C.c_double) for k in ("gamma", "lam", "eps")] + \
+               [(k, C.c_void_p) for k in ("adv", "ret", "ret_norm", "values_raw", "partial", "stats", "counts",
+                                          "vnorm")] + \
+               [("fold", C.c_int32)]
+
+
+PG_VNORM_NAMES = ("count", "mean", "m2", "mu", "sigma", "batch_count", "batch_mean", "batch_m2", "adv_count",
+                  "adv_mean", "adv_m2", "calls", "eps")
+PG_VNORM_NAMED = len(PG_VNORM_NAMES)  # DXRL_PG_VNORM_NAMED
+PG_VNORM_WORDS = 16                   # DXRL_PG_VNORM_WORDS
+PG_VNORM = {k: i for i, k in enumerate(PG_VNORM_NAMES)}
+
+
 # the structs added after tests/test_native_abi.py fixed its list: (C name, mirror), sized against
 # include/dxrl.h by the tests of the layers that use them
 LATER_STRUCTS = (("dxrl_pg_log_args", PgLogArgs), ("dxrl_pg_log_header", PgLogHeader),
                  ("dxrl_pg_val_args", PgValArgs), ("dxrl_pg_val_header", PgValHeader),
                  ("dxrl_pg_val_levels_args", PgValLevelsArgs), ("dxrl_pg_val_paired_args", PgValPairedArgs),
                  ("dxrl_pg_val_failure_args", PgValFailureArgs), ("dxrl_pg_runs_spec", PgRunsSpec),
-                 ("dxrl_pg_runs_args", PgRunsArgs))
+                 ("dxrl_pg_runs_args", PgRunsArgs), ("dxrl_pg_gae_vnorm_args", PgGaeVnormArgs))
 
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
@@ -409,6 +426,9 @@ _SIGS = {
     "dxrl_pg_gae_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_gae_timelimit": (C.c_int, [_I32, _P, _P, _P, _I64, _I64, _F64, _F64, _P, _P, _P, _P, _P, _P]),
     "dxrl_pg_gae_timelimit_count_words": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
+    "dxrl_pg_gae_vnorm": (C.c_int, [_I32, C.POINTER(PgGaeVnormArgs), _P]),
+    "dxrl_pg_gae_vnorm_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
+    "dxrl_pg_vnorm_combine": (C.c_int, [_I32, _P, _I32, _P, _P, _P]),
     "dxrl_pg_adv_finalize": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P]),
     "dxrl_pg_adv_combine": (C.c_int, [_I32, _P, _I32, _P, _P]),
     "dxrl_pg_heads": (C.c_int, [_I32, C.POINTER(PgHeadsArgs), _P]),
@@ -510,6 +530,21 @@ def gae_timelimit_count_words(num_envs: int, horizon: int) -> int:
     out = C.c_int64()
     call("dxrl_pg_gae_timelimit_count_words", num_envs, horizon, C.byref(out))
     return out.value
+
+
+def gae_vnorm_partial_doubles(num_envs: int, horizon: int) -> int:
+    """f64 elements of dxrl_pg_gae_vnorm's `partial` scratch (include/dxrl.h)."""
+    out = C.c_int64()
+    call("dxrl_pg_gae_vnorm_partial_doubles", num_envs, horizon, C.byref(out))
+    return out.value
+
+
+def vnorm_fresh(device=None):
+    """A fresh dxrl_pg_gae_vnorm state block: f64 [PG_VNORM_WORDS], all zero but sigma = 1."""
+    import torch
+    t = torch.zeros(PG_VNORM_WORDS, dtype=torch.float64)
+    t[PG_VNORM["sigma"]] = 1.0
+    return t if device is None else t.to(device)
 
 
 def ptr(t) -> int | None:

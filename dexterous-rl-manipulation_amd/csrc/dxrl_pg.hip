@@ -285,8 +285,40 @@ __global__ __launch_bounds__(64 * kRolloutWaves, 1) void k_pg_rollout(PgRolloutA
 // counts its real envs' (time limits, terminations) into ends[2 group], ends[2 group + 1]: `ends`
 // is a trailing kernel argument of the time-limit instantiation alone (the pack Ends is int64_t*
 // there and empty in the done-byte form, whose arguments and code stay as they were).
+//
+// Value-normalisation form (dxrl_pg_gae_vnorm; include/dxrl.h states the semantics): the pack also
+// carries a GaeVnorm, in last place.  The critic's outputs are decoded with the block's (mu, sigma)
+// as they are loaded, so the terms, the scans and the advantage moments run on raw values as they
+// are; the decoded values go to values_raw, every return also to ret_norm, encoded, and the returns
+// get a second moments triple, reduced exactly as the advantages' (the workgroup's triple lands in
+// partial[workgroups + group]).  The forms without a GaeVnorm keep their arguments and code.
 template <bool kTimeLimit>
 using GaeTape = std::conditional_t<kTimeLimit, uint16_t, uint8_t>;
+struct GaeVnorm {
+    const double* state;  // the vnorm block: mu and sigma are read, nothing is written
+    float* ret_norm;      // [T N]
+    float* values_raw;    // [(T + 1) N]
+};
+template <typename... Extra>
+inline constexpr bool kGaeHasVnorm = (std::is_same_v<Extra, GaeVnorm> || ...);
+template <typename First, typename... Rest>
+__device__ __forceinline__ First gae_pack_first(First x, Rest...) {
+    return x;
+}
+template <typename Last>
+__device__ __forceinline__ Last gae_pack_last(Last x) {
+    return x;
+}
+template <typename First, typename... Rest>
+__device__ __forceinline__ auto gae_pack_last(First, Rest... rest) {
+    return gae_pack_last(rest...);
+}
+__device__ __forceinline__ float gae_decode(float vn, float mu, float sigma) { return sigma * vn + mu; }
+__device__ __forceinline__ float gae_encode(float ret, float mu, float sigma) { return (ret - mu) / sigma; }
+// a thread's shifted sums as a triple (count c > 0)
+__device__ __forceinline__ Moments gae_shifted(double c, double K, double s, double s2) {
+    return Moments{c, K + s / c, fmax(s2 - s * (s / c), 0.0)};
+}
 struct GaeTerms {
     float delta, c;
 };
@@ -314,13 +346,25 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ r
                                                      const float* __restrict__ V, int64_t n, int64_t T, float gamma,
                                                      float lam, float* __restrict__ adv, float* __restrict__ ret,
                                                      Moments* __restrict__ partial, Ends... ends) {
-    static_assert(sizeof...(Ends) == (kTimeLimit ? 1 : 0), "ends: the time-limit form's int64_t*");
+    constexpr bool kVnorm = kGaeHasVnorm<Ends...>;
+    static_assert(sizeof...(Ends) == (kTimeLimit ? 1 : 0) + (kVnorm ? 1 : 0),
+                  "ends: the time-limit form's int64_t*, then the value-normalisation form's GaeVnorm");
     __shared__ Moments red[kGaeThreads];
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t ic = i < n ? i : n - 1;  // clamped: every lane loads, only real envs store
     double s = 0.0, s2 = 0.0, K = 0.0;
     float next_adv = 0.0f;
     float next_v = V[T * n + ic];
+    [[maybe_unused]] GaeVnorm vn{};
+    [[maybe_unused]] float mu = 0.0f, sigma = 1.0f;
+    [[maybe_unused]] double rs = 0.0, rs2 = 0.0, rK = 0.0;  // the returns' shifted sums
+    if constexpr (kVnorm) {
+        vn = gae_pack_last(ends...);
+        mu = (float)vn.state[DXRL_PG_VNORM_MU];
+        sigma = (float)vn.state[DXRL_PG_VNORM_SIGMA];
+        next_v = gae_decode(next_v, mu, sigma);
+        if (i < n) vn.values_raw[T * n + i] = next_v;
+    }
     int64_t n_timeout = 0, n_term = 0;
     for (int64_t hi = T; hi > 0; hi -= kGaeChunk) {
         const int64_t lo = hi - kGaeChunk > 0 ? hi - kGaeChunk : 0;
@@ -337,6 +381,7 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ r
 #pragma unroll
         for (int k = kGaeChunk - 1; k >= 0; --k) {
             if (lo + k >= hi) continue;
+            if constexpr (kVnorm) vv[k] = gae_decode(vv[k], mu, sigma);
             float a;
             if constexpr (kTimeLimit) {
                 const GaeTerms g = gae_timelimit_terms(dv[k], rv[k], vv[k], next_v, gamma, gamma * lam);
@@ -355,6 +400,15 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ r
                 const double d = (double)a - K;
                 s += d;
                 s2 += d * d;
+                if constexpr (kVnorm) {
+                    const float r = a + vv[k];
+                    vn.ret_norm[m] = gae_encode(r, mu, sigma);
+                    vn.values_raw[m] = vv[k];
+                    if (lo + k == T - 1) rK = (double)r;
+                    const double rd = (double)r - rK;
+                    rs += rd;
+                    rs2 += rd * rd;
+                }
             }
             next_adv = a;
             next_v = vv[k];
@@ -373,7 +427,11 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(const float* __restrict__ r
             n_timeout += __shfl_xor(n_timeout, o);
             n_term += __shfl_xor(n_term, o);
         }
-        if (threadIdx.x == 0) gae_store_ends(blockIdx.x, n_timeout, n_term, ends...);
+        if (threadIdx.x == 0) gae_store_ends(blockIdx.x, n_timeout, n_term, gae_pack_first(ends...));
+    }
+    if constexpr (kVnorm) {  // (thread 0 has read red[0]; no other thread writes it)
+        block_merge<kGaeThreads>(i < n ? gae_shifted((double)T, rK, rs, rs2) : Moments{0.0, 0.0, 0.0}, red);
+        if (threadIdx.x == 0) partial[gridDim.x + blockIdx.x] = red[0];
     }
 }
 
@@ -417,7 +475,9 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
                                                         const float* __restrict__ V, int64_t n, int T, float gamma,
                                                         float lam, float* __restrict__ adv, float* __restrict__ ret,
                                                         Moments* __restrict__ partial, Ends... ends) {
-    static_assert(sizeof...(Ends) == (kTimeLimit ? 1 : 0), "ends: the time-limit form's int64_t*");
+    constexpr bool kVnorm = kGaeHasVnorm<Ends...>;
+    static_assert(sizeof...(Ends) == (kTimeLimit ? 1 : 0) + (kVnorm ? 1 : 0),
+                  "ends: the time-limit form's int64_t*, then the value-normalisation form's GaeVnorm");
     extern __shared__ __attribute__((aligned(16))) float gl_lds[];
     const int P = (int)gae_pitch(T), T8 = (T + 7) / 8 * 8;
     float* Le = gl_lds;                            // [16][P] delta_t (env-major, zero past T)
@@ -430,6 +490,13 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
     const int64_t e0 = grp * kGlEnvs;
     const int64_t cnt = (int64_t)T * kGlEnvs;
     const float gl = gamma * lam;
+    [[maybe_unused]] GaeVnorm vn{};
+    [[maybe_unused]] float mu = 0.0f, sigma = 1.0f;
+    if constexpr (kVnorm) {
+        vn = gae_pack_last(ends...);
+        mu = (float)vn.state[DXRL_PG_VNORM_MU];
+        sigma = (float)vn.state[DXRL_PG_VNORM_SIGMA];
+    }
     // 1. batches of kGlBatch elements per thread, every load issued before any lands
     constexpr int kGlBatch = 16;
     int n_timeout = 0, n_term = 0;  // this thread's ends of real envs (time-limit form)
@@ -452,6 +519,14 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
             const int64_t q = q0 + (int64_t)u * kGlThreads + tid;
             if (q < cnt) {
                 const int t = (int)(q / kGlEnvs), e = (int)(q % kGlEnvs);
+                if constexpr (kVnorm) {  // decoded once per use: the same bits as V_t and as V_{t+1}
+                    v0[u] = gae_decode(v0[u], mu, sigma);
+                    v1[u] = gae_decode(v1[u], mu, sigma);
+                    if (e0 + e < n) {
+                        vn.values_raw[(int64_t)t * n + e0 + e] = v0[u];
+                        if (t == T - 1) vn.values_raw[(int64_t)T * n + e0 + e] = v1[u];
+                    }
+                }
                 if constexpr (kTimeLimit) {
                     const GaeTerms g = gae_timelimit_terms(dv[u], rv[u], v0[u], v1[u], gamma, gl);
                     Le[e * P + t] = g.delta;
@@ -489,7 +564,7 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
                 to += wave_ends[2 * w];
                 te += wave_ends[2 * w + 1];
             }
-            gae_store_ends(grp, to, te, ends...);
+            gae_store_ends(grp, to, te, gae_pack_first(ends...));
         }
     } else {
         __syncthreads();
@@ -551,6 +626,7 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
     // 3. store, and the moments of this thread's elements about its first one (merged with Chan's
     // update below and across workgroups: any shift point gives the same moments up to rounding)
     double s = 0.0, s2 = 0.0, K = 0.0, c = 0.0;
+    [[maybe_unused]] double rs = 0.0, rs2 = 0.0, rK = 0.0;  // the returns' shifted sums (count c too)
     for (int64_t q = tid; q < cnt; q += kGlThreads) {
         const int64_t t = q / kGlEnvs, e = q % kGlEnvs;
         if (e0 + e < n) {
@@ -558,8 +634,16 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
             if (!(DXRL_GAE_DIAG & 4)) {
                 adv[t * n + e0 + e] = a;
                 ret[t * n + e0 + e] = a + Vs[q];
+                if constexpr (kVnorm) vn.ret_norm[t * n + e0 + e] = gae_encode(a + Vs[q], mu, sigma);
             }
             if (DXRL_GAE_DIAG & 2) continue;
+            if constexpr (kVnorm) {
+                const float r = a + Vs[q];
+                if (c == 0.0) rK = (double)r;
+                const double rd = (double)r - rK;
+                rs += rd;
+                rs2 += rd * rd;
+            }
             if (c == 0.0) K = (double)a;
             const double d = (double)a - K;
             s += d;
@@ -570,10 +654,16 @@ __global__ __launch_bounds__(kGlThreads) void k_gae_lds(const float* __restrict_
     const Moments mo = c > 0.0 ? Moments{c, K + s / c, fmax(s2 - s * (s / c), 0.0)} : Moments{0.0, 0.0, 0.0};
     if (DXRL_GAE_DIAG & 2) {
         if (tid == 0) partial[grp] = mo;
+        if constexpr (kVnorm)
+            if (tid == 0) partial[gridDim.x + grp] = mo;
         return;
     }
     block_merge<kGlThreads>(mo, red);
     if (tid == 0) partial[grp] = red[0];
+    if constexpr (kVnorm) {  // (thread 0 has read red[0]; no other thread writes it)
+        block_merge<kGlThreads>(c > 0.0 ? gae_shifted(c, rK, rs, rs2) : Moments{0.0, 0.0, 0.0}, red);
+        if (tid == 0) partial[gridDim.x + grp] = red[0];
+    }
 }
 
 // Local moments of the rank, contiguous so ranks exchange them as one 3-element block:
@@ -604,8 +694,8 @@ __global__ void k_gae_sums(const Moments* __restrict__ partial, int nb, double* 
 // Time-limit form: the moments as above, and the workgroups' (time limits, terminations) pairs
 // counts[2 + 2 g], counts[3 + 2 g] summed into counts[0], counts[1] -- thread-strided in index
 // order, then lanes and waves in order; integers, so exact in any order.
-__global__ void k_gae_sums_tl(const Moments* __restrict__ partial, int nb, double* __restrict__ stats,
-                              int64_t* __restrict__ counts) {
+__device__ __forceinline__ void gae_sums_tl(const Moments* __restrict__ partial, int nb, double* __restrict__ stats,
+                                            int64_t* __restrict__ counts) {
     gae_sums(partial, nb, stats);
     __shared__ int64_t wave_ends[2 * 256 / 64];
     int64_t to = 0, te = 0;
@@ -633,17 +723,80 @@ __global__ void k_gae_sums_tl(const Moments* __restrict__ partial, int nb, doubl
         counts[1] = te;
     }
 }
+__global__ void k_gae_sums_tl(const Moments* __restrict__ partial, int nb, double* __restrict__ stats,
+                              int64_t* __restrict__ counts) {
+    gae_sums_tl(partial, nb, stats, counts);
+}
+// Value normalisation: one batch of returns folded into the block's running triple, and the next
+// call's constants from it (one thread; include/dxrl.h states the words).
+__device__ __forceinline__ void vnorm_fold(double* __restrict__ vn, Moments batch, double eps) {
+    const Moments run = merge(Moments{vn[DXRL_PG_VNORM_COUNT], vn[DXRL_PG_VNORM_MEAN], vn[DXRL_PG_VNORM_M2]}, batch);
+    vn[DXRL_PG_VNORM_COUNT] = run.n;
+    vn[DXRL_PG_VNORM_MEAN] = run.mean;
+    vn[DXRL_PG_VNORM_M2] = run.m2;
+    vn[DXRL_PG_VNORM_CALLS] += 1.0;
+    if (run.n > 0.0) {
+        vn[DXRL_PG_VNORM_MU] = (double)(float)run.mean;
+        vn[DXRL_PG_VNORM_SIGMA] = (double)(float)sqrt(run.m2 / run.n + eps);
+    }
+}
+__device__ __forceinline__ void vnorm_store_batch(double* __restrict__ vn, Moments ret, Moments adv) {
+    vn[DXRL_PG_VNORM_BATCH_COUNT] = ret.n;
+    vn[DXRL_PG_VNORM_BATCH_MEAN] = ret.mean;
+    vn[DXRL_PG_VNORM_BATCH_M2] = ret.m2;
+    vn[DXRL_PG_VNORM_ADV_COUNT] = adv.n;
+    vn[DXRL_PG_VNORM_ADV_MEAN] = adv.mean;
+    vn[DXRL_PG_VNORM_ADV_M2] = adv.m2;
+}
+// Value-normalisation form of the finishing launch: k_gae_sums / k_gae_sums_tl's work, then the
+// workgroups' return triples partial[nb ..] merged in the advantage triples' order, the batch words
+// of the block and, with fold, the fold.  The scan kernel before it has read mu / sigma already.
+template <bool kTimeLimit>
+__global__ void k_gae_sums_vn(const Moments* __restrict__ partial, int nb, double* __restrict__ stats,
+                              int64_t* __restrict__ counts, double* __restrict__ vn, double eps, int fold) {
+    if constexpr (kTimeLimit) gae_sums_tl(partial, nb, stats, counts);
+    else gae_sums(partial, nb, stats);
+    __shared__ Moments red[256];
+    Moments a{0.0, 0.0, 0.0};
+    for (int k = threadIdx.x; k < nb; k += blockDim.x) a = merge(a, partial[nb + k]);
+    block_merge<256>(a, red);
+    if (threadIdx.x == 0) {
+        const Moments batch = red[0];
+        vnorm_store_batch(vn, batch, Moments{stats[5], stats[6], stats[7]});  // this thread wrote them
+        vn[DXRL_PG_VNORM_EPS] = eps;
+        if (fold) vnorm_fold(vn, batch, eps);
+    }
+}
 
 // Global statistics from the ranks' (count, mean, M2) triples, merged in rank order:
 // stats[0] count, [1] sum, [2] mean, [3] sum of squared deviations, [4] unbiased std
-__global__ void k_stats_combine(const double* __restrict__ moments, int world, double* stats) {
+// (kStride doubles from one rank's triple to the next)
+template <int kStride>
+__device__ __forceinline__ Moments merge_ranks(const double* __restrict__ moments, int world) {
     Moments a{0.0, 0.0, 0.0};
-    for (int r = 0; r < world; ++r) a = merge(a, Moments{moments[3 * r], moments[3 * r + 1], moments[3 * r + 2]});
+    for (int r = 0; r < world; ++r)
+        a = merge(a, Moments{moments[kStride * r], moments[kStride * r + 1], moments[kStride * r + 2]});
+    return a;
+}
+template <int kStride>
+__device__ __forceinline__ Moments stats_combine(const double* __restrict__ moments, int world, double* stats) {
+    const Moments a = merge_ranks<kStride>(moments, world);
     stats[0] = a.n;
     stats[1] = a.n * a.mean;
     stats[2] = a.mean;
     stats[3] = a.m2;
     stats[4] = sqrt(a.m2 / (a.n > 1.0 ? a.n - 1.0 : 1.0));
+    return a;
+}
+__global__ void k_stats_combine(const double* __restrict__ moments, int world, double* stats) {
+    stats_combine<3>(moments, world, stats);
+}
+// dxrl_pg_vnorm_combine: rows (return triple, advantage triple) in rank order; one thread
+__global__ void k_vnorm_combine(const double* __restrict__ moments6, int world, double* stats,
+                                double* __restrict__ vn) {
+    const Moments adv = stats_combine<6>(moments6 + 3, world, stats), batch = merge_ranks<6>(moments6, world);
+    vnorm_store_batch(vn, batch, adv);
+    vnorm_fold(vn, batch, vn[DXRL_PG_VNORM_EPS]);
 }
 
 // out[slot] = sum(partials) (fixed order)
@@ -1131,6 +1284,43 @@ int rollout_kernel(int64_t n, int32_t diag_flags, bool obs_fm) {
     const bool e8 = !(diag_flags & 2048) && ((diag_flags & 1024) || n >= (int64_t)kE8Envs * cus);
     return e8 ? 2 : 1;
 }
+
+static bool gae_seq_forced() {  // A/B: k_gae, the chunked-load scan (DXRL_GAE_SEQ=1)
+    static const bool seq = [] {
+        const char* v = getenv("DXRL_GAE_SEQ");
+        return v && atoi(v) != 0;
+    }();
+    return seq;
+}
+
+// the two launches of dxrl_pg_gae_vnorm for one tape form (dxrl_pg_gae's choice of kernel)
+template <bool kTimeLimit, typename... Ends>
+static int gae_vnorm_launch(const dxrl_pg_gae_vnorm_args* a, const GaeTape<kTimeLimit>* tape, hipStream_t st,
+                            Ends... ends) {
+    const GaeVnorm vn{a->vnorm, a->ret_norm, a->values_raw};
+    const auto lds_kernel = k_gae_lds<kTimeLimit, Ends..., GaeVnorm>;
+    const auto seq_kernel = k_gae<kTimeLimit, Ends..., GaeVnorm>;
+    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(lds_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024) == hipSuccess;
+    int nb;
+    const int64_t lds = gae_lds_bytes(a->horizon);
+    Moments* partial = reinterpret_cast<Moments*>(a->partial);
+    if (!gae_seq_forced() && attr && lds <= 152 * 1024) {
+        nb = (int)((a->num_envs + kGlEnvs - 1) / kGlEnvs);
+        hipLaunchKernelGGL(lds_kernel, dim3(nb), dim3(kGlThreads), (size_t)lds, st, a->rew, tape, a->values,
+                           a->num_envs, (int)a->horizon, (float)a->gamma, (float)a->lam, a->adv, a->ret, partial,
+                           ends..., vn);
+        if (int rc = launch_check("k_gae_lds<vnorm>")) return rc;
+    } else {
+        nb = (int)((a->num_envs + kGaeThreads - 1) / kGaeThreads);
+        hipLaunchKernelGGL(seq_kernel, dim3(nb), dim3(kGaeThreads), 0, st, a->rew, tape, a->values, a->num_envs,
+                           a->horizon, (float)a->gamma, (float)a->lam, a->adv, a->ret, partial, ends..., vn);
+        if (int rc = launch_check("k_gae<vnorm>")) return rc;
+    }
+    hipLaunchKernelGGL(k_gae_sums_vn<kTimeLimit>, dim3(1), dim3(256), 0, st, partial, nb, a->stats, a->counts,
+                       a->vnorm, a->eps, (int)a->fold);
+    return launch_check("k_gae_sums_vn");
+}
 }  // namespace
 }  // namespace dxrl
 extern "C" {
@@ -1230,14 +1420,6 @@ int dxrl_pg_gae_partial_doubles(int64_t num_envs, int64_t horizon, int64_t* doub
     return DXRL_OK;
 }
 
-static bool gae_seq_forced() {  // A/B: k_gae, the chunked-load scan (DXRL_GAE_SEQ=1)
-    static const bool seq = [] {
-        const char* v = getenv("DXRL_GAE_SEQ");
-        return v && atoi(v) != 0;
-    }();
-    return seq;
-}
-
 int dxrl_pg_gae(int32_t device, const float* rew, const uint8_t* done, const float* values, int64_t num_envs,
                 int64_t horizon, double gamma, double lam, float* adv, float* ret, double* partial, double* stats,
                 void* stream) {
@@ -1302,6 +1484,36 @@ int dxrl_pg_gae_timelimit(int32_t device, const float* rew, const uint16_t* ep_c
     hipLaunchKernelGGL(k_gae_sums_tl, dim3(1), dim3(256), 0, st, reinterpret_cast<const Moments*>(partial), nb, stats,
                        counts);
     return launch_check("k_gae_sums_tl");
+}
+
+int dxrl_pg_gae_vnorm_partial_doubles(int64_t num_envs, int64_t horizon, int64_t* doubles) {
+    DXRL_REQUIRE(doubles && num_envs >= 1 && horizon >= 1, "bad argument");
+    // two Moments triples per workgroup (advantages, then returns); k_gae_lds launches the most
+    *doubles = 2 * 3 * ((num_envs + kGlEnvs - 1) / kGlEnvs);
+    return DXRL_OK;
+}
+
+int dxrl_pg_gae_vnorm(int32_t device, const dxrl_pg_gae_vnorm_args* a, void* stream) {
+    DXRL_REQUIRE(a, "null args");
+    DXRL_REQUIRE(a->rew && a->values && a->adv && a->ret && a->ret_norm && a->values_raw && a->partial && a->stats &&
+                     a->vnorm,
+                 "null argument");
+    DXRL_REQUIRE((a->done != nullptr) != (a->ep_code != nullptr), "exactly one of done and ep_code selects the rule");
+    DXRL_REQUIRE(!a->ep_code || a->counts, "the time-limit rule needs counts");
+    DXRL_REQUIRE(a->num_envs >= 1 && a->horizon >= 1, "num_envs and horizon must be >= 1");
+    DXRL_REQUIRE(a->eps >= 0.0, "eps must be >= 0");
+    DeviceGuard g(device);
+    hipStream_t st = as_stream(stream);
+    if (a->ep_code) return gae_vnorm_launch<true>(a, a->ep_code, st, a->counts + 2);  // the workgroups' pairs
+    return gae_vnorm_launch<false>(a, a->done, st);
+}
+
+int dxrl_pg_vnorm_combine(int32_t device, const double* moments6, int32_t world, double* stats, double* vnorm,
+                          void* stream) {
+    DXRL_REQUIRE(moments6 && stats && vnorm && world >= 1, "bad argument");
+    DeviceGuard g(device);
+    hipLaunchKernelGGL(k_vnorm_combine, dim3(1), dim3(1), 0, as_stream(stream), moments6, world, stats, vnorm);
+    return launch_check("k_vnorm_combine");
 }
 
 int dxrl_pg_adv_combine(int32_t device, const double* moments, int32_t world, double* stats, void* stream) {

@@ -114,6 +114,15 @@ def gather_adv_moments_(out: torch.Tensor, stats: torch.Tensor, world: int, grou
     return all_gather_into_(out, stats[5:8].contiguous(), world, group)
 
 
+def gather_vnorm_moments_(out: torch.Tensor, vnorm: torch.Tensor, world: int, group=None) -> torch.Tensor:
+    """out [world][6] = every rank's (return triple, advantage triple), in rank order: the six
+    contiguous words of the value-normalisation block from batch_count on, as dxrl_pg_gae_vnorm left
+    them (one collective in place of gather_adv_moments_'s)."""
+    from ._native import PG_VNORM
+    lo = PG_VNORM["batch_count"]
+    return all_gather_into_(out, vnorm[lo:lo + 6].contiguous(), world, group)
+
+
 def merge_moments(a, b):
     """Chan, Golub & LeVeque's pairwise update of (count, mean, M2) (csrc/dxrl_pg.hip merge)."""
     if b[0] == 0.0:

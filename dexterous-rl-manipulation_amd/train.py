@@ -28,6 +28,10 @@
                        by the step limit bootstraps with the critic's value of its last observed state (an
                        approximation of the unobserved pre-reset state's); a --resume run keeps its
                        checkpoint's setting
+  --value-norm [--value-norm-eps E]
+                       value normalisation (TrainerConfig.value_norm): the critic learns in normalised units,
+                       the advantages launch decodes its values and encodes its targets with running return
+                       moments kept on the device; a --resume run keeps its checkpoint's setting
   --gpus N [--backend nccl|gloo]
                        a sharded run, one rank per GPU: --envs is the global count, split equally; every
                        rank trains its shard (global env ids rank * n ..) with fit(merge_ranks=True), so
@@ -103,6 +107,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--lr-max", type=float, default=None, metavar="LR")
     p.add_argument("--timeout-bootstrap", action="store_true",
                    help="bootstrap the returns at time-limit episode ends (approximate: V of the last observed state)")
+    p.add_argument("--value-norm", action="store_true",
+                   help="normalise the critic's targets with running return moments (decoded again in GAE)")
+    p.add_argument("--value-norm-eps", type=float, default=None, metavar="E",
+                   help="sigma = sqrt(var + E) (default 1e-5); needs --value-norm")
     p.add_argument("--device", default=None)
     p.add_argument("--gpus", type=int, default=1, metavar="N", help="ranks of a sharded run, one per GPU")
     p.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
@@ -148,6 +156,13 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error(str(e))
     if a.timeout_bootstrap and a.resume is not None:
         p.error("a --resume run keeps the --timeout-bootstrap setting of its checkpoint")
+    if a.value_norm and a.resume is not None:
+        p.error("a --resume run keeps the --value-norm setting of its checkpoint")
+    if a.value_norm_eps is not None:
+        if not a.value_norm:
+            p.error("--value-norm-eps needs --value-norm")
+        if not a.value_norm_eps >= 0.0:
+            p.error("--value-norm-eps must be >= 0")
     if a.converge is not None:
         col, w, thr = a.converge
         if col not in _SCORE_COLUMNS:
@@ -207,6 +222,10 @@ def _build(a, fresh: bool, rank: int = 0, world: int = 1, group=None):
     kw = dict(horizon=a.horizon, epochs=a.epochs, minibatches=a.minibatches, max_steps=a.max_steps, **a.lr_control)
     if a.timeout_bootstrap:
         kw["timeout_bootstrap"] = True
+    if a.value_norm:
+        kw["value_norm"] = True
+        if a.value_norm_eps is not None:
+            kw["value_norm_eps"] = a.value_norm_eps
     if a.config is None:
         w = workloads.WORKLOADS[a.config_name]
         n = (a.envs or w["envs"]) // world

@@ -9,7 +9,8 @@ actor-critic with GAE and policy gradients on top of the same env.  One
      the step kernel (bf16 MFMA), Gaussian sampling, optional fused noise
      injection (robustness_tests.py:140-211), auto-reset, training tape;
   2. critic forward over the T+1 observation blocks (bf16 MFMA GEMMs);
-  3. ``dxrl_pg_gae`` (``dxrl_pg_gae_timelimit`` with ``TrainerConfig.timeout_bootstrap``)
+  3. ``dxrl_pg_gae`` (``dxrl_pg_gae_timelimit`` with ``TrainerConfig.timeout_bootstrap``,
+     ``dxrl_pg_gae_vnorm`` with ``TrainerConfig.value_norm``)
      reverse scan + advantage normalisation from (count, mean, M2)
      moments merged without cancellation (global across ranks: one all-gather of each
      rank's 3 f64, merged in rank order by ``dxrl_pg_adv_combine``);
@@ -33,8 +34,9 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import lr_control
-from .distributed import all_gather_into_, all_reduce_sum_, gather_adv_moments_, global_count, loss_scales
+from . import lr_control, value_norm
+from .distributed import (all_gather_into_, all_reduce_sum_, gather_adv_moments_, gather_vnorm_moments_, global_count,
+                          loss_scales)
 from .envs import VecEnv
 
 # csrc/dxrl_pg.h
@@ -150,6 +152,14 @@ class TrainerConfig:
     # bootstrap as before.  Reads the rollout's episode-end codes (needs success_rule "terminated",
     # whose bit 0 tells the two ends apart); False leaves the trainer's launches as they are.
     timeout_bootstrap: bool = False
+    # value normalisation (value_norm.py, dxrl_pg_gae_vnorm): the critic learns in normalised units;
+    # the advantages launch decodes V with the running mean / std of all raw returns seen before this
+    # iteration and encodes the critic's targets with the same pair, then folds this iteration's
+    # returns into the moments (a device block; no host read).  ret / adv / the log stay raw; the
+    # log's value_mse, which comes from the learner's loss, is then in normalised units (the raw
+    # figure is residual_var).  False leaves the trainer's launches and allocations as they are.
+    value_norm: bool = False
+    value_norm_eps: float = 1e-5  # sigma = sqrt(var + eps)
 
 
 def minibatch_bounds(M: int, B: int, round_samples: int):
@@ -204,6 +214,7 @@ class PGTrainer:
         # executes the same RCCL calls: bench.py --dist, tests/test_gpu_rccl.py)
         self.collective = process_group is not None or world_size > 1
         lr_control.validate_lr_control(cfg)
+        value_norm.validate_value_norm(cfg)
         self.lr_control = lr_control.control_enabled(cfg)  # optimizer_step() is dxrl_pg_adam_step_ctl
         if self.lr_control and self.collective:
             raise ValueError("step-size control (lr_schedule / target_kl) runs on one rank: each rank's KL is its own "
@@ -285,9 +296,15 @@ class PGTrainer:
         self.V = z(OUT if chain else 1, (T + 1) * n)  # the GEMM chain writes all 32 head rows
         self.adv, self.ret = z(M), z(M)
         self.stats = torch.zeros(8, dtype=torch.float64, device=d)
-        self.moments_all = torch.zeros(self.world, 3, dtype=torch.float64, device=d)  # ranks' stats[5..7]
+        # value normalisation: the state block, the critic's targets in normalised units and the
+        # decoded values (tr.V stays the critic's output, tr.ret the raw returns)
+        self.vnorm = N.vnorm_fresh(d) if cfg.value_norm else None
+        self.ret_norm = z(M) if cfg.value_norm else None
+        self.V_raw = z((T + 1) * n) if cfg.value_norm else None
+        # ranks' stats[5..7]; with value_norm their (return triple, advantage triple)
+        self.moments_all = torch.zeros(self.world, 6 if cfg.value_norm else 3, dtype=torch.float64, device=d)
         # shared f64 scratch: the optimiser's 512 grad-norm partials and dxrl_pg_gae's moment triples
-        nb = max(512, N.gae_partial_doubles(n, T))
+        nb = max(512, N.gae_vnorm_partial_doubles(n, T) if cfg.value_norm else N.gae_partial_doubles(n, T))
         self.partial = torch.zeros(nb, dtype=torch.float64, device=d)
         self.dH2 = z(M, H, dt=bf)
         cus = int(torch.cuda.get_device_properties(d).multi_processor_count)
@@ -464,7 +481,7 @@ class PGTrainer:
         f.net, f.train, f.rows = net, int(train), rows
         f.packed, f.params, f.obs = p(self.packed), p(self.params), p(self.obs_rm[start:])
         f.act, f.logp_old, f.adv, f.ret = p(self.act[start:]), p(self.logp[start:]), p(self.adv[start:]), \
-            p(self.ret[start:])
+            p(self.critic_targets[start:])
         f.stats = p(self.stats)
         # each pass is one gradient step on the mean loss over its samples of all ranks (equal
         # shards: rows per rank x world)
@@ -576,8 +593,47 @@ class PGTrainer:
     def _allreduce(self, t):
         all_reduce_sum_(t, self.world, self.pg)
 
+    @property
+    def critic_targets(self):
+        """What the critic's train pass regresses: ret, or ret_norm under value_norm."""
+        return self.ret_norm if self.cfg.value_norm else self.ret
+
+    @property
+    def values_raw(self):
+        """The critic's values in return units [(T + 1) N]: V itself, or V_raw under value_norm."""
+        return self.V_raw if self.cfg.value_norm else self.V[0]
+
+    def _advantages_vnorm(self):
+        c, p = self.cfg, N.ptr
+        a = N.PgGaeVnormArgs()
+        a.rew, a.values = p(self.rew), p(self.V[0])
+        if c.timeout_bootstrap:  # the episode-end codes in place of the done bytes
+            a.ep_code, a.counts = p(self.ep_code), p(self.end_counts)
+        else:
+            a.done = p(self.done)
+        a.num_envs, a.horizon, a.gamma, a.lam, a.eps = self.n, self.T, c.gamma, c.lam, c.value_norm_eps
+        a.adv, a.ret, a.ret_norm, a.values_raw = p(self.adv), p(self.ret), p(self.ret_norm), p(self.V_raw)
+        a.partial, a.stats, a.vnorm = p(self.partial), p(self.stats), p(self.vnorm)
+        a.fold = 0 if self.collective else 1  # ranks fold the merged batch (dxrl_pg_vnorm_combine)
+        N.call("dxrl_pg_gae_vnorm", self.dev.index, C.byref(a), self._s())
+        if self.collective:
+            # one all-gather of six doubles and one combine, where the plain trainer has one of three
+            # and one combine.  The critic's pass reads ret_norm, encoded with the PREVIOUS
+            # iteration's combined state, complete long before: it needs no wait on this exchange
+            # (the actor's pass waits for the advantage moments as before); the next iteration's
+            # dxrl_pg_gae_vnorm follows _join_comm in optimizer_step.
+            with self._on_comm():
+                gather_vnorm_moments_(self.moments_all, self.vnorm, self.world, self.pg)
+                N.call("dxrl_pg_vnorm_combine", self.dev.index, p(self.moments_all), self.world, p(self.stats),
+                       p(self.vnorm), self._s())
+                if self._comm is not None:
+                    self._stats_event.record(self._comm)
+            self._stats_pending = self._comm is not None
+
     def advantages(self):
         c = self.cfg
+        if c.value_norm:
+            return self._advantages_vnorm()
         if c.timeout_bootstrap:  # the episode-end codes in place of the done bytes
             N.call("dxrl_pg_gae_timelimit", self.dev.index, N.ptr(self.rew), N.ptr(self.ep_code), N.ptr(self.V[0]),
                    self.n, self.T, c.gamma, c.lam, N.ptr(self.adv), N.ptr(self.ret), N.ptr(self.partial),
@@ -615,7 +671,7 @@ class PGTrainer:
         c, p = self.cfg, N.ptr
         h = N.PgHeadsArgs()
         h.mu, h.values, h.act, h.logp_old = p(self.mu), p(self.V[0]), p(self.act), p(self.logp)
-        h.adv, h.ret, h.stats, h.params = p(self.adv), p(self.ret), p(self.stats), p(self.params)
+        h.adv, h.ret, h.stats, h.params = p(self.adv), p(self.critic_targets), p(self.stats), p(self.params)
         h.num_samples = self.M
         h.inv_total_samples, h.ent_coef = loss_scales(self.global_M, self.world, c.ent_coef)
         h.clip_eps, h.vf_coef = c.clip_eps, c.vf_coef
@@ -942,6 +998,14 @@ class PGTrainer:
             raise ValueError("timeout_stats() needs TrainerConfig.timeout_bootstrap")
         timeouts, terminations = self.end_counts[:2].tolist()
         return {"timeouts": int(timeouts), "terminations": int(terminations)}
+
+    def value_norm_state(self) -> Dict[str, float]:
+        """The value-normalisation block (value_norm only): the running count / mean / std of all
+        raw returns folded so far, the (mu, sigma) the next iteration decodes and encodes with, the
+        last batch's mean / std and the number of batches folded.  One 128-byte read."""
+        if self.vnorm is None:
+            raise ValueError("value_norm_state() needs TrainerConfig.value_norm")
+        return value_norm.state_dict(self.vnorm.tolist())
 
     def loss_stats(self) -> Dict[str, float]:
         """Loss terms of the last train pass (the last minibatch of the last epoch), per sample of

@@ -1117,7 +1117,7 @@ def log_iteration(tr, st: _RunState, score_col: int, min_episodes: int, conv_col
     a.min_episodes, a.num_params, a.partial_doubles = int(min_episodes), tr.params.numel(), st.partial.numel()
     a.score_col, a.conv_col, a.conv_window, a.conv_threshold = score_col, conv_col, int(window), float(threshold)
     a.ep_count, a.ep_sum_return, a.ep_sum_length = p(tr.ep_count), p(tr.ep_sum_ret), p(tr.ep_sum_len)
-    a.ep_successes, a.rew, a.ret, a.done, a.values = p(tr.ep_succ), p(tr.rew), p(tr.ret), p(tr.done), p(tr.V[0])
+    a.ep_successes, a.rew, a.ret, a.done, a.values = p(tr.ep_succ), p(tr.rew), p(tr.ret), p(tr.done), p(tr.values_raw)
     a.stats, a.loss_partial, a.gnorm2 = p(tr.stats), p(loss), p(tr.gnorm2)
     a.params, a.best_params = p(tr.params), p(st.best_params)
     a.partial, a.log, a.header = p(st.partial), p(st.table), p(st.header)
@@ -1348,6 +1348,8 @@ def save_checkpoint(tr, path):
     }
     if tr.lr_control:  # optional entry: a trainer without step-size control writes the file it always did
         arrays["opt_state"] = host(tr.opt_state)
+    if tr.cfg.value_norm:  # likewise: the running return moments and the next iteration's (mu, sigma)
+        arrays["value_norm_state"] = host(tr.vnorm)
     if st is not None:
         arrays.update(log_table=host(st.table[:st.rows]), log_header=host(st.header),
                       best_params=host(st.best_params))
@@ -1374,11 +1376,12 @@ def save_checkpoint(tr, path):
 
 
 def _trainer_config_state(cfg) -> Dict[str, Any]:
-    """The checkpoint's trainer_config: the dataclass's fields, without the step-size fields and
-    timeout_bootstrap where they sit at their defaults (a trainer without them writes the entry it
-    always did; a missing field loads as its default)."""
+    """The checkpoint's trainer_config: the dataclass's fields, without the step-size fields,
+    timeout_bootstrap and the value-normalisation fields where they sit at their defaults (a trainer
+    without them writes the entry it always did; a missing field loads as its default)."""
     from .lr_control import CONFIG_DEFAULTS
-    later = dict(CONFIG_DEFAULTS, timeout_bootstrap=False)
+    from .value_norm import CONFIG_DEFAULTS as VALUE_NORM_DEFAULTS
+    later = dict(CONFIG_DEFAULTS, timeout_bootstrap=False, **VALUE_NORM_DEFAULTS)
     d = dataclasses.asdict(cfg)
     return {k: v for k, v in d.items() if k not in later or v != later[k]}
 
@@ -1444,6 +1447,8 @@ def load_checkpoint(cls, path, env, process_group=None, world_size: int = 1):
                          f"{', '.join(diff)})")
     cfg = dict(meta["trainer_config"])
     cfg["betas"] = tuple(cfg["betas"])
+    from .value_norm import check_checkpoint
+    check_checkpoint(bool(cfg.get("value_norm", False)), "value_norm_state" in arrays, path)
     tr = cls(env, TrainerConfig(**cfg), process_group=process_group, world_size=world_size)
     if tr.collective and int(meta.get("rank", 0)) != _rank_of(tr):
         raise ValueError(f"{path}: the checkpoint of rank {meta.get('rank', 0)}, loaded on rank {_rank_of(tr)}")
@@ -1464,6 +1469,8 @@ def load_checkpoint(cls, path, env, process_group=None, world_size: int = 1):
     tr.step_count, tr.iteration_index = int(meta["step_count"]), int(meta["iteration_index"])
     if tr.lr_control:
         put(tr.opt_state, "opt_state")
+    if tr.cfg.value_norm:
+        put(tr.vnorm, "value_norm_state")
     if meta["log"] is not None:
         lg = meta["log"]
         st = run_state(tr, int(lg["rows"]))

@@ -440,6 +440,92 @@ int dxrl_pg_gae_timelimit(int32_t device, const float* rew, const uint16_t* ep_c
 /* i64 elements of dxrl_pg_gae_timelimit's `counts` for (num_envs, horizon) (= 2 + 2 ceil(N / 16);
  * host-only query). */
 int dxrl_pg_gae_timelimit_count_words(int64_t num_envs, int64_t horizon, int64_t* words);
+
+/* ---- value normalisation: running return moments in the advantages phase ----------------
+ * The critic works in normalised units; dxrl_pg_gae_vnorm decodes its outputs and encodes its
+ * targets with the running mean / standard deviation of all raw returns seen so far.
+ *
+ * State: vnorm, f64 [DXRL_PG_VNORM_WORDS] on the device (enum below).  A fresh block is all zero
+ * except DXRL_PG_VNORM_MU = 0 and DXRL_PG_VNORM_SIGMA = 1.
+ *
+ * One call under the block's (mu, sigma), both read from the block as f32; all arithmetic f32, in
+ * this order, nothing fused:
+ *   v_t    = sigma * vn_t + mu             for all (T + 1) N critic outputs vn (`values`)
+ *   adv, ret = dxrl_pg_gae (done) or dxrl_pg_gae_timelimit (ep_code) on (rew, tape, v)
+ *   retn_t = (ret_t - mu) / sigma          a true, correctly rounded f32 division (the library is
+ *                                          built with correctly rounded division; no stored 1 / sigma)
+ * Outputs: adv, ret [T N] raw, as those two write them; ret_norm [T N] = retn, what the critic's
+ * train pass regresses; values_raw [(T + 1) N] = v; stats[0..7] as dxrl_pg_gae; counts as
+ * dxrl_pg_gae_timelimit (ep_code only).  Under a fresh block v = 1 * vn + 0 and retn = ret: the
+ * call's adv / ret / stats are the plain entry's bit for bit on values without a -0.0 (which
+ * decodes to +0.0).
+ * Then the fold.  The call's return triple (count, mean, M2 of ret) is reduced as the advantage
+ * triple is -- shifted f64 sums per thread, the workgroup's fixed merge tree, one finishing
+ * workgroup over the partials in the same order -- and written to BATCH_*; stats[5..7] is copied
+ * to ADV_* directly behind it (six contiguous doubles: what ranks exchange).  With fold != 0 the
+ * batch triple is merged into the running triple (dxrl::merge(running, batch)), CALLS grows by
+ * one, and the constants of the NEXT call are refreshed (only when the running count is > 0):
+ *   mu = (float)mean;  sigma = (float)sqrt(M2 / count + eps)     (f64 arithmetic, then narrowed)
+ * so within one call the same (mu, sigma) decode the critic and encode its targets, and the
+ * state lags the data by exactly one call.  eps is stored in the block for dxrl_pg_vnorm_combine.
+ * eps = 0 with constant returns gives sigma = 0: the caller's choice.
+ * Launches: two, as the plain entries (the kernel chosen by horizon as in dxrl_pg_gae,
+ * DXRL_GAE_SEQ included, in its value-normalisation instantiation; then one finishing launch).
+ * partial: f64 [dxrl_pg_gae_vnorm_partial_doubles(N, T)]: the workgroups' advantage triples, then
+ * their return triples.
+ * DXRL_E_INVALID before any launch, outputs untouched: a null pointer (counts may be null with
+ * `done`), both tapes or neither, num_envs or horizon < 1, eps < 0. */
+enum dxrl_pg_vnorm_word {
+    DXRL_PG_VNORM_COUNT = 0,    /* running triple of all raw returns folded so far          */
+    DXRL_PG_VNORM_MEAN,
+    DXRL_PG_VNORM_M2,
+    DXRL_PG_VNORM_MU,           /* f32 constants of the next call, widened to f64           */
+    DXRL_PG_VNORM_SIGMA,
+    DXRL_PG_VNORM_BATCH_COUNT,  /* the last call's return triple                            */
+    DXRL_PG_VNORM_BATCH_MEAN,
+    DXRL_PG_VNORM_BATCH_M2,
+    DXRL_PG_VNORM_ADV_COUNT,    /* copy of the last call's stats[5..7] (after a combine:    */
+    DXRL_PG_VNORM_ADV_MEAN,     /* the ranks' merged advantage triple)                      */
+    DXRL_PG_VNORM_ADV_M2,
+    DXRL_PG_VNORM_CALLS,        /* batches folded                                           */
+    DXRL_PG_VNORM_EPS,          /* eps of the last dxrl_pg_gae_vnorm call                   */
+    DXRL_PG_VNORM_NAMED
+};
+#define DXRL_PG_VNORM_WORDS 16  /* words from DXRL_PG_VNORM_NAMED on are zero */
+typedef struct dxrl_pg_gae_vnorm_args {
+    const float* rew;           /* f32 [T N]                                                */
+    const uint8_t* done;        /* u8 [T N]: the done-byte rule (dxrl_pg_gae), or NULL      */
+    const uint16_t* ep_code;    /* u16 [T N]: the time-limit rule (dxrl_pg_gae_timelimit), or NULL */
+    const float* values;        /* f32 [(T + 1) N] critic outputs, normalised units         */
+    int64_t num_envs, horizon;
+    double gamma, lam, eps;
+    float* adv;                 /* f32 [T N] raw advantages                                 */
+    float* ret;                 /* f32 [T N] raw returns                                    */
+    float* ret_norm;            /* f32 [T N] (ret - mu) / sigma                             */
+    float* values_raw;          /* f32 [(T + 1) N] sigma values + mu                        */
+    double* partial;            /* f64 [dxrl_pg_gae_vnorm_partial_doubles(N, T)]            */
+    double* stats;              /* f64 [8]                                                  */
+    int64_t* counts;            /* ep_code: i64 [dxrl_pg_gae_timelimit_count_words(N, T)]   */
+    double* vnorm;              /* f64 [DXRL_PG_VNORM_WORDS]                                */
+    int32_t fold;               /* 0: write BATCH_* / ADV_* / EPS only (a rank of a sharded
+                                   trainer; dxrl_pg_vnorm_combine folds)                    */
+} dxrl_pg_gae_vnorm_args;
+int dxrl_pg_gae_vnorm(int32_t device, const dxrl_pg_gae_vnorm_args* args, void* stream);
+/* f64 elements of dxrl_pg_gae_vnorm's `partial` for (num_envs, horizon) (= 6 ceil(N / 16);
+ * host-only query). */
+int dxrl_pg_gae_vnorm_partial_doubles(int64_t num_envs, int64_t horizon, int64_t* doubles);
+/* Sharded trainers: moments6 f64 [world][6] in rank order, each row a rank's BATCH_* and ADV_*
+ * words after its own dxrl_pg_gae_vnorm call with fold = 0 (one all-gather).  Writes stats[0..4]
+ * exactly as dxrl_pg_adv_combine would from the rows' advantage triples; merges the return
+ * triples in rank order (from the empty triple) into BATCH_*, writes the merged advantage triple
+ * to ADV_*, and folds BATCH_* into the running state as dxrl_pg_gae_vnorm does with fold != 0,
+ * with the block's EPS.  EPS is the word the last dxrl_pg_gae_vnorm call on the block wrote (eps
+ * is an argument of that call alone): a combine on a fresh block, with no such call before it, folds with
+ * eps = 0, so a caller that combines hand-made rows writes DXRL_PG_VNORM_EPS itself first.  Every
+ * rank ends with the same state bytes; with world = 1 they are the bytes fold = 1 leaves.  One
+ * launch. */
+int dxrl_pg_vnorm_combine(int32_t device, const double* moments6, int32_t world, double* stats, double* vnorm,
+                          void* stream);
 /* Global advantage statistics from every rank's (count, mean, M2) triple -- moments f64
  * [world][3] in rank order (all-gathered stats[5..7]) -- merged in rank order into
  * stats[0] count, [1] sum, [2] mean, [3] sum of squared deviations, [4] unbiased std (what the

@@ -1,0 +1,303 @@
+"""GPU: dxrl_pg_gae_vnorm and dxrl_pg_vnorm_combine (csrc/dxrl_pg.hip: the value-normalisation
+instantiations of k_gae_lds / k_gae, k_gae_sums_vn, k_vnorm_combine) through ctypes against the
+plain entries and the restatement (tests/pg_vnorm_reference.py), at the smallest shapes that reach
+each code path of the two scan kernels, in both tape forms."""
+import ctypes as C
+import itertools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import pg_reference as R
+import pg_vnorm_reference as VN
+
+pytestmark = pytest.mark.gpu
+
+GAMMA, LAM, EPS = 0.99, 0.95, 1e-5
+# k_gae_lds: one chunk with 15 empty segments (1, 8), a chunk boundary (9), fewer chunks than the
+# 16 segments (120), exactly 16 chunks (128), one more (136), the workload's horizon (200), the
+# largest staged horizon (600); a lone env, one full workgroup, a partial second one, three
+LDS_T = (1, 8, 9, 120, 128, 136, 200, 600)
+LDS_N = (1, 16, 17, 40)
+# k_gae: the first horizon whose staging no longer fits the LDS; a lone env, a full wave, one more
+SEQ_T = 601
+SEQ_N = (1, 64, 65)
+CASES = [(n, T) for T in LDS_T for n in LDS_N] + [(n, SEQ_T) for n in SEQ_N]
+FORMS = ("done", "ep_code")
+CANARY = 64
+
+
+@pytest.fixture(scope="module")
+def N():
+    from dexterous_rl_manipulation_amd import _native
+    return _native
+
+
+def test_the_fallback_horizon_is_the_first_past_the_lds():
+    assert SEQ_T == next(T for T in itertools.count(1) if not R.gae_uses_segmented_scan(T))
+
+
+def u16(codes):
+    """An integer tensor of values 0 .. 65535 as the int16 tensor holding those u16 bits."""
+    return torch.from_numpy(codes.numpy().astype(np.uint16).view(np.int16))
+
+
+def data(n, T, seed, v_scale):
+    """rew ~ N(1, 1) (returns with a mean away from 0), V ~ N(0, v_scale), ends at 10 % of the
+    steps: (rew, V, done bytes, u16 codes as int64) on the host."""
+    g = torch.Generator().manual_seed(seed)
+    rew = torch.randn(T * n, generator=g) + 1.0
+    V = torch.randn((T + 1) * n, generator=g) * v_scale
+    assert not ((V == 0) & torch.signbit(V)).any()  # a -0.0 decodes to +0.0
+    ends = torch.rand(T * n, generator=g) < 0.1
+    lengths = torch.randint(1, 1 << 15, (T * n,), generator=g)
+    kind = torch.randint(0, 2, (T * n,), generator=g)
+    return rew, V, ends.to(torch.uint8), torch.where(ends, (lengths << 1) | kind, torch.zeros_like(lengths))
+
+
+def words(N, block):
+    b = block.tolist()
+    return {k: b[i] for k, i in N.PG_VNORM.items()}
+
+
+def triple(w, prefix):
+    return tuple(w[prefix + k] for k in ("count", "mean", "m2"))
+
+
+def running(w):
+    return (w["count"], w["mean"], w["m2"])
+
+
+def close_triple(got, want):
+    return (got[0] == want[0] and math.isclose(got[1], want[1], rel_tol=1e-9, abs_tol=1e-12)
+            and (math.isclose(got[2], want[2], rel_tol=1e-9) if want[0] > 1 else got[2] == 0.0))
+
+
+def run_plain(N, form, rew, tape, V, n, T):
+    """(adv, ret, stats, counts) of dxrl_pg_gae / dxrl_pg_gae_timelimit."""
+    dev = rew.device
+    adv, ret = torch.empty_like(rew), torch.empty_like(rew)
+    part = torch.zeros(N.gae_partial_doubles(n, T), dtype=torch.float64, device=dev)
+    stats = torch.zeros(8, dtype=torch.float64, device=dev)
+    args = [0, N.ptr(rew), N.ptr(tape), N.ptr(V), n, T, GAMMA, LAM, N.ptr(adv), N.ptr(ret), N.ptr(part), N.ptr(stats)]
+    counts = None
+    if form == "ep_code":
+        counts = torch.zeros(N.gae_timelimit_count_words(n, T), dtype=torch.int64, device=dev)
+        args.append(N.ptr(counts))
+    N.call("dxrl_pg_gae" if form == "done" else "dxrl_pg_gae_timelimit", *args, N.stream_of(dev))
+    torch.cuda.synchronize()
+    return adv, ret, stats, counts
+
+
+def vnorm_args(N, form, rew, tape, V, n, T, block, fold, eps=EPS):
+    """(args, outputs): NaN / -7 canaries behind the sized scratch and every output."""
+    dev = rew.device
+    M, need = T * n, N.gae_vnorm_partial_doubles(n, T)
+    assert need == 6 * ((n + 15) // 16)
+    nan = lambda k: torch.full((k + CANARY,), float("nan"), device=dev)  # noqa: E731
+    o = {"adv": nan(M), "ret": nan(M), "ret_norm": nan(M), "values_raw": nan(M + n),
+         "partial": torch.full((need + CANARY,), float("nan"), dtype=torch.float64, device=dev),
+         "stats": torch.zeros(8, dtype=torch.float64, device=dev), "counts": None}
+    a = N.PgGaeVnormArgs()
+    a.rew, a.values = N.ptr(rew), N.ptr(V)
+    if form == "done":
+        a.done = N.ptr(tape)
+    else:
+        o["counts"] = torch.full((N.gae_timelimit_count_words(n, T) + CANARY,), -7, dtype=torch.int64, device=dev)
+        a.ep_code, a.counts = N.ptr(tape), N.ptr(o["counts"])
+    a.num_envs, a.horizon, a.gamma, a.lam, a.eps = n, T, GAMMA, LAM, eps
+    a.adv, a.ret, a.ret_norm, a.values_raw = (N.ptr(o[k]) for k in ("adv", "ret", "ret_norm", "values_raw"))
+    a.partial, a.stats, a.vnorm, a.fold = N.ptr(o["partial"]), N.ptr(o["stats"]), N.ptr(block), fold
+    return a, o
+
+
+def run_vnorm(N, form, rew, tape, V, n, T, block, fold=1):
+    a, o = vnorm_args(N, form, rew, tape, V, n, T, block, fold)
+    N.call("dxrl_pg_gae_vnorm", 0, C.byref(a), N.stream_of(rew.device))
+    torch.cuda.synchronize()
+    M = T * n
+    for k, size in (("adv", M), ("ret", M), ("ret_norm", M), ("values_raw", M + n),
+                    ("partial", N.gae_vnorm_partial_doubles(n, T))):
+        assert torch.isnan(o[k][size:]).all(), f"dxrl_pg_gae_vnorm wrote past {k}"
+        # two triples per launched workgroup: 16 envs each in k_gae_lds, 64 in k_gae
+        written = 6 * (-(-n // (16 if T < SEQ_T else 64))) if k == "partial" else size
+        assert not torch.isnan(o[k][:written]).any(), f"dxrl_pg_gae_vnorm left {k} unwritten"
+        o[k] = o[k][:size]
+    if o["counts"] is not None:
+        size = N.gae_timelimit_count_words(n, T)
+        assert (o["counts"][size:] == -7).all(), "dxrl_pg_gae_vnorm wrote past counts"
+        o["counts"] = o["counts"][:size]
+    return o
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("n,T", CASES)
+def test_vnorm_gae_fresh_prepared_and_unfolded(N, n, T, form):
+    """Three calls on one block.
+    1. Fresh state: adv / ret / stats / counts are the plain entry's on the same inputs bit for bit,
+       ret_norm == ret, values_raw == values; the batch triple is the two-pass f64 triple of ret to
+       the 1e-9 the advantage moments are held to; the running triple is the batch triple.
+    2. The state that fold left (mu, sigma: f32 roundings of moments of random data): adv / ret /
+       ret_norm / values_raw are the restatement's under the (mu, sigma) read from the block, bit for
+       bit; the new running triple is merge_moments(old running, new batch) and (mu, sigma) are
+       (float)mean and (float)sqrt(M2 / count + eps), bit for bit, all read back.
+    3. fold = 0: the running triple, mu, sigma and the call count stay; the batch words are
+       written."""
+    dev = torch.device("cuda", 0)
+    timelimit = form == "ep_code"
+    block = N.vnorm_fresh(dev)
+    # 1
+    rew_h, V_h, done_h, code_h = data(n, T, n * 1000 + T, 50.0)
+    tape = (u16(code_h) if timelimit else done_h).to(dev)
+    rew, V = rew_h.to(dev), V_h.to(dev)
+    o = run_vnorm(N, form, rew, tape, V, n, T, block)
+    adv, ret, stats, counts = run_plain(N, form, rew, tape, V, n, T)
+    assert torch.equal(o["adv"], adv) and torch.equal(o["ret"], ret) and torch.equal(o["stats"], stats)
+    # the sums and one pair per launched workgroup (16 envs each in k_gae_lds, 64 in k_gae)
+    pairs = 2 + 2 * (-(-n // (16 if T < SEQ_T else 64)))
+    assert counts is None or torch.equal(o["counts"][:pairs], counts[:pairs])
+    assert torch.equal(o["ret_norm"], ret) and torch.equal(o["values_raw"], V)
+    w1 = words(N, block)
+    assert close_triple(triple(w1, "batch_"), VN.batch_triple(ret)), (triple(w1, "batch_"), VN.batch_triple(ret))
+    assert running(w1) == triple(w1, "batch_") and triple(w1, "adv_") == tuple(stats[5:8].tolist())
+    assert w1["calls"] == 1.0 and w1["eps"] == EPS
+    assert (w1["mu"], w1["sigma"]) == VN.constants(running(w1), EPS)
+    assert w1["mu"] != 0.0 and w1["sigma"] != 1.0  # a condition on the input of step 2
+    # 2
+    rew_h, V_h, done_h, code_h = data(n, T, n * 1000 + T + 7, 1.0)  # critic outputs in normalised units
+    tape_h = code_h if timelimit else done_h
+    tape = (u16(code_h) if timelimit else done_h).to(dev)
+    rew, V = rew_h.to(dev), V_h.to(dev)
+    o = run_vnorm(N, form, rew, tape, V, n, T, block)
+    a_ref, r_ref, rn_ref, v_ref = VN.gae_vnorm(rew_h, tape_h, V_h, n, T, GAMMA, LAM, w1["mu"], w1["sigma"],
+                                               timelimit=timelimit)
+    assert torch.equal(o["values_raw"].cpu(), v_ref) and torch.equal(o["adv"].cpu(), a_ref)
+    assert torch.equal(o["ret"].cpu(), r_ref) and torch.equal(o["ret_norm"].cpu(), rn_ref)
+    w2 = words(N, block)
+    assert close_triple(triple(w2, "batch_"), VN.batch_triple(o["ret"]))
+    want = VN.fold({"running": running(w1), "mu": w1["mu"], "sigma": w1["sigma"], "calls": 1}, triple(w2, "batch_"), EPS)
+    assert running(w2) == want["running"] and (w2["mu"], w2["sigma"]) == (want["mu"], want["sigma"])
+    assert w2["calls"] == 2.0 and triple(w2, "adv_") == tuple(o["stats"][5:8].tolist())
+    # 3
+    o = run_vnorm(N, form, rew, tape, V, n, T, block, fold=0)
+    w3 = words(N, block)
+    assert running(w3) == running(w2) and (w3["mu"], w3["sigma"], w3["calls"]) == (w2["mu"], w2["sigma"], 2.0)
+    assert close_triple(triple(w3, "batch_"), VN.batch_triple(o["ret"]))
+    assert triple(w3, "batch_") != triple(w2, "batch_") or n * T == 1  # decoded with another pair
+    assert triple(w3, "adv_") == tuple(o["stats"][5:8].tolist())
+    assert all(x == 0.0 for x in block.tolist()[N.PG_VNORM_NAMED:])
+
+
+def prepared_block(N, dev):
+    block = N.vnorm_fresh(dev)
+    for k, v in (("count", 8000.0), ("mean", 34.123456789), ("m2", 8000.0 * 120.5), ("mu", float(np.float32(34.1))),
+                 ("sigma", float(np.float32(10.9))), ("calls", 5.0), ("eps", EPS)):
+        block[N.PG_VNORM[k]] = v
+    return block
+
+
+ROWS = {1: [[800.0, 33.5, 91000.25, 800.0, 0.125, 5000.5]],
+        2: [[640.0, 35.25, 70000.5, 640.0, -0.5, 4100.0], [960.0, 31.0, 99000.0, 960.0, 0.75, 7000.125]],
+        # a rank without samples in the middle
+        3: [[640.0, 35.25, 70000.5, 640.0, -0.5, 4100.0], [0.0, 0.0, 0.0, 0.0, 0.0, 0.0],
+            [320.0, 36.5, 30000.0, 320.0, 0.25, 2000.0]]}
+
+
+@pytest.mark.parametrize("world", sorted(ROWS))
+def test_vnorm_combine_is_the_rank_order_merge(N, world):
+    """stats[0..4] are dxrl_pg_adv_combine's bytes on the rows' advantage triples; the batch and
+    advantage words are the rank-order merges, the running triple merge_moments(old, batch) and
+    (mu, sigma) its constants under the block's eps, bit for bit."""
+    dev = torch.device("cuda", 0)
+    rows = torch.tensor(ROWS[world], dtype=torch.float64)
+    block = prepared_block(N, dev)
+    w0 = words(N, block)
+    stats = torch.full((8,), -3.0, dtype=torch.float64, device=dev)
+    N.call("dxrl_pg_vnorm_combine", 0, N.ptr(rows.to(dev)), world, N.ptr(stats), N.ptr(block), N.stream_of(dev))
+    ref = torch.full((8,), -3.0, dtype=torch.float64, device=dev)
+    N.call("dxrl_pg_adv_combine", 0, N.ptr(rows[:, 3:].contiguous().to(dev)), world, N.ptr(ref), N.stream_of(dev))
+    torch.cuda.synchronize()
+    assert torch.equal(stats, ref) and (stats[5:] == -3.0).all()
+    w = words(N, block)
+    batch = VN.merge_rows(rows[:, :3].tolist())
+    assert triple(w, "batch_") == batch and triple(w, "adv_") == VN.merge_rows(rows[:, 3:].tolist())
+    want = VN.fold({"running": running(w0), "mu": w0["mu"], "sigma": w0["sigma"], "calls": 5}, batch, EPS)
+    assert running(w) == want["running"] and (w["mu"], w["sigma"]) == (want["mu"], want["sigma"])
+    assert w["calls"] == 6.0 and w["eps"] == EPS
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_unfolded_call_and_combine_of_one_rank_is_the_folded_call(N, form):
+    """world = 1: fold = 0 followed by dxrl_pg_vnorm_combine on the block's own six words leaves the
+    block and the stats that fold = 1 leaves, byte for byte."""
+    dev = torch.device("cuda", 0)
+    n, T = 40, 136
+    rew_h, V_h, done_h, code_h = data(n, T, 99, 1.0)
+    tape = (u16(code_h) if form == "ep_code" else done_h).to(dev)
+    rew, V = rew_h.to(dev), V_h.to(dev)
+    folded, split = prepared_block(N, dev), prepared_block(N, dev)
+    o1 = run_vnorm(N, form, rew, tape, V, n, T, folded, fold=1)
+    o0 = run_vnorm(N, form, rew, tape, V, n, T, split, fold=0)
+    lo = N.PG_VNORM["batch_count"]
+    N.call("dxrl_pg_vnorm_combine", 0, N.ptr(split[lo:lo + 6].clone()), 1, N.ptr(o0["stats"]), N.ptr(split),
+           N.stream_of(dev))
+    torch.cuda.synchronize()
+    assert torch.equal(folded, split) and torch.equal(o1["stats"], o0["stats"])
+    assert torch.equal(o1["ret_norm"], o0["ret_norm"]) and words(N, folded)["calls"] == 6.0
+
+
+def test_invalid_arguments_leave_outputs_and_block_untouched(N):
+    """A null pointer, both tapes or neither, the time-limit rule without counts, num_envs or
+    horizon < 1, eps < 0 (or NaN): DXRL_E_INVALID before any launch."""
+    dev = torch.device("cuda", 0)
+    n, T = 17, 9
+    rew_h, V_h, done_h, code_h = data(n, T, 5, 1.0)
+    rew, V, done, code = rew_h.to(dev), V_h.to(dev), done_h.to(dev), u16(code_h).to(dev)
+    block = prepared_block(N, dev)
+    before = block.clone()
+    fn = N.lib().dxrl_pg_gae_vnorm
+    made = []
+
+    def refused(form, **changes):
+        a, o = vnorm_args(N, form, rew, code if form == "ep_code" else done, V, n, T, block, 1)
+        o["stats"].fill_(6.0)
+        for k, v in changes.items():
+            setattr(a, k, v)
+        assert fn(0, C.byref(a), N.stream_of(dev)) == N.DXRL_E_INVALID, (form, changes)
+        with pytest.raises(ValueError):
+            N.call("dxrl_pg_gae_vnorm", 0, C.byref(a), N.stream_of(dev))
+        made.append(o)
+
+    for k in ("rew", "values", "adv", "ret", "ret_norm", "values_raw", "partial", "stats", "vnorm"):
+        refused("done", **{k: None})
+        refused("ep_code", **{k: None})
+    refused("done", done=None)                # neither tape
+    refused("done", ep_code=N.ptr(code))      # both (counts null)
+    refused("ep_code", done=N.ptr(done))      # both
+    refused("ep_code", counts=None)
+    for k, v in (("num_envs", 0), ("num_envs", -1), ("horizon", 0), ("horizon", -3), ("eps", -1e-9),
+                 ("eps", float("nan"))):
+        refused("done", **{k: v})
+    assert fn(0, None, N.stream_of(dev)) == N.DXRL_E_INVALID
+    torch.cuda.synchronize()
+    for o in made:
+        assert all(torch.isnan(o[k]).all() for k in ("adv", "ret", "ret_norm", "values_raw", "partial"))
+        assert (o["stats"] == 6.0).all() and (o["counts"] is None or (o["counts"] == -7).all())
+    assert torch.equal(block, before)
+    out = C.c_int64(-1)
+    for a, b, p in ((0, 5, C.byref(out)), (5, 0, C.byref(out)), (5, 5, None)):
+        assert N.lib().dxrl_pg_gae_vnorm_partial_doubles(a, b, p) == N.DXRL_E_INVALID
+    assert out.value == -1
+    stats = torch.full((8,), 6.0, dtype=torch.float64, device=dev)
+    rows = torch.ones(6, dtype=torch.float64, device=dev)
+    comb = N.lib().dxrl_pg_vnorm_combine
+    for args in ((None, 1, N.ptr(stats), N.ptr(block)), (N.ptr(rows), 0, N.ptr(stats), N.ptr(block)),
+                 (N.ptr(rows), 1, None, N.ptr(block)), (N.ptr(rows), 1, N.ptr(stats), None)):
+        assert comb(0, *args, N.stream_of(dev)) == N.DXRL_E_INVALID
+    torch.cuda.synchronize()
+    assert torch.equal(block, before) and (stats == 6.0).all()
+    # and the same arguments, all valid, run
+    o = run_vnorm(N, "ep_code", rew, code, V, n, T, block)
+    assert not torch.equal(block, before) and words(N, block)["calls"] == 6.0
