@@ -374,10 +374,25 @@ class PgGaeVnormArgs(C.Structure):
 
 
 PG_VNORM_NAMES = ("count", "mean", "m2", "mu", "sigma", "batch_count", "batch_mean", "batch_m2", "adv_count",
-                  "adv_mean", "adv_m2", "calls", "eps")
+                  "adv_mean", "adv_m2", "calls", "eps", "forget")
 PG_VNORM_NAMED = len(PG_VNORM_NAMES)  # DXRL_PG_VNORM_NAMED
 PG_VNORM_WORDS = 16                   # DXRL_PG_VNORM_WORDS
 PG_VNORM = {k: i for i, k in enumerate(PG_VNORM_NAMES)}
+
+
+# dxrl_pg_popart_rescale: the args struct, the words of its state block (enum dxrl_pg_popart_word)
+# and the columns of the row it writes (enum dxrl_pg_vnorm_log_col)
+class PgPopartArgs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("params", "packed", "vnorm", "popart", "row_out")]
+
+
+PG_POPART_NAMES = ("mu_head", "sigma_head", "rescales", "skipped", "last_scale", "last_shift")
+PG_POPART_NAMED = len(PG_POPART_NAMES)  # DXRL_PG_POPART_NAMED
+PG_POPART_WORDS = 8                     # DXRL_PG_POPART_WORDS
+PG_POPART = {k: i for i, k in enumerate(PG_POPART_NAMES)}
+PG_VNORM_LOG_COLUMNS = ("mu", "sigma", "mu_prev", "sigma_prev", "scale", "shift", "rescaled", "count", "mean", "std",
+                        "batch_mean", "batch_std", "calls", "forget")
+PG_VNORM_LOG_COLS = len(PG_VNORM_LOG_COLUMNS)  # DXRL_PG_VNORM_LOG_COLS
 
 
 # the structs added after tests/test_native_abi.py fixed its list: (C name, mirror), sized against
@@ -386,7 +401,8 @@ LATER_STRUCTS = (("dxrl_pg_log_args", PgLogArgs), ("dxrl_pg_log_header", PgLogHe
                  ("dxrl_pg_val_args", PgValArgs), ("dxrl_pg_val_header", PgValHeader),
                  ("dxrl_pg_val_levels_args", PgValLevelsArgs), ("dxrl_pg_val_paired_args", PgValPairedArgs),
                  ("dxrl_pg_val_failure_args", PgValFailureArgs), ("dxrl_pg_runs_spec", PgRunsSpec),
-                 ("dxrl_pg_runs_args", PgRunsArgs), ("dxrl_pg_gae_vnorm_args", PgGaeVnormArgs))
+                 ("dxrl_pg_runs_args", PgRunsArgs), ("dxrl_pg_gae_vnorm_args", PgGaeVnormArgs),
+                 ("dxrl_pg_popart_args", PgPopartArgs))
 
 _P = C.c_void_p
 _I32,_I64, _F64 = C.c_int32, C.c_int64, C.c_double
@@ -429,6 +445,7 @@ _SIGS = {
     "dxrl_pg_gae_vnorm": (C.c_int, [_I32, C.POINTER(PgGaeVnormArgs), _P]),
     "dxrl_pg_gae_vnorm_partial_doubles": (C.c_int, [_I64, _I64, C.POINTER(_I64)]),
     "dxrl_pg_vnorm_combine": (C.c_int, [_I32, _P, _I32, _P, _P, _P]),
+    "dxrl_pg_popart_rescale": (C.c_int, [_I32, C.POINTER(PgPopartArgs), _P]),
     "dxrl_pg_adv_finalize": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P]),
     "dxrl_pg_adv_combine": (C.c_int, [_I32, _P, _I32, _P, _P]),
     "dxrl_pg_heads": (C.c_int, [_I32, C.POINTER(PgHeadsArgs), _P]),
@@ -544,6 +561,14 @@ def vnorm_fresh(device=None):
     import torch
     t = torch.zeros(PG_VNORM_WORDS, dtype=torch.float64)
     t[PG_VNORM["sigma"]] = 1.0
+    return t if device is None else t.to(device)
+
+
+def popart_fresh(device=None):
+    """A fresh dxrl_pg_popart_rescale state block: f64 [PG_POPART_WORDS], all zero but sigma_head = 1."""
+    import torch
+    t = torch.zeros(PG_POPART_WORDS, dtype=torch.float64)
+    t[PG_POPART["sigma_head"]] = 1.0
     return t if device is None else t.to(device)
 
 

@@ -728,9 +728,13 @@ __global__ void k_gae_sums_tl(const Moments* __restrict__ partial, int nb, doubl
     gae_sums_tl(partial, nb, stats, counts);
 }
 // Value normalisation: one batch of returns folded into the block's running triple, and the next
-// call's constants from it (one thread; include/dxrl.h states the words).
+// call's constants from it (one thread; include/dxrl.h states the words).  The running triple is
+// discounted first with d = 1 - FORGET (count and M2; the mean stays): d = 1 on a block without
+// forgetting, which multiplies exactly.
 __device__ __forceinline__ void vnorm_fold(double* __restrict__ vn, Moments batch, double eps) {
-    const Moments run = merge(Moments{vn[DXRL_PG_VNORM_COUNT], vn[DXRL_PG_VNORM_MEAN], vn[DXRL_PG_VNORM_M2]}, batch);
+    const double d = 1.0 - vn[DXRL_PG_VNORM_FORGET];
+    const Moments run =
+        merge(Moments{d * vn[DXRL_PG_VNORM_COUNT], vn[DXRL_PG_VNORM_MEAN], d * vn[DXRL_PG_VNORM_M2]}, batch);
     vn[DXRL_PG_VNORM_COUNT] = run.n;
     vn[DXRL_PG_VNORM_MEAN] = run.mean;
     vn[DXRL_PG_VNORM_M2] = run.m2;
@@ -1242,6 +1246,65 @@ __global__ __launch_bounds__(256) void k_adam_pack_ctl(AdamCtlArgs x) {
     adam_pack_element(a, j, clip_scale(g2, a.max_norm), (float)lr, bc1, bc2);
 }
 
+// dxrl_pg_popart_rescale (include/dxrl.h states the arithmetic and the three cases): one workgroup,
+// thread j < 257 owns element j of the critic head's row 0 (256 weights, then the bias) and
+// scatters the new value into its packed copies with pack_scatter, as the optimiser does.  Every
+// thread reads both pairs and takes the same branch; thread 0 writes the block and the row behind
+// a barrier, after every thread has read the words it replaces.
+constexpr int kPopartThreads = 320;  // >= kH + 1 head elements, whole waves
+__device__ __forceinline__ double popart_std(double n, double m2) { return n > 0.0 ? sqrt(m2 / n) : 0.0; }
+__global__ __launch_bounds__(kPopartThreads) void k_popart_rescale(float* __restrict__ params, bf16* __restrict__ w,
+                                                                    const double* __restrict__ vn,
+                                                                    double* __restrict__ pa,
+                                                                    double* __restrict__ row) {
+    const double mu_h = pa[DXRL_PG_POPART_MU_HEAD], sigma_h = pa[DXRL_PG_POPART_SIGMA_HEAD];
+    const double mu_n = vn[DXRL_PG_VNORM_MU], sigma_n = vn[DXRL_PG_VNORM_SIGMA];
+    const bool lead = threadIdx.x == 0;
+    const bool usable = isfinite(mu_h) && isfinite(mu_n) && isfinite(sigma_h) && isfinite(sigma_n) && sigma_h > 0.0 &&
+                        sigma_n > 0.0;
+    if (!usable) {  // (only thread 0 reads SKIPPED: no barrier needed)
+        if (lead) pa[DXRL_PG_POPART_SKIPPED] += 1.0;
+        return;
+    }
+    const bool same = __double_as_longlong(mu_h) == __double_as_longlong(mu_n) &&
+                      __double_as_longlong(sigma_h) == __double_as_longlong(sigma_n);
+    const double s = same ? 1.0 : sigma_h / sigma_n;
+    const double shift = same ? 0.0 : (mu_h - mu_n) / sigma_n;
+    if (!same) {
+        const int j = (int)threadIdx.x;
+        if (j <= kH) {
+            const double x = (double)params[kOffW3c + j];
+            const float y = j < kH ? (float)(x * s) : (float)((sigma_h * x + (mu_h - mu_n)) / sigma_n);
+            params[kOffW3c + j] = y;
+            pack_scatter(kOffW3c + j, y, w);
+        }
+        __syncthreads();  // every thread holds the old pair before thread 0 replaces it
+        if (lead) {
+            pa[DXRL_PG_POPART_MU_HEAD] = mu_n;
+            pa[DXRL_PG_POPART_SIGMA_HEAD] = sigma_n;
+            pa[DXRL_PG_POPART_RESCALES] += 1.0;
+            pa[DXRL_PG_POPART_LAST_SCALE] = s;
+            pa[DXRL_PG_POPART_LAST_SHIFT] = shift;
+        }
+    }
+    if (lead && row) {
+        row[DXRL_PG_VNORM_LOG_MU] = mu_n;
+        row[DXRL_PG_VNORM_LOG_SIGMA] = sigma_n;
+        row[DXRL_PG_VNORM_LOG_MU_PREV] = mu_h;
+        row[DXRL_PG_VNORM_LOG_SIGMA_PREV] = sigma_h;
+        row[DXRL_PG_VNORM_LOG_SCALE] = s;
+        row[DXRL_PG_VNORM_LOG_SHIFT] = shift;
+        row[DXRL_PG_VNORM_LOG_RESCALED] = same ? 0.0 : 1.0;
+        row[DXRL_PG_VNORM_LOG_COUNT] = vn[DXRL_PG_VNORM_COUNT];
+        row[DXRL_PG_VNORM_LOG_MEAN] = vn[DXRL_PG_VNORM_MEAN];
+        row[DXRL_PG_VNORM_LOG_STD] = popart_std(vn[DXRL_PG_VNORM_COUNT], vn[DXRL_PG_VNORM_M2]);
+        row[DXRL_PG_VNORM_LOG_BATCH_MEAN] = vn[DXRL_PG_VNORM_BATCH_MEAN];
+        row[DXRL_PG_VNORM_LOG_BATCH_STD] = popart_std(vn[DXRL_PG_VNORM_BATCH_COUNT], vn[DXRL_PG_VNORM_BATCH_M2]);
+        row[DXRL_PG_VNORM_LOG_CALLS] = vn[DXRL_PG_VNORM_CALLS];
+        row[DXRL_PG_VNORM_LOG_FORGET] = vn[DXRL_PG_VNORM_FORGET];
+    }
+}
+
 static int reduce_to(const double* partial, int nb, double* out, int slot, hipStream_t st) {
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, partial, nb, out, slot);
     return launch_check("k_sum_partials");
@@ -1514,6 +1577,15 @@ int dxrl_pg_vnorm_combine(int32_t device, const double* moments6, int32_t world,
     DeviceGuard g(device);
     hipLaunchKernelGGL(k_vnorm_combine, dim3(1), dim3(1), 0, as_stream(stream), moments6, world, stats, vnorm);
     return launch_check("k_vnorm_combine");
+}
+
+int dxrl_pg_popart_rescale(int32_t device, const dxrl_pg_popart_args* a, void* stream) {
+    DXRL_REQUIRE(a, "null args");
+    DXRL_REQUIRE(a->params && a->packed && a->vnorm && a->popart, "null argument");
+    DeviceGuard g(device);
+    hipLaunchKernelGGL(k_popart_rescale, dim3(1), dim3(kPopartThreads), 0, as_stream(stream), a->params,
+                       static_cast<bf16*>(a->packed), a->vnorm, a->popart, a->row_out);
+    return launch_check("k_popart_rescale");
 }
 
 int dxrl_pg_adv_combine(int32_t device, const double* moments, int32_t world, double* stats, void* stream) {

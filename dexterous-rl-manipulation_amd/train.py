@@ -32,6 +32,10 @@
                        value normalisation (TrainerConfig.value_norm): the critic learns in normalised units,
                        the advantages launch decodes its values and encodes its targets with running return
                        moments kept on the device; a --resume run keeps its checkpoint's setting
+  --popart [--value-norm-forget F]
+                       with --value-norm: PopArt (TrainerConfig.popart) rescales the critic's head when the
+                       moments move, so its decoded values stay; F in [0, 1) is the forgetting factor of the
+                       moments (TrainerConfig.value_norm_forget); a --resume run keeps its checkpoint's settings
   --gpus N [--backend nccl|gloo]
                        a sharded run, one rank per GPU: --envs is the global count, split equally; every
                        rank trains its shard (global env ids rank * n ..) with fit(merge_ranks=True), so
@@ -111,6 +115,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                    help="normalise the critic's targets with running return moments (decoded again in GAE)")
     p.add_argument("--value-norm-eps", type=float, default=None, metavar="E",
                    help="sigma = sqrt(var + E) (default 1e-5); needs --value-norm")
+    p.add_argument("--popart", action="store_true",
+                   help="rescale the critic's head when the value-normalisation moments move; needs --value-norm")
+    p.add_argument("--value-norm-forget", type=float, default=None, metavar="F",
+                   help="forgetting factor of the running return moments, in [0, 1); needs --value-norm")
     p.add_argument("--device", default=None)
     p.add_argument("--gpus", type=int, default=1, metavar="N", help="ranks of a sharded run, one per GPU")
     p.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
@@ -163,6 +171,13 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             p.error("--value-norm-eps needs --value-norm")
         if not a.value_norm_eps >= 0.0:
             p.error("--value-norm-eps must be >= 0")
+    if a.popart or a.value_norm_forget is not None:
+        if a.resume is not None:
+            p.error("a --resume run keeps the --popart / --value-norm-forget settings of its checkpoint")
+        if not a.value_norm:
+            p.error("--popart and --value-norm-forget need --value-norm")
+        if a.value_norm_forget is not None and not 0.0 <= a.value_norm_forget < 1.0:
+            p.error("--value-norm-forget must be in [0, 1)")
     if a.converge is not None:
         col, w, thr = a.converge
         if col not in _SCORE_COLUMNS:
@@ -226,6 +241,10 @@ def _build(a, fresh: bool, rank: int = 0, world: int = 1, group=None):
         kw["value_norm"] = True
         if a.value_norm_eps is not None:
             kw["value_norm_eps"] = a.value_norm_eps
+        if a.popart:
+            kw["popart"] = True
+        if a.value_norm_forget is not None:
+            kw["value_norm_forget"] = a.value_norm_forget
     if a.config is None:
         w = workloads.WORKLOADS[a.config_name]
         n = (a.envs or w["envs"]) // world

@@ -19,7 +19,9 @@ actor-critic with GAE and policy gradients on top of the same env.  One
      split-K over samples with the bias as an extra ones-row);
   6. the f32 gradient SUM all-reduce over RCCL (world > 1), in two halves on a side stream:
      the critic's beside the actor's train pass, the actor's before Adam;
-  7. global-norm clip + Adam on the f32 master, bf16 repack.
+  7. global-norm clip + Adam on the f32 master, bf16 repack;
+  8. with ``TrainerConfig.popart``: ``dxrl_pg_popart_rescale``, the critic's head into the units
+     of the (mu, sigma) that step 3 left for the next iteration.
 
 Every matrix contraction runs in libdxrl.so; torch only owns the buffers.
 """
@@ -160,6 +162,14 @@ class TrainerConfig:
     # figure is residual_var).  False leaves the trainer's launches and allocations as they are.
     value_norm: bool = False
     value_norm_eps: float = 1e-5  # sigma = sqrt(var + eps)
+    # PopArt (needs value_norm; dxrl_pg_popart_rescale): when the iteration's fold moves (mu, sigma),
+    # the critic's head is rescaled at the end of the iteration so that every decoded value stays
+    # what it was; without it the critic re-learns the shift.  Adam's moments of the head are left.
+    popart: bool = False
+    # forgetting factor of the running return moments, in [0, 1) (needs value_norm): each fold first
+    # discounts the running count and M2 by 1 - forget, so the effective count settles near one
+    # batch / forget and late returns keep their weight.  0: pooled moments, as before.
+    value_norm_forget: float = 0.0
 
 
 def minibatch_bounds(M: int, B: int, round_samples: int):
@@ -299,6 +309,12 @@ class PGTrainer:
         # value normalisation: the state block, the critic's targets in normalised units and the
         # decoded values (tr.V stays the critic's output, tr.ret the raw returns)
         self.vnorm = N.vnorm_fresh(d) if cfg.value_norm else None
+        if cfg.value_norm_forget:  # the block's owner sets the word; no entry writes it
+            self.vnorm[N.PG_VNORM["forget"]] = cfg.value_norm_forget
+        # PopArt: the units the critic's head puts out, and where the iteration's rescale writes its
+        # row (fit() points it into its table; None: no row)
+        self.popart = N.popart_fresh(d) if cfg.popart else None
+        self._vnorm_row_target = None
         self.ret_norm = z(M) if cfg.value_norm else None
         self.V_raw = z((T + 1) * n) if cfg.value_norm else None
         # ranks' stats[5..7]; with value_norm their (return triple, advantage triple)
@@ -630,6 +646,18 @@ class PGTrainer:
                     self._stats_event.record(self._comm)
             self._stats_pending = self._comm is not None
 
+    def popart_rescale(self):
+        """dxrl_pg_popart_rescale: the critic's head (master and pack) from the units the popart
+        block names into the vnorm block's current (mu, sigma); a no-op on the device when they are
+        the same pair.  Every rank of a sharded trainer holds the same two blocks and the same head,
+        so each runs the same launch."""
+        if self._stats_pending:  # the ranks' combine writes the vnorm block on the comm stream
+            self._join_comm()
+        a, p = N.PgPopartArgs(), N.ptr
+        a.params, a.packed, a.vnorm, a.popart = p(self.params), p(self.packed), p(self.vnorm), p(self.popart)
+        a.row_out = p(self._vnorm_row_target)
+        N.call("dxrl_pg_popart_rescale", self.dev.index, C.byref(a), self._s())
+
     def advantages(self):
         c = self.cfg
         if c.value_norm:
@@ -931,6 +959,12 @@ class PGTrainer:
             self._update_follows = True
         if not update:
             self._join_comm()  # nothing of this iteration's exchanges stays in flight
+        if self.popart is not None:
+            # behind every train pass of the iteration (their targets were encoded with the old
+            # pair) and the ranks' combine (joined above or in optimizer_step), ahead of the next
+            # critic-values pass
+            with profiling.range_("pg.popart_rescale") if marks else _null():
+                self.popart_rescale()
         self.iteration_index += 1
 
     # ------------------------------------------------------------------ training runs (training_run.py)
@@ -1006,6 +1040,13 @@ class PGTrainer:
         if self.vnorm is None:
             raise ValueError("value_norm_state() needs TrainerConfig.value_norm")
         return value_norm.state_dict(self.vnorm.tolist())
+
+    def popart_state(self) -> Dict[str, float]:
+        """The PopArt block (popart only): the (mu, sigma) whose units the critic's head puts out,
+        the rescales done and refused, and the last rescale's scale and shift.  One 64-byte read."""
+        if self.popart is None:
+            raise ValueError("popart_state() needs TrainerConfig.popart")
+        return value_norm.popart_dict(self.popart.tolist())
 
     def loss_stats(self) -> Dict[str, float]:
         """Loss terms of the last train pass (the last minibatch of the last epoch), per sample of

@@ -43,6 +43,11 @@ third device table, ``log.optimizer``: the last ``dxrl_pg_adam_step_ctl`` launch
 writes the iteration's row (learning rate, updates applied / skipped, stop pass, KLs, next scale)
 straight into it.  The table and the trainer's device state block ride the JSON and the checkpoint
 as optional entries.
+
+On a trainer with ``TrainerConfig.popart`` the run likewise keeps ``log.value_norm``: the
+``dxrl_pg_popart_rescale`` launch that ends every iteration writes the row (the new and the previous
+(mu, sigma), the head's scale and shift, the running and the batch moments).  ``value_mse`` of the
+main table is in normalised units under ``value_norm``; ``sigma`` of this table is the factor.
 """
 from __future__ import annotations
 
@@ -68,6 +73,8 @@ RANK_COLUMNS = N.PG_LOG_RANK_COLUMNS    # the named entries of a rank record (fi
 RANK_DOUBLES = N.PG_LOG_RANK_DOUBLES
 _MIN_CAP = 256
 OPT_COLUMNS = N.PG_OPT_COLUMNS          # the named columns of log.optimizer (step-size control)
+VNORM_COLUMNS = N.PG_VNORM_LOG_COLUMNS  # the named columns of log.value_norm (popart)
+VNORM_COLS = N.PG_VNORM_LOG_COLS
 OPT_COLS = N.PG_OPT_COLS
 VAL_COLUMNS = N.PG_VAL_COLUMNS
 VAL_COLS = N.PG_VAL_COLS
@@ -132,6 +139,37 @@ class OptimizerLog:
         return self.table.shape[0]
 
 
+# ====================================================================== ValueNormLog
+class ValueNormLog:
+    """The value-normalisation rows of a run on a trainer with popart: f64 [rows][14], one row per
+    logged iteration, written by the iteration's dxrl_pg_popart_rescale launch (``column(name)`` /
+    ``log.value_norm["sigma"]``, names in VNORM_COLUMNS).  ``mu`` / ``sigma``: the pair the next
+    iteration decodes and encodes with -- ``sigma`` is the factor between the log's ``value_mse``
+    (normalised units) and raw units, ``value_mse * sigma ** 2`` being the raw figure for targets
+    encoded with that pair; ``mu_prev`` / ``sigma_prev``: the pair of the iteration itself;
+    ``scale`` / ``shift`` / ``rescaled``: what the rescale did to the head; ``count`` / ``mean`` /
+    ``std``: the running return moments; ``batch_mean`` / ``batch_std``: the iteration's own;
+    ``calls``: batches folded; ``forget``: the forgetting factor.  A row of a refused rescale
+    (``popart_state()["skipped"]``) stays zero."""
+
+    def __init__(self, table):
+        self.table = np.array(table, dtype=np.float64).reshape(-1, VNORM_COLS)
+
+    def column(self, name: str) -> np.ndarray:
+        if name not in VNORM_COLUMNS:
+            raise ValueError(f"a value_norm column is one of {list(VNORM_COLUMNS)}, got {name!r}")
+        return self.table[:, VNORM_COLUMNS.index(name)]
+
+    __getitem__ = column
+
+    @property
+    def columns(self) -> Dict[str, np.ndarray]:
+        return {name: self.table[:, k] for k, name in enumerate(VNORM_COLUMNS)}
+
+    def __len__(self) -> int:
+        return self.table.shape[0]
+
+
 # ====================================================================== TrainingLog
 class TrainingLog:
     """The learning curve of a run: one row per iteration, named NumPy columns
@@ -147,13 +185,15 @@ class TrainingLog:
     ``fit(merge_ranks=True)``; None otherwise.
 
     ``optimizer``: the ``OptimizerLog`` of a run on a trainer with step-size control; None
+    otherwise.  ``value_norm``: the ``ValueNormLog`` of a run on a trainer with popart; None
     otherwise."""
 
     def __init__(self, table=None, header: Optional[Dict[str, Any]] = None, window: Optional[int] = None,
                  settings: Optional[Dict[str, Any]] = None, _pending=None, validation: "Optional[ValidationLog]" = None,
-                 ranks=None, optimizer=None):
+                 ranks=None, optimizer=None, value_norm=None):
         self._pending = _pending
         self._optimizer = None if optimizer is None else OptimizerLog(optimizer)
+        self._value_norm = None if value_norm is None else ValueNormLog(value_norm)
         self._ranks = None if ranks is None else np.array(ranks, dtype=np.float64)
         if self._ranks is not None and (self._ranks.ndim != 3 or self._ranks.shape[2] != RANK_DOUBLES):
             raise ValueError(f"ranks must be [rows][world][{RANK_DOUBLES}], got shape {self._ranks.shape}")
@@ -166,10 +206,12 @@ class TrainingLog:
     # -- lazy fill (fit enqueued the copy; the first read waits for it)
     def _resolve(self):
         if self._pending is not None:
-            event, host_table, host_header, rows, host_ranks, host_opt = self._pending
+            event, host_table, host_header, rows, host_ranks, host_opt, host_vnorm = self._pending
             event.synchronize()
             if host_opt is not None:
                 self._optimizer = OptimizerLog(host_opt[:rows].numpy().copy())
+            if host_vnorm is not None:
+                self._value_norm = ValueNormLog(host_vnorm[:rows].numpy().copy())
             self._table = host_table[:rows].numpy().copy()
             self._header = header_dict(host_header.numpy())
             if host_ranks is not None:
@@ -197,6 +239,12 @@ class TrainingLog:
         """The step-size rows (OptimizerLog), or None for a trainer without step-size control."""
         self._resolve()
         return self._optimizer
+
+    @property
+    def value_norm(self) -> Optional[ValueNormLog]:
+        """The value-normalisation rows (ValueNormLog), or None for a trainer without popart."""
+        self._resolve()
+        return self._value_norm
 
     def rank_column(self, name: str) -> np.ndarray:
         """[rows][world]: one entry of the ranks' records."""
@@ -270,6 +318,9 @@ class TrainingLog:
         if self.optimizer is not None:  # likewise: a run without step-size control
             out["optimizer_columns"] = list(OPT_COLUMNS)
             out["optimizer"] = [[_enc(x) for x in row] for row in self.optimizer.table.tolist()]
+        if self.value_norm is not None:  # likewise: a run without popart
+            out["value_norm_columns"] = list(VNORM_COLUMNS)
+            out["value_norm"] = [[_enc(x) for x in row] for row in self.value_norm.table.tolist()]
         return out
 
     @classmethod
@@ -291,8 +342,13 @@ class TrainingLog:
             if list(d.get("optimizer_columns", [])) != list(OPT_COLUMNS):
                 raise ValueError("not a training log with this build's optimizer columns")
             opt = np.array([[_dec(x) for x in row] for row in d["optimizer"]], dtype=np.float64).reshape(-1, OPT_COLS)
+        vn = None
+        if d.get("value_norm") is not None:  # absent in runs without popart and in older files
+            if list(d.get("value_norm_columns", [])) != list(VNORM_COLUMNS):
+                raise ValueError("not a training log with this build's value_norm columns")
+            vn = np.array([[_dec(x) for x in row] for row in d["value_norm"]], dtype=np.float64).reshape(-1, VNORM_COLS)
         return cls(table, {k: _dec(v) for k, v in d["header"].items()}, d.get("window"), d.get("settings"),
-                   validation=val, ranks=ranks, optimizer=opt)
+                   validation=val, ranks=ranks, optimizer=opt, value_norm=vn)
 
     def save(self, path):
         with open(path, "w") as f:
@@ -1054,6 +1110,9 @@ class _RunState:
         # a trainer with step-size control: the optimizer table, one row per logged iteration
         self.controlled = bool(getattr(tr, "lr_control", False))
         self.opt_table = self.host_opt_table = None
+        # a trainer with popart: the value_norm table, one row per logged iteration
+        self.popart = getattr(tr, "popart", None) is not None
+        self.vnorm_table = self.host_vnorm_table = None
         self.reserve(tr, cap)
 
     def merge_ranks(self, tr):
@@ -1089,6 +1148,12 @@ class _RunState:
                 opt[:self.rows].copy_(self.opt_table[:self.rows])
             self.opt_table = opt
             self.host_opt_table = torch.zeros(cap, OPT_COLS, dtype=torch.float64).pin_memory()
+        if self.popart:
+            vn = torch.zeros(cap, VNORM_COLS, dtype=torch.float64, device=tr.dev)
+            if self.vnorm_table is not None and self.rows:
+                vn[:self.rows].copy_(self.vnorm_table[:self.rows])
+            self.vnorm_table = vn
+            self.host_vnorm_table = torch.zeros(cap, VNORM_COLS, dtype=torch.float64).pin_memory()
         if self.merged:
             self._rank_tables(tr, cap)
 
@@ -1227,10 +1292,14 @@ def fit(tr, iterations: int, keep_best: Optional[str] = "mean_return", min_episo
     for k in range(iterations):
         if st.controlled:  # the iteration's last optimiser launch writes its row into the table
             tr._opt_row_target = st.opt_table[st.rows]
+        if st.popart:  # likewise the iteration's rescale launch
+            tr._vnorm_row_target = st.vnorm_table[st.rows]
         try:
             tr.iteration()
         finally:
             tr._opt_row_target = None
+            if st.popart:
+                tr._vnorm_row_target = None
         log_iteration(tr, st, score_col, min_episodes, conv_col, window, threshold, merge_ranks)
         validated = val is not None and (st.rows % every == 0 or k == iterations - 1)
         if validated:
@@ -1259,12 +1328,15 @@ def training_log(tr) -> TrainingLog:
         st.host_rank_log[:st.rows].copy_(st.rank_log[:st.rows], non_blocking=True)
     if st.controlled and st.rows:
         st.host_opt_table[:st.rows].copy_(st.opt_table[:st.rows], non_blocking=True)
+    if st.popart and st.rows:
+        st.host_vnorm_table[:st.rows].copy_(st.vnorm_table[:st.rows], non_blocking=True)
     st.host_header.copy_(st.header, non_blocking=True)
     st.event.record(torch.cuda.current_stream(tr.dev))
     log = TrainingLog(window=st.window, settings=st.settings,
                       _pending=(st.event, st.host_table, st.host_header, st.rows,
                                 st.host_rank_log if st.merged else None,
-                                st.host_opt_table if st.controlled else None), validation=validation_log(tr))
+                                st.host_opt_table if st.controlled else None,
+                                st.host_vnorm_table if st.popart else None), validation=validation_log(tr))
     st.last_log = weakref.ref(log)
     return log
 
@@ -1350,11 +1422,15 @@ def save_checkpoint(tr, path):
         arrays["opt_state"] = host(tr.opt_state)
     if tr.cfg.value_norm:  # likewise: the running return moments and the next iteration's (mu, sigma)
         arrays["value_norm_state"] = host(tr.vnorm)
+    if tr.cfg.popart:  # likewise: the units the critic's head puts out
+        arrays["popart_state"] = host(tr.popart)
     if st is not None:
         arrays.update(log_table=host(st.table[:st.rows]), log_header=host(st.header),
                       best_params=host(st.best_params))
         if st.controlled:
             arrays["log_optimizer"] = host(st.opt_table[:st.rows])
+        if st.popart:
+            arrays["log_value_norm"] = host(st.vnorm_table[:st.rows])
         meta["log"] = {"rows": st.rows, "env_steps": st.env_steps, "window": st.window, "settings": st.settings}
         if st.merged:  # optional entries: a run without merge_ranks writes the file it always did
             arrays["log_ranks"] = host(st.rank_log[:st.rows])
@@ -1447,8 +1523,11 @@ def load_checkpoint(cls, path, env, process_group=None, world_size: int = 1):
                          f"{', '.join(diff)})")
     cfg = dict(meta["trainer_config"])
     cfg["betas"] = tuple(cfg["betas"])
-    from .value_norm import check_checkpoint
+    from .value_norm import check_checkpoint, check_forget, check_popart_checkpoint
     check_checkpoint(bool(cfg.get("value_norm", False)), "value_norm_state" in arrays, path)
+    check_popart_checkpoint(bool(cfg.get("popart", False)), "popart_state" in arrays, path)
+    if "value_norm_state" in arrays:
+        check_forget(cfg.get("value_norm_forget", 0.0), arrays["value_norm_state"], path)
     tr = cls(env, TrainerConfig(**cfg), process_group=process_group, world_size=world_size)
     if tr.collective and int(meta.get("rank", 0)) != _rank_of(tr):
         raise ValueError(f"{path}: the checkpoint of rank {meta.get('rank', 0)}, loaded on rank {_rank_of(tr)}")
@@ -1471,6 +1550,8 @@ def load_checkpoint(cls, path, env, process_group=None, world_size: int = 1):
         put(tr.opt_state, "opt_state")
     if tr.cfg.value_norm:
         put(tr.vnorm, "value_norm_state")
+    if tr.cfg.popart:
+        put(tr.popart, "popart_state")
     if meta["log"] is not None:
         lg = meta["log"]
         st = run_state(tr, int(lg["rows"]))
@@ -1482,6 +1563,8 @@ def load_checkpoint(cls, path, env, process_group=None, world_size: int = 1):
         put(st.best_params, "best_params")
         if st.controlled and st.rows:
             put(st.opt_table[:st.rows], "log_optimizer")
+        if st.popart and st.rows:
+            put(st.vnorm_table[:st.rows], "log_value_norm")
         if lg.get("merge_ranks"):  # absent in runs without merge_ranks and in older files
             st.merge_ranks(tr)
             if st.rows:

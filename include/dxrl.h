@@ -468,6 +468,10 @@ int dxrl_pg_gae_timelimit_count_words(int64_t num_envs, int64_t horizon, int64_t
  *   mu = (float)mean;  sigma = (float)sqrt(M2 / count + eps)     (f64 arithmetic, then narrowed)
  * so within one call the same (mu, sigma) decode the critic and encode its targets, and the
  * state lags the data by exactly one call.  eps is stored in the block for dxrl_pg_vnorm_combine.
+ * Forgetting: every fold (here and in dxrl_pg_vnorm_combine) first discounts the running triple
+ * with d = 1 - FORGET (f64): count <- d count, M2 <- d M2, the mean kept; then the merge and the
+ * refresh above.  FORGET = 0 (a fresh block) gives d = 1 and the pooled moments, bit for bit;
+ * with FORGET > 0 the count settles near batch count / FORGET, so late returns keep their weight.
  * eps = 0 with constant returns gives sigma = 0: the caller's choice.
  * Launches: two, as the plain entries (the kernel chosen by horizon as in dxrl_pg_gae,
  * DXRL_GAE_SEQ included, in its value-normalisation instantiation; then one finishing launch).
@@ -489,6 +493,8 @@ enum dxrl_pg_vnorm_word {
     DXRL_PG_VNORM_ADV_M2,
     DXRL_PG_VNORM_CALLS,        /* batches folded                                           */
     DXRL_PG_VNORM_EPS,          /* eps of the last dxrl_pg_gae_vnorm call                   */
+    DXRL_PG_VNORM_FORGET,       /* forgetting factor of the fold, in [0, 1): set by the owner
+                                   of the block before the first call, written by no entry  */
     DXRL_PG_VNORM_NAMED
 };
 #define DXRL_PG_VNORM_WORDS 16  /* words from DXRL_PG_VNORM_NAMED on are zero */
@@ -526,6 +532,75 @@ int dxrl_pg_gae_vnorm_partial_doubles(int64_t num_envs, int64_t horizon, int64_t
  * launch. */
 int dxrl_pg_vnorm_combine(int32_t device, const double* moments6, int32_t world, double* stats, double* vnorm,
                           void* stream);
+
+/* ---- PopArt: keep the critic's decoded values when (mu, sigma) move --------------------------
+ * The critic's head (kOffW3c row 0: 256 weights, then the bias in column 256) puts out values in
+ * the units of some pair (mu_h, sigma_h); dxrl_pg_gae_vnorm decodes them with the vnorm block's
+ * (MU, SIGMA) = (mu_n, sigma_n).  dxrl_pg_popart_rescale rewrites the head so that it puts out the
+ * units of (mu_n, sigma_n) and decodes to what it decoded to before.
+ *
+ * State: popart, f64 [DXRL_PG_POPART_WORDS] on the device (enum below).  A fresh block is all zero
+ * except DXRL_PG_POPART_SIGMA_HEAD = 1.  The vnorm block is only read.
+ *
+ * Arithmetic: all f64, nothing fused, one rounding to f32 per stored value.
+ *   s  = sigma_h / sigma_n
+ *   w' = (float)((double)w * s)                                       the 256 head weights
+ *   b' = (float)((sigma_h * (double)b + (mu_h - mu_n)) / sigma_n)     the bias
+ *   MU_HEAD = mu_n; SIGMA_HEAD = sigma_n; RESCALES += 1; LAST_SCALE = s;
+ *   LAST_SHIFT = (mu_h - mu_n) / sigma_n
+ * so sigma_n (w' h + b') + mu_n = sigma_h (w h + b) + mu_h up to the f32 roundings of w', b'.
+ * Written: the 257 master floats in place in `params`, and every copy of them in the bf16 `packed`
+ * buffer (the pack then equals dxrl_pg_pack_weights(params) byte for byte).  Nothing else of
+ * either buffer changes.  Adam's moments of the head are NOT rescaled (PopArt's own choice: they
+ * keep describing gradients in the old units and decay at Adam's rates).
+ * The cases, decided in this order:
+ *   refusal: sigma_h or sigma_n not finite or <= 0, or mu_h or mu_n not finite (eps = 0 on constant
+ *            returns gives sigma_n = 0): SKIPPED += 1 and nothing else is written, row_out included;
+ *   no-op:   (mu_h, sigma_h) equal (mu_n, sigma_n) bitwise: params, packed and the block stay
+ *            untouched (a call on a fresh pair rounds nothing); row_out is written with
+ *            rescaled = 0, scale = 1, shift = 0;
+ *   rescale: the above; row_out is written with rescaled = 1.
+ * The entry keeps no order of its own: it compares the two blocks, so it may run after any
+ * iteration, updated or not, resumed or not.
+ * row_out: f64 [DXRL_PG_VNORM_LOG_COLS] or NULL (enum below), written by the same launch; std =
+ * sqrt(M2 / count) (0 for an empty triple).
+ * One launch of one workgroup.  DXRL_E_INVALID before any launch for a null params / packed /
+ * vnorm / popart. */
+enum dxrl_pg_popart_word {
+    DXRL_PG_POPART_MU_HEAD = 0,  /* the units the critic's head puts out                     */
+    DXRL_PG_POPART_SIGMA_HEAD,
+    DXRL_PG_POPART_RESCALES,     /* calls that changed the head                              */
+    DXRL_PG_POPART_SKIPPED,      /* calls refused on the device                              */
+    DXRL_PG_POPART_LAST_SCALE,   /* s and the shift of the last rescale                      */
+    DXRL_PG_POPART_LAST_SHIFT,
+    DXRL_PG_POPART_NAMED
+};
+#define DXRL_PG_POPART_WORDS 8   /* words from DXRL_PG_POPART_NAMED on are zero */
+enum dxrl_pg_vnorm_log_col {     /* the row of an iteration, f64 [DXRL_PG_VNORM_LOG_COLS]    */
+    DXRL_PG_VNORM_LOG_MU = 0,    /* the pair the next iteration decodes with, = the head's   */
+    DXRL_PG_VNORM_LOG_SIGMA,
+    DXRL_PG_VNORM_LOG_MU_PREV,   /* the head's pair before the call                          */
+    DXRL_PG_VNORM_LOG_SIGMA_PREV,
+    DXRL_PG_VNORM_LOG_SCALE,     /* s (1 on the no-op path)                                  */
+    DXRL_PG_VNORM_LOG_SHIFT,     /* (mu_prev - mu) / sigma (0 on the no-op path)             */
+    DXRL_PG_VNORM_LOG_RESCALED,  /* 0 / 1                                                    */
+    DXRL_PG_VNORM_LOG_COUNT,     /* the running triple, as count / mean / std                */
+    DXRL_PG_VNORM_LOG_MEAN,
+    DXRL_PG_VNORM_LOG_STD,
+    DXRL_PG_VNORM_LOG_BATCH_MEAN,
+    DXRL_PG_VNORM_LOG_BATCH_STD,
+    DXRL_PG_VNORM_LOG_CALLS,
+    DXRL_PG_VNORM_LOG_FORGET,
+    DXRL_PG_VNORM_LOG_COLS
+};
+typedef struct dxrl_pg_popart_args {
+    float* params;               /* f32 master [dxrl_pg_sizes params]                        */
+    void* packed;                /* bf16 pack [dxrl_pg_sizes packed_bf16]                    */
+    const double* vnorm;         /* f64 [DXRL_PG_VNORM_WORDS], read                          */
+    double* popart;              /* f64 [DXRL_PG_POPART_WORDS]                               */
+    double* row_out;             /* f64 [DXRL_PG_VNORM_LOG_COLS] or NULL                     */
+} dxrl_pg_popart_args;
+int dxrl_pg_popart_rescale(int32_t device, const dxrl_pg_popart_args* args, void* stream);
 /* Global advantage statistics from every rank's (count, mean, M2) triple -- moments f64
  * [world][3] in rank order (all-gathered stats[5..7]) -- merged in rank order into
  * stats[0] count, [1] sum, [2] mean, [3] sum of squared deviations, [4] unbiased std (what the
