@@ -361,6 +361,7 @@ PG_OPT_SLOT_WORDS = 16                      # DXRL_PG_OPT_SLOT_WORDS
 PG_OPT_STATE_WORDS = 2 * PG_OPT_SLOT_WORDS  # DXRL_PG_OPT_STATE_WORDS
 PG_OPT_COLUMNS = ("lr", "lr_last", "updates", "skipped", "stop_pass", "kl_max", "kl_epoch", "lr_scale")
 PG_OPT_COLS = len(PG_OPT_COLUMNS)           # DXRL_PG_OPT_COLS
+PG_KL_RECORD_WORDS = 2                      # DXRL_PG_KL_RECORD_WORDS: a rank's (kl_sum, rows) of a pass
 
 
 # dxrl_pg_gae_vnorm: the args struct and the words of the state block (enum dxrl_pg_vnorm_word)
@@ -491,6 +492,9 @@ _SIGS = {
                                     _I32, _P, _P, _P]),
     "dxrl_pg_adam_step_ctl": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _I64, _F64, _F64, _F64, _F64, _P, _I32, _P,
                                         _P, _P, _I32, _I64, PgLrControl, _P, _P, _P]),
+    "dxrl_pg_kl_rank_pack": (C.c_int, [_I32, _P, _I32, _I64, _P, _P]),
+    "dxrl_pg_adam_step_ctl_world": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, _I64, _F64, _F64, _F64, _F64, _P, _I32,
+                                              _P, _P, _P, _I32, PgLrControl, _P, _P, _P]),
 }
 
 _lib = None

@@ -1143,26 +1143,30 @@ struct AdamCtlArgs {
     AdamPackArgs a;            // a.lr unused; a.bc1 / a.bc2: the host's corrections for t = calls
     dxrl_pg_lr_control c;
     double beta1, beta2;
-    const double* loss;        // f64 [loss_rows][4], column 3 = the pass's approx-KL sums
-    int loss_rows;
-    double rows;               // samples of the pass
+    union {                    // where (kl_sum, rows) come from, one member per kernel:
+        const double* loss;    // k_adam_pack_ctl: f64 [loss_rows][4], column 3 = the pass's approx-KL sums
+        const double* records; // k_adam_pack_ctl_world: f64 [world][2], the ranks' (kl_sum, rows) in rank order
+    };
+    union {
+        int loss_rows;
+        int world;
+    };
+    double rows;               // k_adam_pack_ctl: samples of the pass (k_adam_pack_ctl_world: unused)
     const int64_t* rd;         // state slot read
     int64_t* wr;               // state slot written
     double* row;               // f64 [DXRL_PG_OPT_COLS] or null
 };
 
-__global__ __launch_bounds__(256) void k_adam_pack_ctl(AdamCtlArgs x) {
-    __shared__ double red4[4];
+// (the rules, once, for both forms below: g2 the squared grad norm, (kl_sum, rows) the pass's KL
+// sum and samples, each already the same bits in every thread of the launch)
+__device__ __forceinline__ void adam_pack_ctl_apply(const AdamCtlArgs& x, double g2, double kl_sum, double rows) {
     const AdamPackArgs& a = x.a;
     const dxrl_pg_lr_control& c = x.c;
-    const double g2 = block_sum_partials(a.partial, a.nb, red4);
-    __syncthreads();  // red4 is reused
-    const double kl_sum = block_sum_partials<4>(x.loss + 3, x.loss_rows, red4);
     const double* rdf = reinterpret_cast<const double*>(x.rd);
     const bool first = c.pass_index == 0;
     const int64_t applied = x.rd[DXRL_PG_OPT_APPLIED], skipped = x.rd[DXRL_PG_OPT_SKIPPED];
     const double lr_scale = rdf[DXRL_PG_OPT_SCALE];
-    const double kl = kl_sum / x.rows;
+    const double kl = kl_sum / rows;
     bool stopped = !first && x.rd[DXRL_PG_OPT_STOPPED] != 0;
     const bool stops = c.target_kl > 0.0 && !stopped && kl > c.stop_factor * c.target_kl;
     stopped = stopped || stops;
@@ -1184,7 +1188,7 @@ __global__ __launch_bounds__(256) void k_adam_pack_ctl(AdamCtlArgs x) {
         double acc_kl = first ? 0.0 : rdf[DXRL_PG_OPT_KL_SUM], acc_rows = first ? 0.0 : rdf[DXRL_PG_OPT_KL_ROWS];
         if (c.last_epoch) {
             acc_kl += kl_sum;
-            acc_rows += x.rows;
+            acc_rows += rows;
         }
         double next = lr_scale;
         if (c.last_pass) {
@@ -1244,6 +1248,41 @@ __global__ __launch_bounds__(256) void k_adam_pack_ctl(AdamCtlArgs x) {
         bc2 = (float)(1.0 - pow(x.beta2, t));
     }
     adam_pack_element(a, j, clip_scale(g2, a.max_norm), (float)lr, bc1, bc2);
+}
+
+__global__ __launch_bounds__(256) void k_adam_pack_ctl(AdamCtlArgs x) {
+    __shared__ double red4[4];
+    const double g2 = block_sum_partials(x.a.partial, x.a.nb, red4);
+    __syncthreads();  // red4 is reused
+    const double kl_sum = block_sum_partials<4>(x.loss + 3, x.loss_rows, red4);
+    adam_pack_ctl_apply(x, g2, kl_sum, x.rows);
+}
+
+// The sharded form (dxrl_pg_adam_step_ctl_world): x.records is the gathered f64 [x.world][2] records
+// (kl_sum, rows) of dxrl_pg_kl_rank_pack in rank order.
+// Every thread merges the 2 x world doubles sequentially in rank order -- the same bytes on every
+// rank, so the same decision on every rank -- and the rest is k_adam_pack_ctl's.
+__global__ __launch_bounds__(256) void k_adam_pack_ctl_world(AdamCtlArgs x) {
+    __shared__ double red4[4];
+    const double g2 = block_sum_partials(x.a.partial, x.a.nb, red4);
+    double kl_sum = x.records[0], rows = x.records[1];
+    for (int r = 1; r < x.world; ++r) {
+        kl_sum += x.records[2 * r];
+        rows += x.records[2 * r + 1];
+    }
+    adam_pack_ctl_apply(x, g2, kl_sum, rows);
+}
+
+// dxrl_pg_kl_rank_pack: one workgroup; record = (column 3 of the loss partials summed in
+// k_adam_pack_ctl's order, the pass's rows)
+__global__ __launch_bounds__(256) void k_kl_rank_pack(const double* __restrict__ loss, int loss_rows, double rows,
+                                                      double* __restrict__ record) {
+    __shared__ double red4[4];
+    const double kl_sum = block_sum_partials<4>(loss + 3, loss_rows, red4);
+    if (threadIdx.x == 0) {
+        record[0] = kl_sum;
+        record[1] = rows;
+    }
 }
 
 // dxrl_pg_popart_rescale (include/dxrl.h states the arithmetic and the three cases): one workgroup,
@@ -1665,20 +1704,22 @@ int dxrl_pg_adam_step(int32_t device, const float* params, const float* grads, c
     return launch_check("k_adam_pack");
 }
 
-int dxrl_pg_adam_step_ctl(int32_t device, const float* params, const float* grads, const float* m1, const float* m2,
-                          float* params_out, float* m1_out, float* m2_out, int64_t n, double beta1, double beta2,
-                          double eps, double max_norm, double* gnorm_partial, int32_t gnorm_blocks, double* gnorm2,
-                          void* packed, const double* loss_partial, int32_t loss_blocks, int64_t pass_rows,
-                          dxrl_pg_lr_control ctl, int64_t* state, double* row_out, void* stream) {
-    DXRL_REQUIRE(params && grads && m1 && m2 && params_out && m1_out && m2_out && gnorm_partial && gnorm2 && packed &&
-                     loss_partial && state && gnorm_blocks >= 0 && loss_blocks >= 1 && pass_rows >= 1,
-                 "bad adam_step_ctl arguments");
-    DXRL_REQUIRE(n == kParams, "adam_step_ctl: n must be the padded parameter count %lld", (long long)kParams);
-    DXRL_REQUIRE(params != params_out && m1 != m1_out && m2 != m2_out, "adam_step_ctl: outputs must not alias inputs");
-    DXRL_REQUIRE(ctl.calls >= 1 && ctl.pass_index >= 0, "adam_step_ctl: calls >= 1 and pass_index >= 0");
+// The two controlled entry points after their own argument checks: the k_sumsq launch when the
+// caller holds no norm partials, the argument block, and the launch of `kernel`.  (kl, kl_rows,
+// rows) is (loss_partial, loss_blocks, pass_rows) for k_adam_pack_ctl and (records, world, unused)
+// for k_adam_pack_ctl_world.
+static int adam_step_ctl_launch(const char* what, void (*kernel)(AdamCtlArgs), int32_t device, const float* params,
+                                const float* grads, const float* m1, const float* m2, float* params_out,
+                                float* m1_out, float* m2_out, int64_t n, double beta1, double beta2, double eps,
+                                double max_norm, double* gnorm_partial, int32_t gnorm_blocks, double* gnorm2,
+                                void* packed, const double* kl, int32_t kl_rows, double rows,
+                                const dxrl_pg_lr_control& ctl, int64_t* state, double* row_out, void* stream) {
+    DXRL_REQUIRE(n == kParams, "%s: n must be the padded parameter count %lld", what, (long long)kParams);
+    DXRL_REQUIRE(params != params_out && m1 != m1_out && m2 != m2_out, "%s: outputs must not alias inputs", what);
+    DXRL_REQUIRE(ctl.calls >= 1 && ctl.pass_index >= 0, "%s: calls >= 1 and pass_index >= 0", what);
     DXRL_REQUIRE(ctl.lr_nominal > 0.0 && ctl.lr_min > 0.0 && ctl.lr_min <= ctl.lr_max && ctl.target_kl >= 0.0 &&
                      ctl.stop_factor > 0.0 && ctl.adapt_factor > 0.0 && ctl.adapt_band > 0.0,
-                 "adam_step_ctl: 0 < lr_nominal, 0 < lr_min <= lr_max, target_kl >= 0, positive factors");
+                 "%s: 0 < lr_nominal, 0 < lr_min <= lr_max, target_kl >= 0, positive factors", what);
     DeviceGuard g(device);
     hipStream_t st = as_stream(stream);
     if (gnorm_blocks == 0) {  // dxrl_pg_optimizer_step's source of the norm: gnorm_partial is f64 [512] scratch
@@ -1693,13 +1734,49 @@ int dxrl_pg_adam_step_ctl(int32_t device, const float* params, const float* grad
                        gnorm2, static_cast<bf16*>(packed)};
     x.c = ctl;
     x.beta1 = beta1, x.beta2 = beta2;
-    x.loss = loss_partial, x.loss_rows = loss_blocks, x.rows = (double)pass_rows;
+    x.loss = kl, x.loss_rows = kl_rows, x.rows = rows;
     // call c reads slot (c - 1) & 1 and writes slot c & 1
     x.rd = state + ((ctl.calls - 1) & 1) * DXRL_PG_OPT_SLOT_WORDS;
     x.wr = state + (ctl.calls & 1) * DXRL_PG_OPT_SLOT_WORDS;
     x.row = ctl.last_pass ? row_out : nullptr;
-    hipLaunchKernelGGL(k_adam_pack_ctl, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x);
-    return launch_check("k_adam_pack_ctl");
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x);
+    return launch_check(what);
+}
+
+int dxrl_pg_adam_step_ctl(int32_t device, const float* params, const float* grads, const float* m1, const float* m2,
+                          float* params_out, float* m1_out, float* m2_out, int64_t n, double beta1, double beta2,
+                          double eps, double max_norm, double* gnorm_partial, int32_t gnorm_blocks, double* gnorm2,
+                          void* packed, const double* loss_partial, int32_t loss_blocks, int64_t pass_rows,
+                          dxrl_pg_lr_control ctl, int64_t* state, double* row_out, void* stream) {
+    DXRL_REQUIRE(params && grads && m1 && m2 && params_out && m1_out && m2_out && gnorm_partial && gnorm2 && packed &&
+                     loss_partial && state && gnorm_blocks >= 0 && loss_blocks >= 1 && pass_rows >= 1,
+                 "bad adam_step_ctl arguments");
+    return adam_step_ctl_launch("adam_step_ctl", k_adam_pack_ctl, device, params, grads, m1, m2, params_out, m1_out,
+                                m2_out, n, beta1, beta2, eps, max_norm, gnorm_partial, gnorm_blocks, gnorm2, packed,
+                                loss_partial, loss_blocks, (double)pass_rows, ctl, state, row_out, stream);
+}
+
+int dxrl_pg_kl_rank_pack(int32_t device, const double* loss_partial, int32_t loss_blocks, int64_t pass_rows,
+                         double* record, void* stream) {
+    DXRL_REQUIRE(loss_partial && record && loss_blocks >= 1 && pass_rows >= 1, "bad kl_rank_pack arguments");
+    DeviceGuard g(device);
+    hipLaunchKernelGGL(k_kl_rank_pack, dim3(1), dim3(256), 0, as_stream(stream), loss_partial, loss_blocks,
+                       (double)pass_rows, record);
+    return launch_check("k_kl_rank_pack");
+}
+
+int dxrl_pg_adam_step_ctl_world(int32_t device, const float* params, const float* grads, const float* m1,
+                                const float* m2, float* params_out, float* m1_out, float* m2_out, int64_t n,
+                                double beta1, double beta2, double eps, double max_norm, double* gnorm_partial,
+                                int32_t gnorm_blocks, double* gnorm2, void* packed, const double* records,
+                                int32_t world, dxrl_pg_lr_control ctl, int64_t* state, double* row_out,
+                                void* stream) {
+    DXRL_REQUIRE(params && grads && m1 && m2 && params_out && m1_out && m2_out && gnorm_partial && gnorm2 && packed &&
+                     records && state && gnorm_blocks >= 0 && world >= 1,
+                 "bad adam_step_ctl_world arguments");
+    return adam_step_ctl_launch("adam_step_ctl_world", k_adam_pack_ctl_world, device, params, grads, m1, m2, params_out,
+                                m1_out, m2_out, n, beta1, beta2, eps, max_norm, gnorm_partial, gnorm_blocks, gnorm2,
+                                packed, records, world, 0.0, ctl, state, row_out, stream);
 }
 
 int dxrl_pg_adam(int32_t device, float* params, const float* grads, float* m1, float* m2, int64_t n, double lr,

@@ -13,6 +13,8 @@ sharded run draws exactly what the same envs draw unsharded.  The PG learner
     enters each rank as ent_coef/world (``loss_scales``), so the SUM is the
     gradient of the global-batch mean loss (that algebra alone would also hold for
     ragged shards; the trainer requires equal ones, see below).
+With step-size control every optimiser step additionally all-gathers each rank's
+(kl_sum, rows) record (``gather_kl_records_``), so all ranks decide from the same KL.
 The curriculum scheduler (config C3) additionally all-gathers each rank's
 episode-end codes so every rank feeds the same global episode stream.
 
@@ -121,6 +123,12 @@ def gather_vnorm_moments_(out: torch.Tensor, vnorm: torch.Tensor, world: int, gr
     from ._native import PG_VNORM
     lo = PG_VNORM["batch_count"]
     return all_gather_into_(out, vnorm[lo:lo + 6].contiguous(), world, group)
+
+
+def gather_kl_records_(out: torch.Tensor, record: torch.Tensor, world: int, group=None) -> torch.Tensor:
+    """out [world][2] = every rank's (kl_sum, rows) of the pass, in rank order: the record
+    dxrl_pg_kl_rank_pack wrote, which dxrl_pg_adam_step_ctl_world merges on every rank."""
+    return all_gather_into_(out, record, world, group)
 
 
 def merge_moments(a, b):

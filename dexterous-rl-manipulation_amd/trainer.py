@@ -19,7 +19,9 @@ actor-critic with GAE and policy gradients on top of the same env.  One
      split-K over samples with the bias as an extra ones-row);
   6. the f32 gradient SUM all-reduce over RCCL (world > 1), in two halves on a side stream:
      the critic's beside the actor's train pass, the actor's before Adam;
-  7. global-norm clip + Adam on the f32 master, bf16 repack;
+  7. global-norm clip + Adam on the f32 master, bf16 repack (with step-size control on several
+     ranks: one all-gather of each rank's (kl_sum, rows) record ahead of step 6, merged in rank
+     order inside the optimiser launch, ``dxrl_pg_adam_step_ctl_world``);
   8. with ``TrainerConfig.popart``: ``dxrl_pg_popart_rescale``, the critic's head into the units
      of the (mu, sigma) that step 3 left for the next iteration.
 
@@ -37,8 +39,8 @@ import torch
 
 from . import _native as N
 from . import lr_control, value_norm
-from .distributed import (all_gather_into_, all_reduce_sum_, gather_adv_moments_, gather_vnorm_moments_, global_count,
-                          loss_scales)
+from .distributed import (all_gather_into_, all_reduce_sum_, gather_adv_moments_, gather_kl_records_,
+                          gather_vnorm_moments_, global_count, loss_scales)
 from .envs import VecEnv
 
 # csrc/dxrl_pg.h
@@ -226,11 +228,13 @@ class PGTrainer:
         lr_control.validate_lr_control(cfg)
         value_norm.validate_value_norm(cfg)
         self.lr_control = lr_control.control_enabled(cfg)  # optimizer_step() is dxrl_pg_adam_step_ctl
-        if self.lr_control and self.collective:
-            raise ValueError("step-size control (lr_schedule / target_kl) runs on one rank: each rank's KL is its own "
-                             "shard's, so the ranks would decide differently and their weights diverge.  The missing "
-                             "piece is one all-reduce of (kl_sum, rows) over the ranks before the optimiser step, "
-                             "the KL all-reduce, which is not built")
+        if self.lr_control and world_size > 1 and process_group is None:
+            import torch.distributed as dist
+            if not (dist.is_available() and dist.is_initialized()):  # before any collective
+                raise ValueError("step-size control (lr_schedule / target_kl) on several ranks: each rank's KL is its "
+                                 "own shard's, so the ranks must decide from the merged one.  The KL all-reduce, one "
+                                 "all-reduce of (kl_sum, rows) over the ranks before every optimiser step, needs an "
+                                 "initialised process group: pass process_group or initialise the default group")
         # Exchanges that overlap compute (collective mode): the advantage-moment all-gather runs
         # beside the critic's train pass (which does not read the normalisation), the critic
         # half of the gradient all-reduce beside the actor's, the scheduler's code exchange
@@ -342,6 +346,12 @@ class PGTrainer:
             self.opt_state.view(torch.float64)[[k for k, (nm, _) in enumerate(N.PG_OPT_SLOTS) if nm == "scale"]] = 1.0
             self.opt_state[[k for k, (nm, _) in enumerate(N.PG_OPT_SLOTS) if nm == "stop_pass"]] = -1
             self.opt_row = torch.zeros(N.PG_OPT_COLS, dtype=torch.float64, device=d)
+        # step-size control on a collective trainer: this rank's (kl_sum, rows) of a pass and the
+        # ranks' gathered records, which every rank merges in its optimiser launch
+        self.kl_record = self.kl_records = None
+        if self.lr_control and self.collective:
+            self.kl_record = torch.zeros(N.PG_KL_RECORD_WORDS, dtype=torch.float64, device=d)
+            self.kl_records = torch.zeros(self.world, N.PG_KL_RECORD_WORDS, dtype=torch.float64, device=d)
         tr_, pf_ = C.c_int32(), C.c_int64()
         N.call("dxrl_pg_fused_sizes", C.byref(tr_), C.byref(pf_))
         # up to two learner workgroups per CU (64-sample tiles); the library clamps to its geometry
@@ -722,10 +732,23 @@ class PGTrainer:
         buffers, which then become current (params / m1 / m2 are swapped, not copied).
 
         With step-size control (cfg.lr_schedule / cfg.target_kl) the launch is
-        dxrl_pg_adam_step_ctl on either source of the norm: pass_index within the iteration and the
-        last_epoch / last_pass flags are ppo_updates()'s; a single-update iteration is pass 0 with
-        both set.  A pass the device skips leaves its inputs in the swapped-in buffers."""
+        dxrl_pg_adam_step_ctl on either source of the norm.  On a collective trainer it is
+        dxrl_pg_adam_step_ctl_world, fed the ranks' all-gathered (kl_sum, rows) records.
+        pass_index within the iteration and the last_epoch / last_pass flags are ppo_updates()'s;
+        a single-update iteration is pass 0 with both set.  A pass the device skips leaves its
+        inputs in the swapped-in buffers."""
         c = self.cfg
+        if self.kl_record is not None:
+            # every controlled pass, schedule-only configurations included (one rule; kl_max and
+            # kl_epoch of the log stay global): this rank's record, then the ranks' records.  The
+            # pack goes out on self._s() and the gather on torch's current stream -- one and the same
+            # stream, the compute stream, which is also where the actor half of the gradient goes
+            # out under both overlap_comm settings: ahead of it, behind the train passes that wrote
+            # the loss partials
+            loss, rows = self._control_inputs()
+            N.call("dxrl_pg_kl_rank_pack", self.dev.index, N.ptr(loss), loss.shape[0], rows, N.ptr(self.kl_record),
+                   self._s())
+            gather_kl_records_(self.kl_records, self.kl_record, self.world, self.pg)
         if self._grads_pending:  # critic half already in flight on the comm stream
             self._allreduce(self.grads[:OFF["W1c"]])
             self._join_comm()
@@ -752,6 +775,12 @@ class PGTrainer:
         self.params, self.m1, self.m2 = po, m1o, m2o
         self._h2a_fresh = self._h2c_fresh = False  # new weights: the stored activations are stale
 
+    def _control_inputs(self):
+        """(loss partials, rows) of the last train pass: what the controlled step reads the KL from."""
+        if self.cfg.fused:
+            return self.fused_loss, self._loss_rows
+        return self.loss_partial, self.M
+
     def _controlled_step(self, po, m1o, m2o, pass_index, last_epoch, last_pass):
         c = self.cfg
         k = N.PgLrControl()
@@ -761,15 +790,18 @@ class PGTrainer:
         k.stop_factor = c.kl_stop_factor if c.kl_stop else math.inf
         k.adapt, k.adapt_factor, k.adapt_band = int(c.kl_adaptive), c.kl_adapt_factor, c.kl_adapt_band
         k.pass_index, k.last_epoch, k.last_pass, k.calls = pass_index, int(last_epoch), int(last_pass), self.step_count
-        loss = self.fused_loss if c.fused else self.loss_partial
-        rows = self._loss_rows if c.fused else self.M
         # the pair's norm partials, or (0 blocks) the 512-partial scratch a k_sumsq launch fills
         gn = self.gn_partial if self._gn_blocks else self.partial
         row = self.opt_row if self._opt_row_target is None else self._opt_row_target
-        N.call("dxrl_pg_adam_step_ctl", self.dev.index, N.ptr(self.params), N.ptr(self.grads), N.ptr(self.m1),
-               N.ptr(self.m2), N.ptr(po), N.ptr(m1o), N.ptr(m2o), NPARAMS, c.betas[0], c.betas[1], c.adam_eps,
-               c.max_grad_norm, N.ptr(gn), self._gn_blocks, N.ptr(self.gnorm2), N.ptr(self.packed), N.ptr(loss),
-               loss.shape[0], rows, k, N.ptr(self.opt_state), N.ptr(row), self._s())
+        head = (self.dev.index, N.ptr(self.params), N.ptr(self.grads), N.ptr(self.m1), N.ptr(self.m2), N.ptr(po),
+                N.ptr(m1o), N.ptr(m2o), NPARAMS, c.betas[0], c.betas[1], c.adam_eps, c.max_grad_norm, N.ptr(gn),
+                self._gn_blocks, N.ptr(self.gnorm2), N.ptr(self.packed))
+        tail = (k, N.ptr(self.opt_state), N.ptr(row), self._s())
+        if self.kl_records is not None:  # the ranks' records (optimizer_step gathered them)
+            N.call("dxrl_pg_adam_step_ctl_world", *head, N.ptr(self.kl_records), self.world, *tail)
+        else:
+            loss, rows = self._control_inputs()
+            N.call("dxrl_pg_adam_step_ctl", *head, N.ptr(loss), loss.shape[0], rows, *tail)
         self._gn_blocks = 0
 
     def optimizer_state(self) -> Dict[str, float]:

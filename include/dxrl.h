@@ -807,6 +807,40 @@ int dxrl_pg_adam_step_ctl(int32_t device, const float* params, const float* grad
                           void* packed, const double* loss_partial, int32_t loss_blocks, int64_t pass_rows,
                           dxrl_pg_lr_control ctl, int64_t* state, double* row_out, void* stream);
 
+/* ---- step-size control on sharded trainers: one KL record per rank ---------------------
+ * Each rank of a sharded trainer sees the KL of its own shard only; ranks on opposite sides of a
+ * threshold would apply different updates.  So every rank packs (kl_sum, rows) of its pass into a
+ * record, the records are all-gathered in rank order, and every rank merges the same bytes in the
+ * same order inside its optimiser launch: the same decision on every rank.
+ *
+ * Convention: column 3 of the loss partials holds UNSCALED sums of (logp_old - logp) over the
+ * rank's own samples -- neither dxrl_pg_fused nor dxrl_pg_heads applies inv_total_samples (which
+ * carries the world factor 1 / (rows x world) on a sharded trainer) to the loss columns, only to
+ * the gradients -- and pass_rows counts the rank's own samples.  A record therefore holds a plain
+ * sum and a plain count, and the merged kl = sum_r kl_sum_r / sum_r rows_r is the mean approximate
+ * KL over the samples of all ranks, for equal and unequal shards alike.
+ *
+ * dxrl_pg_kl_rank_pack: one launch of one workgroup.  record[0] = the sum of column 3 of
+ * loss_partial (f64 [loss_blocks][4]) in exactly the order dxrl_pg_adam_step_ctl sums it;
+ * record[1] = (double)pass_rows.  Null pointers, loss_blocks < 1 or pass_rows < 1 are refused with
+ * the record untouched. */
+#define DXRL_PG_KL_RECORD_WORDS 2
+int dxrl_pg_kl_rank_pack(int32_t device, const double* loss_partial, int32_t loss_blocks, int64_t pass_rows,
+                         double* record, void* stream);
+
+/* dxrl_pg_adam_step_ctl with (loss_partial, loss_blocks, pass_rows) replaced by the gathered
+ * records: f64 [world][DXRL_PG_KL_RECORD_WORDS] in rank order, world >= 1.  Every workgroup reads
+ * the 2 x world doubles and merges them sequentially in rank order, kl_sum = ((r0 + r1) + r2) ..
+ * and rows likewise; everything after that is dxrl_pg_adam_step_ctl's rules, stated once.  With
+ * world == 1 and the record dxrl_pg_kl_rank_pack wrote from the same partials the call writes
+ * dxrl_pg_adam_step_ctl's bytes: *_out, pack, state slot, gnorm2 and row. */
+int dxrl_pg_adam_step_ctl_world(int32_t device, const float* params, const float* grads, const float* m1,
+                                const float* m2, float* params_out, float* m1_out, float* m2_out, int64_t n,
+                                double beta1, double beta2, double eps, double max_norm, double* gnorm_partial,
+                                int32_t gnorm_blocks, double* gnorm2, void* packed, const double* records,
+                                int32_t world, dxrl_pg_lr_control ctl, int64_t* state, double* row_out,
+                                void* stream);
+
 /* ---- fused one-pass learner step (csrc/dxrl_pg_fused.hip) ----------------------------
  * One launch per network replaces forward GEMMs + heads + backward GEMMs of the
  * layer-by-layer path (dxrl_gemm_bf16 / dxrl_pg_heads / dxrl_wgrad_bf16): per
