@@ -13,7 +13,7 @@ import subprocess
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
-SOURCES = ["dxrl_env.hip", "dxrl_rollout.hip", "dxrl_gemm.hip", "dxrl_pg.hip", "dxrl_pg_fused.hip", "dxrl_pg_rollout16.hip", "dxrl_pg_rollout8.hip", "dxrl_eval.hip", "dxrl_eval_mlp.hip",
+SOURCES = ["dxrl_env.hip", "dxrl_rollout.hip", "dxrl_gemm.hip", "dxrl_pg.hip", "dxrl_pg_gae.hip", "dxrl_pg_fused.hip", "dxrl_pg_rollout16.hip", "dxrl_pg_rollout8.hip", "dxrl_eval.hip", "dxrl_eval_mlp.hip",
            "dxrl_sched.hip", "dxrl_eval_summary.hip", "dxrl_failure_summary.hip",
            "dxrl_robustness_summary.hip", "dxrl_study_summary.hip", "dxrl_pg_log.hip", "dxrl_pg_val.hip",
            "dxrl_pg_val_levels.hip", "dxrl_pg_val_paired.hip", "dxrl_pg_val_failure.hip", "dxrl_pg_runs.hip"]

@@ -1,5 +1,5 @@
 // dxrl_moments.h -- (count, mean, M2) triples: the only home of the moments arithmetic of every
-// translation unit that reduces means and variances on the device (dxrl_pg.hip, dxrl_pg_log.hip,
+// translation unit that reduces means and variances on the device (dxrl_pg_gae.hip, dxrl_pg_log.hip,
 // dxrl_pg_val*.hip and the four dxrl_*_summary.hip).
 //
 // Moments without cancellation: M2 is the sum of squared deviations about the mean; triples are

@@ -132,7 +132,7 @@ def gather_kl_records_(out: torch.Tensor, record: torch.Tensor, world: int, grou
 
 
 def merge_moments(a, b):
-    """Chan, Golub & LeVeque's pairwise update of (count, mean, M2) (csrc/dxrl_pg.hip merge)."""
+    """Chan, Golub & LeVeque's pairwise update of (count, mean, M2) (csrc/dxrl_moments.h merge)."""
     if b[0] == 0.0:
         return a
     if a[0] == 0.0:

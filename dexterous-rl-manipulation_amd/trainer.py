@@ -642,19 +642,26 @@ class PGTrainer:
         a.partial, a.stats, a.vnorm = p(self.partial), p(self.stats), p(self.vnorm)
         a.fold = 0 if self.collective else 1  # ranks fold the merged batch (dxrl_pg_vnorm_combine)
         N.call("dxrl_pg_gae_vnorm", self.dev.index, C.byref(a), self._s())
-        if self.collective:
-            # one all-gather of six doubles and one combine, where the plain trainer has one of three
-            # and one combine.  The critic's pass reads ret_norm, encoded with the PREVIOUS
-            # iteration's combined state, complete long before: it needs no wait on this exchange
-            # (the actor's pass waits for the advantage moments as before); the next iteration's
-            # dxrl_pg_gae_vnorm follows _join_comm in optimizer_step.
-            with self._on_comm():
-                gather_vnorm_moments_(self.moments_all, self.vnorm, self.world, self.pg)
-                N.call("dxrl_pg_vnorm_combine", self.dev.index, p(self.moments_all), self.world, p(self.stats),
-                       p(self.vnorm), self._s())
-                if self._comm is not None:
-                    self._stats_event.record(self._comm)
-            self._stats_pending = self._comm is not None
+        # one all-gather of six doubles and one combine, where the plain trainer has one of three
+        # and one combine.  The critic's pass reads ret_norm, encoded with the PREVIOUS
+        # iteration's combined state, complete long before: it needs no wait on this exchange
+        # (the actor's pass waits for the advantage moments as before); the next iteration's
+        # dxrl_pg_gae_vnorm follows _join_comm in optimizer_step.
+        self._combine_ranks(gather_vnorm_moments_, self.vnorm, "dxrl_pg_vnorm_combine", p(self.vnorm))
+
+    def _combine_ranks(self, gather, local, combine, *block):
+        """The collective tail of the advantages phase: every rank's moments (`gather` of `local`) in
+        rank order, merged on the device by the entry point `combine` (identical on all ranks), on
+        the comm stream.  One rank: the GAE entry point already wrote the combined statistics."""
+        if not self.collective:
+            return
+        with self._on_comm():
+            gather(self.moments_all, local, self.world, self.pg)
+            N.call(combine, self.dev.index, N.ptr(self.moments_all), self.world, N.ptr(self.stats), *block,
+                   self._s())
+            if self._comm is not None:
+                self._stats_event.record(self._comm)
+        self._stats_pending = self._comm is not None
 
     def popart_rescale(self):
         """dxrl_pg_popart_rescale: the critic's head (master and pack) from the units the popart
@@ -680,16 +687,7 @@ class PGTrainer:
             N.call("dxrl_pg_gae", self.dev.index, N.ptr(self.rew), N.ptr(self.done), N.ptr(self.V[0]), self.n,
                    self.T, c.gamma, c.lam, N.ptr(self.adv), N.ptr(self.ret), N.ptr(self.partial), N.ptr(self.stats),
                    self._s())
-        # every rank's (count, mean, M2) in rank order, merged on device (identical on all ranks);
-        # one rank: dxrl_pg_gae already wrote the combined statistics
-        if self.collective:
-            with self._on_comm():
-                gather_adv_moments_(self.moments_all, self.stats, self.world, self.pg)
-                N.call("dxrl_pg_adv_combine", self.dev.index, N.ptr(self.moments_all), self.world,
-                       N.ptr(self.stats), self._s())
-                if self._comm is not None:
-                    self._stats_event.record(self._comm)
-            self._stats_pending = self._comm is not None
+        self._combine_ranks(gather_adv_moments_, self.stats, "dxrl_pg_adv_combine")
 
     def _on_comm(self):
         """Context for an exchange: the comm stream (after everything enqueued so far on the

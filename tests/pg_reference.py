@@ -49,7 +49,7 @@ def mlp_forward(X, Wd, net, bf16):
 
 
 def gae_uses_segmented_scan(T):
-    """dxrl_pg_gae's kernel choice (csrc/dxrl_pg.hip): k_gae_lds (segmented scan) while the horizon's
+    """dxrl_pg_gae's kernel choice (csrc/dxrl_pg_gae.hip): k_gae_lds (segmented scan) while the horizon's
     LDS staging fits 152 KiB, else k_gae (one sequential chain per env)."""
     pitch = (T + 7) // 8 * 8 + 4
     return 16 * (12 * pitch + 4 * T) <= 152 * 1024

@@ -306,7 +306,7 @@ def test_32_env_kernel_equals_16_env_kernel_at_full_size(pkg, name):
 def test_normalisation_large_mean(pkg):
     """The normalisation moments with |mean| / std > 1e3 (every step its own episode,
     A = r - V, rewards shifted by 1e4): a one-pass sum(a^2) - mean sum(a) lost 2.8e-6 of
-    the std here; the merged (count, mean, M2) moments (k_gae / k_gae_sums /
+    the std here; the merged (count, mean, M2) moments (k_gae / k_gae_finish /
     k_stats_combine) match a two-pass f64 reduction of the kernel's advantages to 1e-9."""
     dev = torch.device("cuda", 0)
     env, tr = pkg.workloads.build_pg_workload("easy", dev)

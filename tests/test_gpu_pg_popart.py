@@ -1,5 +1,5 @@
 """GPU: dxrl_pg_popart_rescale (csrc/dxrl_pg.hip k_popart_rescale) and the forgetting factor of the
-value-normalisation fold (vnorm_fold, behind k_gae_sums_vn and k_vnorm_combine) through ctypes
+value-normalisation fold (vnorm_fold, behind k_gae_finish and k_vnorm_combine) through ctypes
 against the restatement (tests/pg_popart_reference.py).  The rescale kernel has one shape, so its
 cases are states."""
 import ctypes as C

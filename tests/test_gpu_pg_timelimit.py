@@ -1,4 +1,4 @@
-"""GPU: dxrl_pg_gae_timelimit (csrc/dxrl_pg.hip, k_gae_lds<true> / k_gae<true>) through ctypes
+"""GPU: dxrl_pg_gae_timelimit (csrc/dxrl_pg_gae.hip, k_gae_lds<true, false> / k_gae<true, false>) through ctypes
 against its restatement (tests/pg_timelimit_reference.py), at the smallest shapes that reach each
 code path of the two kernels."""
 import ctypes as C

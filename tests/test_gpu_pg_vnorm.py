@@ -1,5 +1,5 @@
-"""GPU: dxrl_pg_gae_vnorm and dxrl_pg_vnorm_combine (csrc/dxrl_pg.hip: the value-normalisation
-instantiations of k_gae_lds / k_gae, k_gae_sums_vn, k_vnorm_combine) through ctypes against the
+"""GPU: dxrl_pg_gae_vnorm and dxrl_pg_vnorm_combine (csrc/dxrl_pg_gae.hip: the value-normalisation
+instantiations of k_gae_lds / k_gae, k_gae_finish, k_vnorm_combine) through ctypes against the
 plain entries and the restatement (tests/pg_vnorm_reference.py), at the smallest shapes that reach
 each code path of the two scan kernels, in both tape forms."""
 import ctypes as C

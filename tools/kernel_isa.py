@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dexterous-rl-manipulation_amd"))
 import build as B  # noqa: E402
 
-UNITS = ["dxrl_env", "dxrl_rollout", "dxrl_pg", "dxrl_pg_rollout16", "dxrl_pg_rollout8", "dxrl_eval", "dxrl_eval_mlp"]
+UNITS = ["dxrl_env", "dxrl_rollout", "dxrl_pg", "dxrl_pg_gae", "dxrl_pg_rollout16", "dxrl_pg_rollout8", "dxrl_eval", "dxrl_eval_mlp"]
 FIELDS = ["VGPRs", "AGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]",
           "Occupancy [waves/SIMD]"]
 
